@@ -11,11 +11,17 @@ The headline runs at the north star's accuracy (float32 arithmetic of the Keras 
 accumulation; measured at least as accurate as exact-fp32 MFMA), fp32 = exact-fp32 MFMA everywhere, bf16 = the
 reduced-precision path (a leg at N = 1, with its parity against the 1e-4 bound).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--dump-outputs DIR]
+    python bench.py --full [...]             (the headline, then everything else this file measures)
     python bench.py --e2e [--steps K]        (BASELINE configs[4], its own JSON line)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  At N = 1 the line also carries the other BASELINE
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(metric, value, unit, ms_per_step, dtype, the range guard's verdict on the timed batches, the per-window spread).
+--dump-outputs DIR then writes what the last timed step computed (DIR/out.npy, DIR/mel.npy, float32; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output).  --full adds, after the timed
+steps, the dominant kernel's roofline and per-stage breakdown (live HIP-event profile + committed PMC profile), the
+blocking checked form's throughput, the parity against the float64 oracle and, at N = 1, the other BASELINE
 configs as extra legs, each timed with HIP events on the stream its kernels run on:
   configs[1] STFT only, 4096 segments, >= 4 rotated buffer sets (past the 256 MB MALL) -> HBM roofline
   configs[2] audio branch fp32, batch 256, all-zero video (embedding computed once)   -> fp32 MFMA roofline
@@ -89,6 +95,22 @@ def synth(rng, B, video=True):
     audio = np.clip(np.round(audio), -32768, 32767).astype(np.float32)
     vid = rng.integers(0, 256, (B, 128, 128, 5), dtype=np.uint8).astype(np.float32) if video else None
     return audio, vid
+
+
+DUMP_BUDGET = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32, at most 64 MB in all.  An array larger than its
+    share of that budget is cut to a seeded sample of its leading-axis entries (sorted; the same ones on every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // len(arrays) - 4096          # .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = share // max(1, a[:1].nbytes)
+        if keep < len(a):
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_summary(B, dtype):
@@ -353,7 +375,7 @@ def run_e2e(args, world, rank, dev, model, dist_on):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -362,6 +384,8 @@ def run_e2e(args, world, rank, dev, model, dist_on):
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"enhanced": last.cpu().numpy()})      # [U, samples] enhanced speech
     clips = U * S
     stage = {}
     for _ in range(3):
@@ -397,6 +421,70 @@ def run_e2e(args, world, rank, dev, model, dist_on):
         print(json.dumps(res), flush=True)
 
 
+def roofline_report(args, dw, audio, video, mean, std, mel, out, B, ms_per_step):
+    """--full: the headline result's `roofline` (the dominant kernel, v_conv2) and `breakdown` (per-stage times), from
+    --profile-reps profiled passes over the timed step's own buffers after the timed steps."""
+    # ---- live per-kernel durations (HIP events on the launch stream) for the roofline ----
+    stage_ms = {}
+    for _ in range(args.profile_reps):
+        ops.spectrogram(audio, frames_per_slice=20, out=mel)
+        _, st = ops.forward_profile(dw, mel.view(B, 80, 20), video, mean, std, out=out)
+        for k, v in st.items():
+            stage_ms[k] = stage_ms.get(k, 0.0) + v / args.profile_reps
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.profile_reps):
+        ops.spectrogram(audio, frames_per_slice=20, out=mel)
+    e1.record()
+    torch.cuda.synchronize()
+    stft_ms = e0.elapsed_time(e1) / args.profile_reps
+
+    dom = "v_conv2"
+    achieved = FLOP_V_CONV2 * B / (stage_ms[dom] * 1e-3) / 1e12
+    peak = PEAK_TFLOPS[args.dtype]
+    pmc_file, pmc, pmc_status = pmc_summary(B, args.dtype)
+    kp = (pmc or {}).get("kernels", {}).get(dom, {})
+    # rocprof average over the headline-batch launches of the profiled run (kernel trace filtered by grid: the --stats
+    # average also counts the configs[2] leg's one-clip zero-video launch; tools/pmc_summary.py)
+    ksym, rp_ms = kernel_stat((pmc or {}).get("kernel_trace_headline_avg_ms"), args.dtype)
+    _, rp_all_ms = kernel_stat((pmc or {}).get("kernel_stats_avg_ms"), args.dtype)
+    fwd_ms = sum(stage_ms.values())
+    kdesc = {"bf16": "k_conv_stream<5,16,16,1> bf16: persistent warp-specialised implicit GEMM M=4096/clip N=128 "
+                     "K=3200, fused BN+LReLU+2x2 maxpool",
+             "fp32_split": "k_conv_stream<5,16,16,1,S16>: the persistent warp-specialised implicit GEMM (M=4096/clip "
+                           "N=128 K=3200, fused BN+LReLU+2x2 maxpool) on split-f16 operands, 3 f16 MFMA products per "
+                           "fp32 MAC; peak = dense f16 MFMA peak / 3",
+             "fp32": "k_conv<float,128> implicit GEMM, exact-fp32 MFMA"}[args.dtype]
+    roofline = {"kernel": f"{dom} ({kdesc})", "kernel_symbol": ksym or KERNEL_PATTERN[args.dtype],
+                "bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": kp.get("traffic_bytes"),
+                "algorithmic_bytes": kp.get("algorithmic_bytes"),
+                "mfma_busy_frac": kp.get("mfma_busy_frac"), "eff_clock_ghz": kp.get("eff_clock_ghz"),
+                "pmc_source": pmc_file, "pmc_status": pmc_status or "source digest matches this tree",
+                "source_digest": _lib.source_digest(),
+                "per_launch_flop": FLOP_V_CONV2 * B, "avg_launch_ms": round(stage_ms[dom], 4),
+                "timing": "avg_launch_ms: HIP events on the launch stream in this run; avg_launch_ms_rocprof / "
+                          "frac_rocprof: rocprofv3 --kernel-trace average of the same source tree's B = 512 "
+                          "launches (profiles/<tag>_pmc.json kernel_trace_headline_avg_ms, a separate profiled "
+                          "run); avg_launch_ms_rocprof_stats: the --stats average over every launch of the symbol "
+                          "(profiles/<tag>_kernel_stats.csv), which also counts the configs[2] leg's N = 1 launch",
+                "avg_launch_ms_rocprof": rp_ms,
+                "frac_rocprof": round(FLOP_V_CONV2 * B / (rp_ms * 1e-3) / 1e12 / peak, 4) if rp_ms else None,
+                "avg_launch_ms_rocprof_stats": rp_all_ms,
+                "frac_pmc_profiled": (round(FLOP_V_CONV2 * B / (kp["profiled_ns"] * 1e-9) / 1e12 / peak, 4)
+                                      if kp.get("profiled_ns") else None),
+                "achieved_vs_fp32_mfma_peak": round(achieved / PEAK_TFLOPS["fp32"], 4)}
+    breakdown = {
+        "stft_ms": round(stft_ms, 4),
+        "stft_hbm_gbs": round(STFT_BYTES_PER_CLIP * B / (stft_ms * 1e-3) / 1e9, 1),
+        "forward_ms": round(fwd_ms, 4),
+        "forward_tflops": round(FLOP_PER_CLIP * B / (fwd_ms * 1e-3) / 1e12, 2),
+        "step_frac_of_peak": round(FLOP_PER_CLIP * B / (ms_per_step * 1e-3) / 1e12 / peak, 4),
+        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+    }
+    return roofline, breakdown
+
+
 def _local_store():
     """A TCP rendezvous on 127.0.0.1 for a one-rank group started without a launcher (--rccl)."""
     import socket
@@ -426,12 +514,18 @@ def main():
     ap.add_argument("--strong", action="store_true", help="split a fixed global batch of --batch clips over the ranks")
     ap.add_argument("--dtype", default="fp32_split", choices=["fp32_split", "fp32", "bf16"],
                     help="headline compute dtype (fp32_split / fp32 meet the north star's 1e-4 RMS; bf16 does not)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: the blocking checked form, the live "
+                         "per-kernel profile and roofline, the configs[1] / configs[2] / dtype / training legs, the CPU "
+                         "baseline and the parity against the oracle (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline / parity")
     ap.add_argument("--graph", action="store_true", help="the forward replays a hipGraph per argument set (option graph)")
     ap.add_argument("--checked", action="store_true",
                     help="fp32_split: avse_forward_checked per step (default: avse_forward, the sticky range guard read "
                          "once after the timed steps)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the configs[1] / configs[2] legs")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the configs[1] / configs[2] legs")
     ap.add_argument("--profile-reps", type=int, default=5)
     ap.add_argument("--e2e", action="store_true", help="BASELINE configs[4]: end-to-end predict, utterance-sharded")
     ap.add_argument("--utterances", type=int, default=E2E_UTTERANCES)
@@ -442,6 +536,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start one rank per GPU as a child torch.distributed.run
         # (nothing in this process has touched the GPU yet) and exit with its status
@@ -551,6 +647,13 @@ def main():
     value = global_batch * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
     timed_out = out.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives: the predicted spectrograms, the mel-dB spectrograms the STFT
+        # wrote, and with collectives on the all-gathered predictions
+        arrays = {"out": timed_out, "mel": mel.view(B, 80, 20).cpu().numpy()}
+        if dist_on:
+            arrays["gathered"] = gathered.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     bits = pipe.bits | dw.ctx.range_status() | (dw.last_range_bits if checked else 0)
     if dist_on:
         every = [0] * world
@@ -564,7 +667,7 @@ def main():
                            "per step, one step later (ops.RangePipeline: avse_range_snapshot + event, read while the "
                            "next step runs; a flagged batch is recomputed on the exact-fp32 kernels)",
                    "act_exponents_nonzero": {k: v for k, v in dw.act_exponents().items() if v}}
-    if args.dtype == "fp32_split" and world == 1 and not checked:
+    if args.full and args.dtype == "fp32_split" and world == 1 and not checked:
         # the per-batch checked path (what speech_enhancer predict / pipeline.Enhancer run), same batch, 20 steps
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -575,37 +678,6 @@ def main():
         range_guard["blocking_checked_per_step_clips_per_s"] = round(B * 20 / (time.perf_counter() - t1), 1)
         range_guard["blocking_checked_per_step_bits"] = dw.last_range_bits
 
-    # ---- live per-kernel durations (HIP events on the launch stream) for the roofline ----
-    stage_ms = {}
-    for _ in range(args.profile_reps):
-        ops.spectrogram(audio, frames_per_slice=20, out=mel)
-        _, st = ops.forward_profile(dw, mel.view(B, 80, 20), video, mean, std, out=out)
-        for k, v in st.items():
-            stage_ms[k] = stage_ms.get(k, 0.0) + v / args.profile_reps
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.profile_reps):
-        ops.spectrogram(audio, frames_per_slice=20, out=mel)
-    e1.record()
-    torch.cuda.synchronize()
-    stft_ms = e0.elapsed_time(e1) / args.profile_reps
-
-    dom = "v_conv2"
-    achieved = FLOP_V_CONV2 * B / (stage_ms[dom] * 1e-3) / 1e12
-    peak = PEAK_TFLOPS[args.dtype]
-    pmc_file, pmc, pmc_status = pmc_summary(B, args.dtype)
-    kp = (pmc or {}).get("kernels", {}).get(dom, {})
-    # rocprof average over the headline-batch launches of the profiled run (kernel trace filtered by grid: the --stats
-    # average also counts the configs[2] leg's one-clip zero-video launch; tools/pmc_summary.py)
-    ksym, rp_ms = kernel_stat((pmc or {}).get("kernel_trace_headline_avg_ms"), args.dtype)
-    _, rp_all_ms = kernel_stat((pmc or {}).get("kernel_stats_avg_ms"), args.dtype)
-    fwd_ms = sum(stage_ms.values())
-    kdesc = {"bf16": "k_conv_stream<5,16,16,1> bf16: persistent warp-specialised implicit GEMM M=4096/clip N=128 "
-                     "K=3200, fused BN+LReLU+2x2 maxpool",
-             "fp32_split": "k_conv_stream<5,16,16,1,S16>: the persistent warp-specialised implicit GEMM (M=4096/clip "
-                           "N=128 K=3200, fused BN+LReLU+2x2 maxpool) on split-f16 operands, 3 f16 MFMA products per "
-                           "fp32 MAC; peak = dense f16 MFMA peak / 3",
-             "fp32": "k_conv<float,128> implicit GEMM, exact-fp32 MFMA"}[args.dtype]
     result = {
         "metric": METRIC,
         "value": round(value, 1),
@@ -626,36 +698,12 @@ def main():
                                "(BASELINE configs[3]) on 200-ms@16kHz clips",
                    "global_batch": global_batch, "per_gpu_batch": B, "parallelism": f"dp{world}"},
         "window_ms_per_step": win.summary(),
-        "roofline": {"kernel": f"{dom} ({kdesc})", "kernel_symbol": ksym or KERNEL_PATTERN[args.dtype],
-                     "bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": kp.get("traffic_bytes"),
-                     "algorithmic_bytes": kp.get("algorithmic_bytes"),
-                     "mfma_busy_frac": kp.get("mfma_busy_frac"), "eff_clock_ghz": kp.get("eff_clock_ghz"),
-                     "pmc_source": pmc_file, "pmc_status": pmc_status or "source digest matches this tree",
-                     "source_digest": _lib.source_digest(),
-                     "per_launch_flop": FLOP_V_CONV2 * B, "avg_launch_ms": round(stage_ms[dom], 4),
-                     "timing": "avg_launch_ms: HIP events on the launch stream in this run; avg_launch_ms_rocprof / "
-                               "frac_rocprof: rocprofv3 --kernel-trace average of the same source tree's B = 512 "
-                               "launches (profiles/<tag>_pmc.json kernel_trace_headline_avg_ms, a separate profiled "
-                               "run); avg_launch_ms_rocprof_stats: the --stats average over every launch of the symbol "
-                               "(profiles/<tag>_kernel_stats.csv), which also counts the configs[2] leg's N = 1 launch",
-                     "avg_launch_ms_rocprof": rp_ms,
-                     "frac_rocprof": round(FLOP_V_CONV2 * B / (rp_ms * 1e-3) / 1e12 / peak, 4) if rp_ms else None,
-                     "avg_launch_ms_rocprof_stats": rp_all_ms,
-                     "frac_pmc_profiled": (round(FLOP_V_CONV2 * B / (kp["profiled_ns"] * 1e-9) / 1e12 / peak, 4)
-                                           if kp.get("profiled_ns") else None),
-                     "achieved_vs_fp32_mfma_peak": round(achieved / PEAK_TFLOPS["fp32"], 4)},
-        "breakdown": {
-            "stft_ms": round(stft_ms, 4),
-            "stft_hbm_gbs": round(STFT_BYTES_PER_CLIP * B / (stft_ms * 1e-3) / 1e9, 1),
-            "forward_ms": round(fwd_ms, 4),
-            "forward_tflops": round(FLOP_PER_CLIP * B / (fwd_ms * 1e-3) / 1e12, 2),
-            "step_frac_of_peak": round(FLOP_PER_CLIP * B / (ms_per_step * 1e-3) / 1e12 / peak, 4),
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-        },
     }
+    if args.full:
+        result["roofline"], result["breakdown"] = roofline_report(args, dw, audio, video, mean, std, mel, out, B,
+                                                                  ms_per_step)
     outs = {args.dtype: timed_out}
-    if rank == 0 and world == 1 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_legs:
         result["legs"] = {}
         for ldt in ("fp32", "fp32_split", "bf16"):
             if ldt != args.dtype:
@@ -663,7 +711,7 @@ def main():
         result["legs"].update({"stft_b4096": leg_stft(dev), "audio_fp32_b256": leg_audio_fp32(dev, model),
                                "audio_fp32_split_b256": leg_audio_fp32(dev, model, dtype="fp32_split"),
                                "train_fp32_b16": leg_train(dev, model)})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the same 16 clips through a dB-scale copy of the model in every dtype timed (north star bound on dB outputs)
         dbm, db_outs = db_scaled(model), {}
         ops.spectrogram(audio, frames_per_slice=20, out=mel)

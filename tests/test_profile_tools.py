@@ -34,6 +34,27 @@ def test_bench_finds_the_dominant_kernel_by_pattern():
     assert bench.kernel_stat({}, "fp32_split") == (None, None)
 
 
+def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: <name>.npy per array in float32; an array over its share of the 64 MB budget is cut to the same
+    sorted sample of leading-axis entries on every call, a small one is written whole."""
+    import numpy as np
+    bench = _load("bench_under_test", "bench.py")
+    rng = np.random.default_rng(3)
+    small = rng.normal(size=(7, 80, 20))                                   # float64 in, float32 out
+    big = np.arange(1000, dtype=np.float32)[:, None] + np.zeros((1, 25000), np.float32)     # 100 MB, row i holds i
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], small.astype(np.float32))
+    assert got["big"].dtype == np.float32 and got["big"].shape[1:] == big.shape[1:]
+    rows = got["big"][:, 0]
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)             # a sorted sample without repeats
+    assert np.array_equal(got["big"], big[rows.astype(int)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_pmc_summary_names_mangled_half_instantiations():
     pmc = _load("pmc_summary_under_test", "tools/pmc_summary.py")
     assert pmc.short("_ZN4avse12_GLOBAL__N_16k_convIDF16_Li64ELb1ELb1EEEvNS_8ConvArgsE") == \

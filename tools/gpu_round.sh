@@ -10,7 +10,7 @@ timeout -k 10 1100 python -u -m pytest tests -m gpu -v -rP --timeout 300 --timeo
 rc=$?
 echo "pytest rc=$rc"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit $?
+timeout -k 10 400 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit $?
 echo bench ok
 timeout -k 10 300 python bench.py --e2e --steps 5 --warmup 2 > $OUT/bench_e2e_$TAG.json 2> $OUT/bench_e2e_$TAG.err || exit $?
 echo e2e ok

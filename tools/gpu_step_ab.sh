@@ -7,7 +7,7 @@ O=gpurun_out/step_ab.log; : > $O
 IFS='|' read -ra CFGS <<< "$ENVS"
 for c in "${CFGS[@]}"; do
   echo "== $c" >> $O
-  env $c timeout -k 10 180 python bench.py --steps 30 --warmup 5 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])" >> $O || exit 1
+  env $c timeout -k 10 180 python bench.py --full --steps 30 --warmup 5 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])" >> $O || exit 1
 done
 if [ -n "$TRACE" ]; then
   ROOT=$(pwd); OUT=$ROOT/gpurun_out/trace_step; mkdir -p $OUT

@@ -155,7 +155,7 @@ def main():
     avse_pkg.load()
     from avse_amd import _lib
     res = {"tag": tag, "batch": 512, "source_digest": _lib.source_digest(),
-           "source": "rocprofv3 --kernel-trace --stats of `bench.py --steps 20` (kernel_stats_avg_ms, by kernel "
+           "source": "rocprofv3 --kernel-trace --stats of `bench.py --full --steps 20` (kernel_stats_avg_ms, by kernel "
            "symbol); --pmc passes FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES+GRBM_GUI_ACTIVE over "
            "tools/fwd_loop.py (B=512 spectrogram + forward, AVSE_DTYPE per dtype) and FETCH_SIZE | WRITE_SIZE over "
            "AVSE_MODE=stft (B=4096, 5 rotated buffer sets)",

@@ -14,7 +14,7 @@ mkdir -p $OUT
 rm -rf $OUT/prof_$TAG $OUT/pmc_${TAG}_*
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- \
-    python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_${TAG}_bench.log 2>&1
+    python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_${TAG}_bench.log 2>&1
 for dt in fp32_split bf16; do
     lib=$dt; [ $dt = fp32_split ] && lib=float32_split
     for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "mfma:SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
