@@ -69,6 +69,9 @@ SIGNATURES = {
                             _c_void_p]),
     "avse_video_normalize": (_int, [_c_void_p, _c_void_p, _i64, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p]),
     "avse_mse": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "avse_mix_pairs": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _c_void_p,
+                              _c_void_p, _c_void_p, _c_void_p]),
+    "avse_video_stats": (_int, [_c_void_p, _c_void_p, _i64, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p]),
     "avse_forward_checked": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
                                     _c_void_p, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "avse_range_status": (_int, [_c_void_p, _c_void_p, ctypes.POINTER(ctypes.c_uint32)]),

@@ -385,4 +385,18 @@ int launch_video_normalize(float* video, int64_t S, int H, int W, int F, const f
                            const float* stdv, hipStream_t s);
 int launch_mse(const float* a, const float* b, int64_t n, float* loss, float* partial, hipStream_t s);
 
+// ---- device-side preprocess (prep.hip) ---------------------------------------------------
+// avse_mix_pairs: exact integer powers (64-bit integer atomics into `scratch`), the float64 gain of
+// AudioMixer.snr_factor, then the mixture / speech / scaled-noise rows.  scratch: mix_pairs_scratch_bytes(U) bytes.
+size_t mix_pairs_scratch_bytes(int64_t n_pairs);
+int launch_mix_pairs(const int16_t* speech, const int64_t* speech_off, const int16_t* noise, const int64_t* noise_off,
+                     const double* snr_lin, int64_t n_pairs, int64_t L, float* rows, double* mix64, double* factor,
+                     void* scratch, hipStream_t s);
+// avse_video_stats: per-pixel float64 moments about the pixel's first value, partials per chunk of slices in
+// `scratch` (video_stats_scratch_bytes), combined in chunk order.  F <= kVideoStatsMaxF.
+constexpr int kVideoStatsMaxF = 8;
+size_t video_stats_scratch_bytes(int64_t S, int H, int W);
+int launch_video_stats(const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv, void* scratch,
+                       hipStream_t s);
+
 }  // namespace avse

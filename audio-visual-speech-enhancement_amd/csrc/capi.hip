@@ -142,6 +142,8 @@ struct avse_ctx {
     unsigned* range_host = nullptr;   // pinned readback word
     char* arena = nullptr;
     size_t arena_bytes = 0;
+    char* prep = nullptr;       // avse_mix_pairs / avse_video_stats scratch (power words, per-chunk moments)
+    size_t prep_bytes = 0;
     NetPlan last_plan = kPlan25;    // the network shape of the last forward (avse_debug_scratch's arena layout)
     // side stream for the audio branch of the forward (runs concurrently with the video encoder)
     hipStream_t side = nullptr;
@@ -351,6 +353,24 @@ int ensure_arena(avse_ctx* c, int64_t clips, int dtype, const NetPlan& p, hipStr
     c->arena_bytes = 0;
     if (hipMalloc((void**)&c->arena, need) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (forward scratch)");
     c->arena_bytes = need;
+    return 0;
+}
+
+// grows the preprocess scratch (avse_mix_pairs, avse_video_stats), like the arena never inside a capture
+int ensure_prep(avse_ctx* c, size_t need, hipStream_t s) {
+    if (need <= c->prep_bytes) return 0;
+    if (s) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        AVSE_HIP_CHECK(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(AVSE_ERR_INVALID, "the preprocess scratch would grow while the stream is being captured: run "
+                                          "one call of this size before the capture");
+    }
+    if (c->prep) (void)hipFree(c->prep);
+    c->prep = nullptr;
+    c->prep_bytes = 0;
+    if (hipMalloc((void**)&c->prep, need) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (preprocess scratch)");
+    c->prep_bytes = need;
     return 0;
 }
 
@@ -1064,6 +1084,7 @@ void avse_ctx_destroy(avse_ctx* c) {
     (void)hipHostFree(c->range_host);
     (void)hipFree(c->zero_video);
     (void)hipFree(c->arena);
+    (void)hipFree(c->prep);
     for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
     if (c->cap) (void)hipStreamDestroy(c->cap);
     if (c->side) (void)hipStreamDestroy(c->side);
@@ -1871,6 +1892,30 @@ int avse_mse(avse_ctx* c, const float* pred, const float* target, int64_t n, flo
     if (n <= 0) return fail(AVSE_ERR_INVALID, "n must be positive");
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     return launch_mse(pred, target, n, loss, c->mse_partial, (hipStream_t)stream);
+}
+
+int avse_mix_pairs(avse_ctx* c, const int16_t* speech, const int64_t* speech_off, const int16_t* noise,
+                   const int64_t* noise_off, const double* snr_lin, int64_t n_pairs, int64_t L, float* rows,
+                   double* mix64, double* factor, void* stream) {
+    if (!c || !speech || !speech_off || !noise || !noise_off || !rows) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (n_pairs < 0 || L <= 0) return fail(AVSE_ERR_INVALID, "bad mix_pairs shape (n_pairs >= 0, L > 0)");
+    if (L >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "L must be below 2^31 samples");
+    if (n_pairs == 0) return 0;
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = ensure_prep(c, mix_pairs_scratch_bytes(n_pairs), (hipStream_t)stream)) return rc;
+    return launch_mix_pairs(speech, speech_off, noise, noise_off, snr_lin, n_pairs, L, rows, mix64, factor, c->prep,
+                            (hipStream_t)stream);
+}
+
+int avse_video_stats(avse_ctx* c, const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv,
+                     void* stream) {
+    if (!c || !video || !mean || !stdv) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (S <= 0 || H <= 0 || W <= 0 || F <= 0) return fail(AVSE_ERR_INVALID, "bad video shape (every extent positive)");
+    if (F > kVideoStatsMaxF) return fail(AVSE_ERR_UNSUPPORTED, "more than 8 frames per slice not supported");
+    if ((int64_t)H * W * F >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "H * W * F must be below 2^31");
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = ensure_prep(c, video_stats_scratch_bytes(S, H, W), (hipStream_t)stream)) return rc;
+    return launch_video_stats(video, S, H, W, F, mean, stdv, c->prep, (hipStream_t)stream);
 }
 
 int avse_debug_scratch(avse_ctx* c, int64_t N, int dtype, void** base, int64_t* offsets) {

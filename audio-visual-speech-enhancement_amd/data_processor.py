@@ -72,6 +72,69 @@ def preprocess_audio_batch(signals, sample_rate, slice_duration_ms, n_video_slic
                            frames_per_slice=g["spectrogram_samples_per_slice"])
 
 
+def _mono_int16(audio_signal, what):
+    """The samples of an AudioSignal holding mono int16 data (what wav files of the corpora give), else TypeError."""
+    data = np.asarray(audio_signal.get_data())
+    if data.dtype != np.int16:
+        raise TypeError(f"{what}: the batched path takes int16 samples, got {data.dtype}")
+    if data.ndim != 2 or data.shape[1] != 1:
+        raise TypeError(f"{what}: the batched path takes mono signals, got {data.shape[1:]} channels")
+    return data[:, 0]
+
+
+def _per_pair(value, n):
+    """A per-pair argument of preprocess_audio_pairs: one value for every pair, or a sequence of n."""
+    if np.ndim(value) == 0:
+        return [value] * n
+    if len(value) != n:
+        raise ValueError(f"{len(value)} values for {n} pairs")
+    return list(value)
+
+
+def pair_groups(speech_signals, slice_duration_ms, n_video_slices, video_frame_rate):
+    """The pairs that preprocess as one batch: those with one (signal_length, n_fft, sample_rate), the geometry of
+    frame_geometry.  Returns [((signal_length, n_fft, sample_rate), [pair indices])], groups in first-seen order and
+    the indices of a group in input order."""
+    n = len(speech_signals)
+    groups = {}
+    for i, (sig, ns, fps) in enumerate(zip(speech_signals, _per_pair(n_video_slices, n),
+                                           _per_pair(video_frame_rate, n))):
+        g = frame_geometry(sig.get_sample_rate(), slice_duration_ms, ns, fps)
+        groups.setdefault((g["signal_length"], g["n_fft"], sig.get_sample_rate()), []).append(i)
+    return list(groups.items())
+
+
+def preprocess_audio_pairs(speech_signals, noise_signals, slice_duration_ms, n_video_slices, video_frame_rate,
+                           snr_db=0):
+    """The batched preprocess_audio_pair (data_processor.py:119-139): per pair_groups group ONE ops.mix_pairs (noise
+    looped to the speech, SNR gain, mixture, pad / truncate, all on the device) and ONE ops.spectrogram over the
+    group's 3 U rows, instead of float64 numpy mixing and three one-utterance STFT launches per pair.
+
+    speech_signals / noise_signals: AudioSignals holding mono int16 samples (TypeError otherwise, so that a caller can
+    fall back to the per-sample path); n_video_slices, video_frame_rate, snr_db: one value, or one per pair.
+    Returns per pair (mixed, speech, noise slice stacks [n_slices, 80, spf] float32, mixed AudioSignal of float64
+    [signal_length, 1] samples): the shapes, dtypes and values of the per-sample path."""
+    n = len(speech_signals)
+    if len(noise_signals) != n:
+        raise ValueError(f"{n} speech signals but {len(noise_signals)} noise signals")
+    speech = [_mono_int16(s, "speech %d" % i) for i, s in enumerate(speech_signals)]
+    noise = [_mono_int16(s, "noise %d" % i) for i, s in enumerate(noise_signals)]
+    n_slices, fps, snr = _per_pair(n_video_slices, n), _per_pair(video_frame_rate, n), _per_pair(snr_db, n)
+    out = [None] * n
+    for (L, n_fft, sr), idx in pair_groups(speech_signals, slice_duration_ms, n_slices, fps):
+        g = frame_geometry(sr, slice_duration_ms, n_slices[idx[0]], fps[idx[0]])
+        U = len(idx)
+        rows, mix64, _ = ops.mix_pairs([speech[i] for i in idx], [noise[i] for i in idx], L,
+                                       snr_db=[snr[i] for i in idx])
+        stacks = ops.spectrogram(rows.view(3 * U, L), sample_rate=sr, n_fft=n_fft, hop_length=g["hop_length"],
+                                 n_mels=N_MELS, fmin=MEL_FMIN, fmax=MEL_FMAX,
+                                 frames_per_slice=g["spectrogram_samples_per_slice"]).cpu().numpy()
+        mix64 = mix64.cpu().numpy()
+        for k, i in enumerate(idx):
+            out[i] = (stacks[k], stacks[U + k], stacks[2 * U + k], AudioSignal(mix64[k], sr))
+    return out
+
+
 def reconstruct_speech_signal(mixed_signal, speech_spectrograms, video_frame_rate):
     """data_processor.py:60-74: phase of the mixture's STFT + predicted speech mel-dB slices
     [n_slices, 80, spf] -> AudioSignal (K1 for the phase, K6 for the inverse)."""
@@ -124,6 +187,15 @@ class VideoNormalizer(object):
         obj.__mean_image = np.asarray(mean_image, np.float32)
         obj.__std_image = np.asarray(std_image, np.float32)
         return obj
+
+    @classmethod
+    def fit_device(cls, video_tensor):
+        """The fit of __init__ for a [S, H, W, F] float32 ROCm tensor, on the device: one streaming read
+        (ops.video_stats, float64 sums per pixel) instead of a copy to the host and two numpy passes.  The images
+        are np.mean / np.std over axes (0, 3) evaluated in float64 and rounded once to float32 — within a float32
+        ulp or two of __init__'s float32 numpy arithmetic, not its bits."""
+        mean, std = ops.video_stats(video_tensor)
+        return cls.from_stats(mean.cpu().numpy(), std.cpu().numpy())
 
     def save(self, path):
         """The fitted images as .npz (the reference pickles the object: speech_enhancer.py:48-49)."""

@@ -313,6 +313,125 @@ def video_normalize_(video, mean, std):
     return video
 
 
+def video_stats(video):
+    """VideoNormalizer's fit (data_processor.py:203-206) on the device: video [S, H, W, F] float32 device tensor ->
+    (mean [H, W], std [H, W]) float32 device tensors, np.mean / np.std over axes (0, 3) from one streaming read
+    (float64 sums about each pixel's first value, include/avse.h avse_video_stats)."""
+    _dev_f32(video, "video")
+    if video.dim() != 4:
+        raise ValueError("video must be [slices, height, width, frames_per_slice]")
+    S, H, W, F = video.shape
+    if 0 in (S, H, W, F):
+        raise ValueError("video_stats of an empty video")
+    mean = torch.empty((H, W), dtype=torch.float32, device=video.device)
+    std = torch.empty((H, W), dtype=torch.float32, device=video.device)
+    ctx = _lib.context(video.device)
+    with torch.cuda.device(video.device):
+        _lib.check(_lib.load().avse_video_stats(ctx.handle, _lib.ptr(video), S, H, W, F, _lib.ptr(mean), _lib.ptr(std),
+                                                _lib.stream_handle(video.device)), "avse_video_stats")
+    return mean, std
+
+
+def _is_packed(x):
+    """A (samples tensor, int64 offsets) tuple, as against a sequence of signals (whose entries must be int16)."""
+    if not (isinstance(x, tuple) and len(x) == 2 and isinstance(x[0], torch.Tensor)):
+        return False
+    dt = x[1].dtype if isinstance(x[1], (torch.Tensor, np.ndarray)) else np.asarray(x[1]).dtype
+    return dt in (torch.int64, np.dtype(np.int64))
+
+
+def _int16_signals(x, name):
+    """The host-side check of mix_pairs' signal arguments, before anything touches a device: a sequence of mono int16
+    signals (1-D, or [n, 1]; numpy or tensors) -> (list of 1-D signals, int64 offsets [U + 1]); or an already packed
+    pair (1-D int16 device tensor, int64 offsets) -> (tensor, offsets).  Anything else is a TypeError."""
+    if _is_packed(x):
+        packed, off = x
+        if packed.dtype != torch.int16:
+            raise TypeError(f"{name}: the packed samples must be int16, got {packed.dtype}")
+        if not packed.is_cuda or not packed.is_contiguous():
+            raise TypeError(f"{name}: the packed samples must be a contiguous ROCm device tensor")
+        off = np.ascontiguousarray(np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off), dtype=np.int64)
+        if off.ndim != 1 or off.size < 1 or off[0] < 0 or np.any(np.diff(off) < 0) or off[-1] > packed.numel():
+            raise ValueError(f"{name}: offsets must be [U + 1] non-decreasing element offsets into the packed samples")
+        return packed, off
+    sigs = []
+    for k, a in enumerate(x):
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+        dt = a.dtype
+        if dt not in (torch.int16, np.dtype(np.int16)):
+            raise TypeError(f"{name}[{k}] must hold int16 samples, got {dt}")
+        if a.ndim == 2 and a.shape[1] == 1:
+            a = a[:, 0]
+        if a.ndim != 1:
+            raise TypeError(f"{name}[{k}] must be one channel of samples, got shape {tuple(a.shape)}")
+        sigs.append(a)
+    off = np.zeros(len(sigs) + 1, dtype=np.int64)
+    np.cumsum([a.shape[0] for a in sigs], out=off[1:])
+    return sigs, off
+
+
+def _pack_int16(sigs, dev):
+    """_int16_signals' first result -> one 1-D int16 tensor on `dev` (never empty: the C-ABI takes no NULL buffer)."""
+    if isinstance(sigs, torch.Tensor):
+        packed = sigs
+    elif all(isinstance(a, np.ndarray) for a in sigs):
+        packed = torch.from_numpy(np.concatenate(sigs) if sigs else np.zeros(0, np.int16)).to(dev)
+    else:
+        packed = torch.cat([a.to(dev) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                            for a in sigs])
+    if packed.numel() == 0:
+        packed = torch.zeros(1, dtype=torch.int16, device=dev)
+    return packed
+
+
+def mix_pairs(speech, noise, L, snr_db=0, return_mix64=True, device=None):
+    """The pair mixing of preprocess_audio_pair (data_processor.py:119-139) for a ragged group of U pairs in one
+    avse_mix_pairs call: each noise looped cyclically to its speech's length, scaled by AudioMixer.snr_factor for
+    snr_db (a number, or one per pair), added to the speech, everything padded / truncated to L samples.
+
+    speech / noise: a sequence of mono int16 signals (numpy or tensors, 1-D or [n, 1]), or a packed pair
+    (1-D int16 device tensor, int64 offsets [U + 1]).  Multi-channel or non-int16 input raises TypeError.
+    Returns (rows [3, U, L] float32: mixture, speech, scaled noise; mix64 [U, L] float64 or None; factor [U] float64),
+    device tensors equal to the numpy path's float64 results (and their float32 casts) bit for bit for utterances
+    below 2^23 samples (include/avse.h).  rows.view(3 * U, L) feeds spectrogram()."""
+    sp, so = _int16_signals(speech, "speech")
+    nz, no = _int16_signals(noise, "noise")
+    U = so.size - 1
+    if no.size - 1 != U:
+        raise ValueError(f"{U} speech signals but {no.size - 1} noise signals")
+    L = int(L)
+    if L <= 0:
+        raise ValueError("L must be positive")
+    if np.any(np.diff(so) == 0):
+        raise _lib.AvseError("avse_mix_pairs refused (status 1, AVSE_ERR_INVALID): speech signal "
+                             f"{int(np.argmin(np.diff(so)))} is empty")
+    if np.ndim(snr_db) == 0:
+        snr_lin = None if float(snr_db) == 0.0 else np.full(U, 10.0 ** (snr_db / 10.0), dtype=np.float64)
+    else:
+        if len(snr_db) != U:
+            raise ValueError(f"snr_db has {len(snr_db)} entries for {U} pairs")
+        snr_lin = np.array([10.0 ** (d / 10.0) for d in snr_db], dtype=np.float64)
+    for t in (sp, nz):
+        if isinstance(t, torch.Tensor) and device is None:
+            device = t.device
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    ctx = _lib.context(dev)
+    rows = torch.empty((3, U, L), dtype=torch.float32, device=dev)
+    mix64 = torch.empty((U, L), dtype=torch.float64, device=dev) if return_mix64 else None
+    factor = torch.empty((U,), dtype=torch.float64, device=dev)
+    if U == 0:
+        return rows, mix64, factor
+    sp, nz = _pack_int16(sp, dev), _pack_int16(nz, dev)
+    so_d, no_d = torch.from_numpy(so).to(dev), torch.from_numpy(no).to(dev)
+    lin_d = torch.from_numpy(snr_lin).to(dev) if snr_lin is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_mix_pairs(ctx.handle, _lib.ptr(sp), _lib.ptr(so_d), _lib.ptr(nz), _lib.ptr(no_d),
+                                              _lib.ptr(lin_d), U, L, _lib.ptr(rows), _lib.ptr(mix64), _lib.ptr(factor),
+                                              _lib.stream_handle(dev)), "avse_mix_pairs")
+    return rows, mix64, factor
+
+
 def mse(pred, target):
     """Keras mean_squared_error over every element -> 0-dim device tensor."""
     _dev_f32(pred, "pred")

@@ -16,6 +16,9 @@ Differences (host plumbing outside the hot path):
     allow_pickle=False), the normaliser normalization.npz, the model model.safetensors (a Keras model.h5py
     is converted once by tools/keras_h5_to_avse.py); the reference's own .pkl caches are not read (this
     build never unpickles);
+  * preprocess `--batch N` mixes and transforms the audio of up to N pairs per device call
+    (data_processor.preprocess_audio_pairs; the cache it writes equals the default per-sample loop's), and train
+    `--device-normalizer` fits the video normaliser with one streaming read on the device (VideoNormalizer.fit_device);
   * predict runs ONE forward per sample: the printed loss (speech_enhancer.py:76-77, an MSE over the
     sample like Model.evaluate) is computed from the same prediction that is reconstructed (the reference
     runs evaluate and predict, two forwards of the same input);
@@ -93,9 +96,49 @@ def preprocess_sample(speech_entry, noise_file_path, slice_duration_ms=200):
                   video_samples[:n], mixed[:n], speech[:n], noise[:n], mixed_signal, fps)
 
 
-def preprocess_data(speech_entries, noise_file_paths):
-    """data_processor.py:180-198 (catch-and-skip per sample; the GPU does the spectrograms, so no Pool)."""
+def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200):
+    """preprocess_sample for a group of entries with the audio of all pairs in one
+    data_processor.preprocess_audio_pairs call (device-side mixing, one STFT launch per geometry).  Catch-and-skip as
+    preprocess_data: an entry whose files do not load is skipped; when the batched call fails (a multi-channel or
+    float wav: TypeError) the group is redone pair by pair on preprocess_sample, so only the failing pair is lost."""
+    loaded = []
+    for entry, noise in zip(speech_entries, noise_file_paths):
+        try:
+            video_samples, fps = preprocess_video_sample(entry.video_path, slice_duration_ms)
+            loaded.append((entry, noise, video_samples, fps, AudioSignal.from_wav_file(entry.audio_path),
+                           AudioSignal.from_wav_file(noise)))
+        except Exception as e:  # noqa: BLE001 — mirrors try_preprocess_sample
+            print("failed to preprocess %s (%s)" % ((entry, noise), e))
+    if not loaded:
+        return []
+    try:
+        audio = data_processor.preprocess_audio_pairs([x[4] for x in loaded], [x[5] for x in loaded], slice_duration_ms,
+                                                      [x[2].shape[0] for x in loaded], [x[3] for x in loaded])
+    except Exception:  # noqa: BLE001 — isolate the failing pair below
+        audio = None
     samples = []
+    for k, (entry, noise, video_samples, fps, _, _) in enumerate(loaded):
+        if audio is None:
+            try:
+                samples.append(preprocess_sample(entry, noise, slice_duration_ms))
+            except Exception as e:  # noqa: BLE001
+                print("failed to preprocess %s (%s)" % ((entry, noise), e))
+            continue
+        mixed, speech, noise_spec, mixed_signal = audio[k]
+        n = min(video_samples.shape[0], mixed.shape[0])
+        samples.append(Sample(entry.speaker_id, entry.video_path, entry.audio_path, noise, video_samples[:n], mixed[:n],
+                              speech[:n], noise_spec[:n], mixed_signal, fps))
+    return samples
+
+
+def preprocess_data(speech_entries, noise_file_paths, batch=0):
+    """data_processor.py:180-198 (catch-and-skip per sample; the GPU does the spectrograms, so no Pool).
+    batch > 0: groups of up to `batch` consecutive pairs through preprocess_batch (same samples, same order)."""
+    samples = []
+    if batch > 0:
+        for a in range(0, len(speech_entries), batch):
+            samples.extend(preprocess_batch(speech_entries[a:a + batch], noise_file_paths[a:a + batch]))
+        return samples
     for entry, noise in zip(speech_entries, noise_file_paths):
         try:
             samples.append(preprocess_sample(entry, noise))
@@ -162,7 +205,7 @@ def preprocess(args):
     layout = Layout(args.base_dir)
     speech_entries, noise_file_paths = pair_speech_with_noise(args.dataset_dir, selected_speakers(args),
                                                               args.noise_dirs, limit=1000, shuffle=True)
-    samples = preprocess_data(speech_entries, noise_file_paths)
+    samples = preprocess_data(speech_entries, noise_file_paths, batch=args.batch)
     save_preprocessed_blob(layout.preprocessed(args.data_name), samples)
     print("preprocessed %d samples" % len(samples))
 
@@ -173,7 +216,11 @@ def train(args):
     layout = Layout(args.base_dir)
     samples = load_preprocessed_blobs([layout.preprocessed(d) for d in args.train_data_names])
     video, mixed, speech = make_sample_set(samples)
-    normalizer = data_processor.VideoNormalizer(video)
+    if args.device_normalizer:
+        from . import ops
+        normalizer = data_processor.VideoNormalizer.fit_device(ops.to_device(video))   # one upload, one streaming read
+    else:
+        normalizer = data_processor.VideoNormalizer(video)
     normalizer.save(layout.normalizer_file(args.model))
     network = SpeechEnhancementNetwork.build(mixed.shape[1:], video.shape[1:], seed=args.seed)
     if not args.init_only:
@@ -360,6 +407,8 @@ def main(argv=None):
     p.add_argument("-n", "--noise_dirs", nargs="+", type=str, required=True)
     p.add_argument("-s", "--speakers", nargs="+", type=str)
     p.add_argument("-is", "--ignored_speakers", nargs="+", type=str)
+    p.add_argument("--batch", type=int, default=0,
+                   help="preprocess the audio of up to N pairs per device call (0: one pair at a time)")
     p.set_defaults(func=preprocess)
 
     t = sub.add_parser("train")
@@ -370,6 +419,8 @@ def main(argv=None):
     t.add_argument("--init-only", action="store_true")
     t.add_argument("--epochs", type=int, default=1000)
     t.add_argument("--seed", type=int, default=0)
+    t.add_argument("--device-normalizer", action="store_true",
+                   help="fit the video normaliser on the device (float64 sums) instead of numpy on the host")
     t.set_defaults(func=train)
 
     q = sub.add_parser("predict")

@@ -31,7 +31,8 @@ extern "C" {
 /* 2: compute dtype AVSE_F32_SPLIT, avse_ctx_reserve_weights; option names tile_alt / aud_side removed (round 3);
  *    status AVSE_ERR_CHECK (checked build)
  * 3: AVSE_F32_SPLIT range guard (avse_forward_checked, avse_range_status, status AVSE_ERR_RANGE), per-layer activation
- *    exponents (avse_weights_act_exponents, option no_act_scale) */
+ *    exponents (avse_weights_act_exponents, option no_act_scale); later additions under the same version (new symbols
+ *    only, nothing existing changed): avse_mix_pairs, avse_video_stats */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -251,6 +252,42 @@ int avse_forward_profile(avse_ctx* ctx, const avse_weights* w, const float* audi
  *   video[s, :, :, f] = (video[s, :, :, f] - mean) / std   for video [S][H][W][F]. */
 int avse_video_normalize(avse_ctx* ctx, float* video, int64_t S, int H, int W, int F,
                          const float* mean, const float* std, void* stream);
+
+/* ---- device-side preprocess ------------------------------------------------------------- */
+
+/* Replaces the arithmetic of preprocess_audio_pair (data_processor.py:119-139) between reading the wav files and
+ * the three signal_to_spectrogram calls, for a ragged group of pairs: the noise looped cyclically to the speech's
+ * length (:124-128), AudioMixer.snr_factor and amplify_by_factor (:130-131), AudioMixer.mix (:133), and the pad /
+ * truncate to the slice geometry of preprocess_audio_signal (:39-42).
+ *   speech      int16 samples of n_pairs utterances, concatenated (channel 0)
+ *   speech_off  [n_pairs + 1] int64 element offsets into speech (device array); utterance u is
+ *               speech[speech_off[u] .. speech_off[u + 1]), n_s samples, at any element offset
+ *   noise, noise_off  the same for the noises (n_n samples; n_n == 0 is silence)
+ *   snr_lin     nullable (= 1.0, 0 dB); [n_pairs] float64, 10.0 ** (snr_db / 10.0) as the caller computed it
+ *   L           common output length (signal_length of the slice geometry), 0 < L < 2^31
+ *   rows        [3][n_pairs][L] float32: mixture, speech, scaled noise, each the round-to-nearest float32 of the
+ *               float64 value; zeros from sample n_s on.  With L % 4 == 0 every row is 16-byte aligned when rows is,
+ *               and avse_spectrogram takes the buffer as [3 n_pairs][L]
+ *   mix64       nullable; [n_pairs][L] float64, the mixed signal itself
+ *   factor      nullable; [n_pairs] float64, the noise gain
+ * Numerics: the powers are exact 64-bit integer sums (deterministic; equal to numpy's float64 means while a sum stays
+ * below 2^53, i.e. for n_s < 2^23 samples); factor = sqrt((S / n_s) / ((N / n_s) * snr_lin)) in float64 with every
+ * operation correctly rounded, 0.0 when N == 0; noise * factor and speech + that are two separately rounded float64
+ * operations (no FMA).  factor, mix64 and rows therefore equal the numpy path's bit for bit.
+ * n_s == 0 is not meaningful (numpy: a mean over nothing): the caller, who built the offsets, refuses it; such a pair's
+ * outputs here are zeros.  Scratch comes from the context and grows outside a stream capture only. */
+int avse_mix_pairs(avse_ctx* ctx, const int16_t* speech, const int64_t* speech_off, const int16_t* noise,
+                   const int64_t* noise_off, const double* snr_lin, int64_t n_pairs, int64_t L, float* rows,
+                   double* mix64, double* factor, void* stream);
+
+/* Replaces VideoNormalizer.__init__ (data_processor.py:203-206): np.mean / np.std over axes (0, 3) of
+ * video [S][H][W][F] (float32, F <= 8) -> mean [H][W], std [H][W] (float32; population std).
+ * One streaming read.  Per pixel, float64 sums of d and d^2 with d = x - video[0][h][w][0] (exact in float64: a
+ * constant pixel gives std == 0 exactly), per chunk of slices, combined in chunk order — no floating-point atomics,
+ * so two calls on one input agree bit for bit; mean = pivot + E[d], std = sqrt(max(0, E[d^2] - E[d]^2)), each rounded
+ * once to float32 (within 1 float32 ulp of numpy's float64 result rounded to float32).  Scratch as avse_mix_pairs. */
+int avse_video_stats(avse_ctx* ctx, const float* video, int64_t S, int H, int W, int F, float* mean, float* std,
+                     void* stream);
 
 /* SpeechEnhancementNetwork.evaluate's loss (network.py:214-220, Keras mean_squared_error over
  * every element): *loss = mean((pred - target)^2) over n values; loss is a device float. */
