@@ -43,6 +43,7 @@ struct Options {
     int no_win = 0;           // AVSE_NO_WIN: split stride-1 gather layers on k_conv, not the windowed conv_win.hip
     int no_v1p = 0;           // AVSE_NO_V1P: split 5-frame v_conv1 on k_conv_v1s (K 160), not k_conv_v1p (K 128; read at load)
     int no_a1valu = 0;        // AVSE_NO_A1VALU: split a_conv1 on k_conv after audio_prep, not k_aconv1_split
+    int no_planar = 0;        // AVSE_NO_PLANAR: split stream convs on the slice-by-slice [Ah | Al] grouping with lane swaps
     int side_prio = 0;        // AVSE_SIDE_PRIO: audio side stream priority (0 default, 1 least, 2 greatest; read when created)
 };
 
@@ -360,6 +361,7 @@ struct HaloArgs {
     int out_pix_stride;
     int out_c_off;
     int mfma32;              // conv_stream.hip: 1 = v_mfma_f32_32x32x16_bf16 compute waves (A/B variant)
+    int no_planar;           // conv_stream.hip, split: 1 = the [Ah | Al] x Bh grouping with v_permlane32_swap (A/B variant)
     int split;               // 1 = split-f16 operands (AVSE_F32_SPLIT): in is the split-pair layout, Ci counts halves
                              // (2 x channels), w holds [Bh | Bl] rows; out_mode OUT_S16 or OUT_F32
     int out_mode;            // HaloOut

@@ -203,6 +203,7 @@ const OptionName kOptionNames[] = {
     {"no_win", "AVSE_NO_WIN", &Options::no_win},
     {"no_v1p", "AVSE_NO_V1P", &Options::no_v1p},
     {"no_a1valu", "AVSE_NO_A1VALU", &Options::no_a1valu},
+    {"no_planar", "AVSE_NO_PLANAR", &Options::no_planar},
     {"side_prio", "AVSE_SIDE_PRIO", &Options::side_prio},
 };
 
@@ -917,6 +918,7 @@ HaloArgs halo_args(const GpuLayer& G, const void* in, const float* video, const 
     a.out = out;
     a.w = G.w_halo;
     a.mfma32 = opt.mfma32;
+    a.no_planar = opt.no_planar;
     a.scale = G.scale_h;
     a.shift = G.shift;
     a.N = (int)N;

@@ -90,7 +90,7 @@ __device__ __forceinline__ void barrier_raw() { asm volatile("s_barrier" ::: "me
 // LAT (load -> LDS store distance, steps): 10 for 5x5, 6 for 3x3; it divides the unrolled chunk pair
 // (2 KS^2 steps).  Measured on v_conv2 (runtime-tap loader): LAT 4 / 5 / 10 / 20 = 1.14 / 1.04-1.13 / 1.00 /
 // 1.27 ms (20 spills).
-template <int KS, int TH, int TW, int NCLIP, int LAT_ = (KS == 5 ? 10 : 6), int BP_ = 1, bool S16_ = false>
+template <int KS, int TH, int TW, int NCLIP, int LAT_ = (KS == 5 ? 10 : 6), int BP_ = 1, bool S16_ = false, bool PL_ = false>
 struct StreamGeom {
     static constexpr int HH = TH + KS - 1, HW = TW + KS - 1;
     static constexpr int HPIX = NCLIP * HH * HW;              // halo pixels per chunk
@@ -106,9 +106,17 @@ struct StreamGeom {
     // S16 (split-f16 operands): BP / 2 slice pairs per barrier; during period p the compute waves read the weights of
     // slices BP p .. BP p + BP (one past the period: the next pair's first slice) while the loader stores the BP
     // slices after those: a ring of 2 BP + 1 slots
+    // PL (planar slice pairs): the h halves of BOTH slices of a pair are read during the previous pair's third group,
+    // so period p reads slices BP p .. BP p + BP + 1 (two past the period).  The loader therefore runs one slice
+    // further ahead — during step j it stores slice j + BP + 2 — and the ring has 2 BP + 2 slots: the slots written
+    // during period p (slices BP p + BP + 2 .. BP p + 2 BP + 1) held slices BP p - BP .. BP p - 1, last read (their l
+    // halves, by the pairs of period p - 1) before the barrier that opens period p.  NWS is even, so a pair's two
+    // slots are always ws, ws + 1 with ws even
+    // WAH: the loader stores slice j + WAH during step j
     // PAIR: loader steps per unrolled iteration (2 chunks; 4 when a period of 4 steps would not divide 2 chunks)
-    static constexpr int LAT = LAT_, BP = BP_, NWS = S16_ ? 2 * BP + 1 : 2 * BP, WD = LAT + BP + 1, NHS = 3,
-                         PAIR = ((2 * NTAP) % BP ? 4 : 2) * NTAP, CPI = PAIR / NTAP;
+    static_assert(!PL_ || S16_, "planar slice pairs: split-f16 operands only");
+    static constexpr int LAT = LAT_, BP = BP_, WAH = BP + (PL_ ? 2 : 1), NWS = PL_ ? 2 * BP + 2 : S16_ ? 2 * BP + 1 : 2 * BP,
+                         WD = LAT + WAH, NHS = 3, PAIR = ((2 * NTAP) % BP ? 4 : 2) * NTAP, CPI = PAIR / NTAP;
     static_assert(PAIR % BP == 0, "barrier periods align with the unrolled loader iteration");
     static_assert(BP == 1 || BP == 2 || (S16_ && BP == 4), "barrier period");
     static_assert(!S16_ || BP % 2 == 0, "split-f16 operands: whole slice pairs per barrier");
@@ -120,7 +128,22 @@ struct StreamGeom {
     // the first fragment read of chunk g+2 at step NTAP-1 of chunk g+1
     // (a store is visible after the barrier closing its BP-step group: at most BP - 1 steps later)
     // (S16 reads A fragments up to the slice after its period: chunk g+2's first slice is read BP + 1 steps before it)
-    static_assert(HPW <= NTAP && HPW - 1 + LAT + BP - 1 <= 2 * NTAP - (S16_ ? BP + 1 : 2), "halo pieces must land in time");
+    // PL: the worst-case form above (BP + 2) is too coarse for the 3x3 tiles at BP 4, so every alignment of a chunk
+    // start s0 = g NTAP against the periods is checked: the last piece of chunk g+2 is stored at step s0 + HPW - 1 + LAT
+    // and visible from the first step of the following period; chunk g+2's first slice s2 = s0 + 2 NTAP belongs to the
+    // pair starting at s2 & ~1, whose h halves are read by the pair before it, i.e. in the period of step (s2 & ~1) - 2.
+    // A piece also may not overwrite chunk g-1's slot while its last slice is read (the l half of slice s0 - 1, by the
+    // pair that holds it, at the latest in the period of step s0): stores start at step s0 + LAT, LAT >= BP
+    static constexpr bool planar_halo_in_time() {
+        for (int g = 0; g < 2 * BP; ++g) {
+            const int s0 = g * NTAP, visible = ((s0 + HPW - 1 + LAT) / BP + 1) * BP;
+            const int first_read = (((s0 + 2 * NTAP) & ~1) - 2) / BP * BP;
+            if (visible > first_read) return false;
+        }
+        return LAT >= BP;
+    }
+    static_assert(HPW <= NTAP && (PL_ ? planar_halo_in_time() : HPW - 1 + LAT + BP - 1 <= 2 * NTAP - (S16_ ? BP + 1 : 2)),
+                  "halo pieces must land in time");
     // loads issued by step j (tap j % NTAP): two weight chunks + one piece on the first HPW taps
     static constexpr int loads(int j, int abl) {
         const int tap = ((j % NTAP) + NTAP) % NTAP;
@@ -152,11 +175,22 @@ struct StreamGeom {
 //      B' = [Bl(t) | Bl(t+1)] (lanes of k-groups 0, 1 read slice t's Bl half, 2, 3 slice t+1's) -> Ah Bl of both
 // i.e. three of the four products of (Ah + Al)(Bh + Bl) — Al Bl (2^-22 of |a b|, below the pieces' representation
 // error) is dropped — on 3/4 of the MFMAs of the four-product form.
+//
+// PL (planar slice pairs, the default for S16; Options::no_planar selects the grouping above): the same three products
+// with every operand a slice PAIR, lanes of k-groups 0, 1 holding slice t and 2, 3 slice t+1 (per-lane halo tap / slot and
+// weight ring slot):
+//   1. A'h = [Ah(t) | Ah(t+1)] x B'h = [Bh(t) | Bh(t+1)]
+//   2. A'l = [Al(t) | Al(t+1)] x B'h (the same B registers)
+//   3. A'h (the same A registers) x B'l = [Bl(t) | Bl(t+1)]
+// Every distinct operand byte is read from LDS once (24 ds_read_b128 per pair against 32) and no lanes are exchanged.
+// Register rotation (24 live fragments): group 1 reads A'l, group 2 B'l, group 3 the NEXT pair's A'h (into the A'l
+// registers) and B'h (into the B'h registers), so the two A sets swap roles every pair.
+// (PL is an int so that the kernel symbol ends in ", 0>" / ", 1>": profile tooling matches symbols with a numeric tail.)
 template <int KS, int TH, int TW, int NCLIP, bool M16 = true, int LAT_ = StreamGeom<KS, TH, TW, NCLIP>::LAT, int ABL = 0,
-          int BP_ = 1, bool S16 = false>
+          int BP_ = 1, bool S16 = false, int PL = 0>
 __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
     static_assert(!S16 || M16, "split-f16 operands: 16x16x32 compute waves only");
-    using G = StreamGeom<KS, TH, TW, NCLIP, LAT_, BP_, S16>;
+    using G = StreamGeom<KS, TH, TW, NCLIP, LAT_, BP_, S16, PL != 0>;
     constexpr int HH = G::HH, HW = G::HW, HPIX = G::HPIX, HPW = G::HPW, NTAP = G::NTAP;
     constexpr int CSLOT = G::CSLOT, WSLOT = G::WSLOT, LAT = G::LAT, WD = G::WD, PAIR = G::PAIR;
     constexpr int BP = G::BP, NWS = G::NWS;
@@ -249,7 +283,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
         char* const pbase0 = halo + w * 1024 + lane * 16;   // + slot * CSLOT + pc * 4096
 
         // prologue: chunk 0 and the pieces of chunk 1 that no virtual step -LAT..-1 loads, weight slices
-        // 0, 1 straight to LDS; the sets of the virtual steps (weights of slices 2 .. LAT+1, pieces of chunk
+        // 0 .. WAH-1 straight to LDS; the sets of the virtual steps (weights of slices WAH .. WAH+LAT-1, pieces of chunk
         // 1 on taps NTAP-LAT ..) into the register ring — steps 0 .. LAT-1 store them
         [&]<int... PC>(std::integer_sequence<int, PC...>) {
             (piece_store(std::integral_constant<int, PC>{}, pbase0, ld16(cur_rs, vo_cur[PC], 0)), ...);
@@ -257,14 +291,14 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                               : (void)0), ...);
         }(std::make_integer_sequence<int, HPW>{});
 #pragma unroll
-        for (int s = 0; s <= BP; ++s)
+        for (int s = 0; s < G::WAH; ++s)
 #pragma unroll
             for (int u = 0; u < 2; ++u) st16(wdst + s * WSLOT + 1024 * u, ld16w(wrs, wvoff[u], (s % spt) * wslice));
         i32x4 rw[LAT][2], rp[LAT];
         [&]<int... S>(std::integer_sequence<int, S...>) {
             ([&] {
-                 rw[S][0] = ld16w(wrs, wvoff[0], ((S + BP + 1) % spt) * wslice);
-                 rw[S][1] = ld16w(wrs, wvoff[1], ((S + BP + 1) % spt) * wslice);
+                 rw[S][0] = ld16w(wrs, wvoff[0], ((S + G::WAH) % spt) * wslice);
+                 rw[S][1] = ld16w(wrs, wvoff[1], ((S + G::WAH) % spt) * wslice);
                  constexpr int vt = NTAP - LAT + S;   // tap of virtual step S - LAT
                  if constexpr (vt < HPW && !(ABL & 1)) rp[S] = ld16(cur_rs, vo_cur[vt < HPW ? vt : 0], 64);
              }(), ...);
@@ -321,10 +355,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
             constexpr int tl = ((jl % NTAP) + NTAP) % NTAP;
             constexpr bool lprev = (jl < 0) || (jl / NTAP != j / NTAP);  // ... during the previous chunk
             if constexpr (tap == 0) chunk_begin();
-            // 1. LDS stores of set S: weights of slice j+BP+1 (slot (j+BP+1) % NWS) and the piece loaded
+            // 1. LDS stores of set S: weights of slice j+WAH (slot (j+WAH) % NWS) and the piece loaded
             //    with them
             if constexpr (!(ABL & 2)) {
-                int wsl = (j + BP + 1) % NWS + (kRot ? wrot : 0);
+                int wsl = (j + G::WAH) % NWS + (kRot ? wrot : 0);
                 if (wsl >= NWS) wsl -= NWS;
                 char* const wd = wdst + wsl * WSLOT;
                 st16(wd, rw[S][0]);
@@ -485,10 +519,66 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
 
         unsigned long long ptp = (ABL & 128) ? __builtin_amdgcn_s_memtime() : 0, pt0 = 0, pt1 = 0, p_work = 0,
                            p_wait = 0, p_bar = 0;
-        int tap1 = 1, hs1 = 0;
+        int tap1 = PL ? 0 : 1, hs1 = 0;   // the next slice to read (PL: the first slice of the next pair)
         i32x4 fa[4], fb[8], na[4], nb[8];
-        frags(0, 0, 0, fa, fb);
-        if constexpr ((ABL & 8) != 0) frags(0, 0, 0, na, nb);
+        // PL: a lane of k-groups 2, 3 (hi_half) holds the second slice of a pair.  Halo offset of the lane's A'h fragment =
+        // (ac0 + slot and tap offset of its slice) ^ ((ky & 1) << 5): ac0 carries 16-B slot (kg & 1) ^ hsw(dy), hsw(dy + ky)
+        // = hsw(dy) ^ hsw(ky), and every other term is a multiple of 64.  A'l is slot 2 + (kg & 1): the same offset ^ 32.
+        // B'h of the pair in ring slots ws, ws + 1 (ws even) is at bc0 + ws * WSLOT, B'l at that ^ 32
+        const bool hi_half = kg >= 2;
+        const int ac0 = ab + (((kg & 1) ^ hsw<true>(dy)) << 4);
+        const int bc0 = G::NHS * CSLOT + (hi_half ? WSLOT : 0) + bo16;
+        static_assert(PL == 0 || (CSLOT % 64 == 0 && WSLOT % 64 == 0 && NWS % 2 == 0), "the xor forms of the l-half offsets");
+        // State of the pair in registers, kept as running per-lane offsets so that ac0 / bc0 need not stay live through
+        // the slice loop: abase = ac0 + (slot and tap offset of the lane's slice), moved on by the difference of the
+        // wave-uniform offsets (us0, us1 -> the next pair's); ps0, ps1 the two slices' (ky & 1) << 5; bbase = bc0 +
+        // ws * WSLOT of the pair's (even) ring slot ws = wsc
+        int abase = ac0, bbase = bc0, us0 = 0, us1 = 0, ps0 = 0, ps1 = 0, wsc = 0;
+        auto advance = [&]() {
+            if (++tap1 == NTAP) {
+                tap1 = 0;
+                hs1 = hs1 == 2 ? 0 : hs1 + 1;
+            }
+        };
+        // moves the A state to the pair at (hs1, tap1) and (hs1, tap1) two slices on.  NTAP is odd for 5x5, so the
+        // second slice can be the next chunk's tap 0 in the next halo slot: both wave-uniform offsets, selected per lane
+        auto next_pair = [&]() {
+            const int ky0 = tap1 / KS, kx0 = tap1 % KS;
+            const int u0 = hs1 * CSLOT + (ky0 * HW + kx0) * 64;
+            ps0 = (ky0 & 1) << 5;
+            advance();
+            const int ky1 = tap1 / KS, kx1 = tap1 % KS;
+            const int u1 = hs1 * CSLOT + (ky1 * HW + kx1) * 64;
+            ps1 = (ky1 & 1) << 5;
+            advance();
+            abase += hi_half ? u1 - us1 : u0 - us0;
+            us0 = u0;
+            us1 = u1;
+        };
+        auto aoff_h = [&]() { return abase ^ (hi_half ? ps1 : ps0); };   // the pair's A'h offset
+        auto rd_a = [&](int off, i32x4 (&f)[4]) {
+            const char* hp = halo + off;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) f[i] = *reinterpret_cast<const i32x4*>(hp + boff_of(i));
+        };
+        auto rd_b = [&](int off, i32x4 (&f)[8]) {
+            const char* wp = lds + off;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                f[j] = ((ABL & 256) && j >= 4) ? f[j - 4] : *reinterpret_cast<const i32x4*>(wp + 1024 * j);
+        };
+        if constexpr (PL != 0) {
+            next_pair();
+            rd_a(aoff_h(), fa);
+            rd_b(bbase, fb);
+            if constexpr ((ABL & 8) != 0) {
+                rd_a(aoff_h() ^ 32, na);
+                rd_b(bbase ^ 32, nb);
+            }
+        } else {
+            frags(0, 0, 0, fa, fb);
+            if constexpr ((ABL & 8) != 0) frags(0, 0, 0, na, nb);
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         barrier_raw();   // slice 0 read: the loaders may now overwrite weight slot 0
 
@@ -539,12 +629,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
         int t = 0;
         int cur_clip0, cur_oy0, cur_ox0;
         if constexpr (S16) {
-            auto advance = [&]() {
-                if (++tap1 == NTAP) {
-                    tap1 = 0;
-                    hs1 = hs1 == 2 ? 0 : hs1 + 1;
-                }
-            };
             auto mfma_group = [&](const i32x4 (&ca)[4], const i32x4 (&cb)[8]) {
                 if constexpr (!(ABL & 16))
 #pragma unroll
@@ -564,7 +648,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 32 - ND * PER, 0);
                 __builtin_amdgcn_sched_barrier(0);
             };
-            const bool hi_half = kg >= 2;   // group 3's B': lanes of k-groups 2, 3 read slice t+1's Bl half
+            // (hi_half: group 3's B', lanes of k-groups 2, 3 read slice t+1's Bl half)
             // slices t, t+1 with (a0, b0) = A(t), Bh(t) in registers; reads A(t+2), Bh(t+2) into (na, nb); bar: the
             // pair closes a BP-slice period
             auto pstep = [&](auto bar, int t, i32x4 (&a0)[4], i32x4 (&b0)[8], i32x4 (&na)[4], i32x4 (&nb)[8]) {
@@ -601,10 +685,48 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                     }
                 }
             };
+            // PL: the pair in ring slots wsc, wsc + 1 with (ah, bh) = A'h, B'h in registers; reads
+            // A'l (group 1), B'l (group 2) and the next pair's A'h, B'h (group 3, into al and bh), one read per MFMA from
+            // the start of each group; the caller swaps ah / al for the next pair
+            auto ppl = [&](auto bar, i32x4 (&ah)[4], i32x4 (&al)[4], i32x4 (&bh)[8], i32x4 (&bl)[8]) {
+                if constexpr (!(ABL & 8)) rd_a(aoff_h() ^ 32, al);
+                mfma_group(ah, bh);
+                sched(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
+                if constexpr (!(ABL & 8)) rd_b(bbase ^ 32, bl);
+                mfma_group(al, bh);
+                sched(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{});
+                bbase += wsc + 2 == NWS ? -(NWS - 2) * WSLOT : 2 * WSLOT;
+                wsc = wsc + 2 == NWS ? 0 : wsc + 2;
+                next_pair();
+                if constexpr (!(ABL & 8)) {
+                    rd_a(aoff_h(), al);
+                    rd_b(bbase, bh);
+                }
+                mfma_group(ah, bl);
+                sched(std::integral_constant<int, 12>{}, std::integral_constant<int, 1>{});
+                if constexpr (!(ABL & 4) && decltype(bar)::value) {
+                    if constexpr ((ABL & 128) != 0) pt0 = __builtin_amdgcn_s_memtime();
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if constexpr ((ABL & 128) != 0) pt1 = __builtin_amdgcn_s_memtime();
+                    barrier_raw();
+                    if constexpr ((ABL & 128) != 0) {
+                        const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
+                        p_work += pt0 - ptp;
+                        p_wait += pt1 - pt0;
+                        p_bar += pt2 - pt1;
+                        ptp = pt2;
+                    }
+                }
+            };
             for (int kt = 0; kt < nmine; ++kt) {
                 for (int s = 0; s < spt; s += 4, t += 4) {   // spt % 4 == 0 (launch_stream)
-                    pstep(std::bool_constant<BP == 2>{}, t, fa, fb, na, nb);
-                    pstep(std::true_type{}, t + 2, na, nb, fa, fb);
+                    if constexpr (PL != 0) {
+                        ppl(std::bool_constant<BP == 2>{}, fa, na, fb, nb);
+                        ppl(std::true_type{}, na, fa, fb, nb);
+                    } else {
+                        pstep(std::bool_constant<BP == 2>{}, t, fa, fb, na, nb);
+                        pstep(std::true_type{}, t + 2, na, nb, fa, fb);
+                    }
                 }
                 tile_origin(kt, cur_clip0, cur_oy0, cur_ox0);
                 epilogue(cur_clip0, cur_oy0, cur_ox0);
@@ -776,7 +898,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
         }
 }
 
-// split-f16: two slice pairs per barrier (a 9-slot weight ring fits beside the 3 halo slots; v_conv2 3.64 -> 3.49 ms).
+// split-f16: two slice pairs per barrier (a 9-slot weight ring, 10 slots for the planar pairs, fits beside the 3 halo
+// slots: 155 KB + the BN table for the 5x5 and 8x8x4 tiles; v_conv2 3.64 -> 3.49 ms).
 // The 3x3 layers' halo pieces land in time at BP 4 only with LAT 4 (a split step is ~3x a bf16 step, so 4 steps still
 // cover the load latency): v_conv3 / v_conv4 / v_conv5 0.688 / 0.337 / 0.170 -> 0.665 / 0.324 / 0.165 ms
 #ifndef AVSE_S16_BP5
@@ -788,12 +911,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
 #ifndef AVSE_S16_LAT3
 #define AVSE_S16_LAT3 4
 #endif
-template <int KS, int TH, int TW, int NCLIP, bool M16, bool S16 = false>
+template <int KS, int TH, int TW, int NCLIP, bool M16, bool S16 = false, int PL = 0>
 int launch_stream(const HaloArgs& a, hipStream_t s) {
     constexpr int BP = S16 ? (KS == 5 ? AVSE_S16_BP5 : AVSE_S16_BP3) : 1;
     constexpr int LAT = (S16 && KS == 3) ? AVSE_S16_LAT3 : StreamGeom<KS, TH, TW, NCLIP>::LAT;
-    using G = StreamGeom<KS, TH, TW, NCLIP, LAT, BP, S16>;
-    constexpr auto kern = k_conv_stream<KS, TH, TW, NCLIP, M16, G::LAT, 0, BP, S16>;
+    using G = StreamGeom<KS, TH, TW, NCLIP, LAT, BP, S16, PL != 0>;
+    constexpr auto kern = k_conv_stream<KS, TH, TW, NCLIP, M16, G::LAT, 0, BP, S16, PL>;
     if (int rc = ensure_lds_attr((const void*)kern, G::LDS + 1024)) return rc;
     if (a.Hc % TH || a.Wc % TW || a.Co % 128 || a.Ci % 64) {   // an even number of 32-channel chunks
         set_error("stream conv: tile does not divide the layer");
@@ -822,10 +945,11 @@ int launch_stream(const HaloArgs& a, hipStream_t s) {
 int launch_conv_stream(const HaloArgs& a, hipStream_t s) {
     const bool m32 = a.mfma32 != 0;   // v_mfma_f32_32x32x16_bf16 compute waves (A/B variant, Options::mfma32)
     if (a.split) {   // split-f16 operands (a.Ci counts halves: 2 x the layer's channels)
+        const bool pl = a.no_planar == 0;   // planar slice pairs; Options::no_planar keeps the lane-swap grouping (A/B)
         switch (a.variant) {
-            case HALO_K5: return launch_stream<5, 16, 16, 1, true, true>(a, s);
-            case HALO_K3_16: return launch_stream<3, 16, 16, 1, true, true>(a, s);
-            case HALO_K3_8: return launch_stream<3, 8, 8, 4, true, true>(a, s);
+            case HALO_K5: return pl ? launch_stream<5, 16, 16, 1, true, true, 1>(a, s) : launch_stream<5, 16, 16, 1, true, true>(a, s);
+            case HALO_K3_16: return pl ? launch_stream<3, 16, 16, 1, true, true, 1>(a, s) : launch_stream<3, 16, 16, 1, true, true>(a, s);
+            case HALO_K3_8: return pl ? launch_stream<3, 8, 8, 4, true, true, 1>(a, s) : launch_stream<3, 8, 8, 4, true, true>(a, s);
         }
         set_error("stream conv: unsupported variant");
         return 3;

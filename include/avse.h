@@ -97,6 +97,8 @@ void avse_ctx_destroy(avse_ctx* ctx);
  *   no_v1p (AVSE_NO_V1P)             AVSE_F32_SPLIT 5-frame v_conv1 on k_conv_v1s (K 160) instead of k_conv_v1p
  *                                    (K 128; applies to weights loaded afterwards)
  *   no_a1valu (AVSE_NO_A1VALU)       AVSE_F32_SPLIT a_conv1 on audio_prep + k_conv instead of k_aconv1_split
+ *   no_planar (AVSE_NO_PLANAR)       AVSE_F32_SPLIT stream convolutions on the slice-by-slice [Ah | Al] grouping with
+ *                                    lane swaps instead of the planar slice-pair grouping
  *   side_prio (AVSE_SIDE_PRIO)       audio side stream priority: 0 default, 1 least, 2 greatest (set before the
  *                                    context's first concurrent forward)
  * Unknown names return AVSE_ERR_INVALID. */

@@ -4,6 +4,11 @@ operand layout (lane l reads row l & 15, 16-B k-group l >> 4 with one ds_read_b1
 ds_read_b128 serves a wave in four 16-lane groups (MI355X_MICROARCH.md, LDS table); a group is conflict-free
 when its 16 lanes hit 16 distinct 16-B bank units of a 256-B line.  Checked for every tap offset and for the
 three tile geometries of conv_stream.hip (5x5 16x16, 3x3 16x16, 3x3 8x8 x 4 clips).
+
+The split-f16 planar slice pairs read other lane -> slot maps from the same images: every lane takes 16-B slot kg & 1
+(h halves) or 2 + (kg & 1) (l halves), and lanes 32..63 read the pair's second slice (another tap, possibly another
+halo slot, and the next weight ring slot: whole multiples of 1 KB away).  A 16-lane service group never spans both
+halves of the wave, so a group sees one tap and one slot; the maps are checked below over every tap like the bf16 one.
     python tools/lds_swizzle_search.py
 """
 import itertools
@@ -20,7 +25,12 @@ def lane_pixel(lane):
     return 2 * (q >> 1) + dy, 2 * (q & 1) + dx, k
 
 
-def halo_ok(f):
+# lane -> 16-B slot (before the image's xor): the bf16 / swap-form operand layout, and the planar slice pairs' two halves
+KMAPS = {"bf16": lambda lane: lane >> 4, "planar h": lambda lane: (lane >> 4) & 1,
+         "planar l": lambda lane: 2 + ((lane >> 4) & 1)}
+
+
+def halo_ok(f, kmap=KMAPS["bf16"]):
     for g in GEOMS:
         ks = g["KS"]
         hh, hw = g["TH"] + ks - 1, g["TW"] + ks - 1
@@ -32,19 +42,19 @@ def halo_ok(f):
                             for grp in GROUPS:
                                 units = set()
                                 for lane in grp:
-                                    py, px, k = lane_pixel(lane)
+                                    py, px, _ = lane_pixel(lane)
                                     y, x = y0 + py + ky, x0 + px + kx
                                     p = (cl * hh + y) * hw + x
-                                    units.add((4 * (p % 4) + (k ^ f(y))) % 16)
+                                    units.add((4 * (p % 4) + (kmap(lane) ^ f(y))) % 16)
                                 if len(units) < 16:
                                     return False
     return True
 
 
-def weights_ok(tab):
+def weights_ok(tab, kmap=KMAPS["bf16"]):
     for jb in range(8):
         for grp in GROUPS:
-            units = {(4 * ((16 * jb + (l & 15)) % 4) + ((l >> 4) ^ tab[((16 * jb + (l & 15)) >> 2) & 3])) % 16 for l in grp}
+            units = {(4 * ((16 * jb + (l & 15)) % 4) + (kmap(l) ^ tab[((16 * jb + (l & 15)) >> 2) & 3])) % 16 for l in grp}
             if len(units) < 16:
                 return False
     return True
@@ -77,8 +87,11 @@ if __name__ == "__main__":
         for pitch in range(20, 29):
             print(f"conv_v1r window pitch {pitch}: {v1r_read2_cycles(pitch)} LDS cycles per A fragment (8 = conflict-free)")
         sys.exit(0)
-    assert halo_ok(lambda y: 2 * (y & 1)), "hsw<true>"
-    assert weights_ok((0, 2, 0, 2)), "wswz<true>"
+    assert all(max(g) < 32 or min(g) >= 32 for g in GROUPS), "a service group stays within one half of the wave"
+    for name, kmap in KMAPS.items():
+        assert halo_ok(lambda y: 2 * (y & 1), kmap), f"hsw<true>, {name}"
+        assert weights_ok((0, 2, 0, 2), kmap), f"wswz<true>, {name}"
+        print(f"{name}: halo and weight images conflict-free for every tap and all three geometries")
     assert not halo_ok(lambda y: y & 3)      # the 32x32x16 swizzle conflicts under the 16x16x32 layout
     print("halo swizzles (y mod 4 -> slot xor):", [t for t in itertools.product(range(4), repeat=4) if halo_ok(lambda y, t=t: t[y % 4])])
     print("weight swizzles ((co >> 2) mod 4 -> slot xor):", [t for t in itertools.product(range(4), repeat=4) if weights_ok(t)])

@@ -5,6 +5,14 @@ keeps (products of bf16 pieces are exact in float64), its output rounded to floa
 epilogue; so the differences between schemes are representation / dropped-product errors, not accumulation order.
 
     python tools/split_err.py [N] [seed]
+    python tools/split_err.py [N] [seed] groupings    # the stream kernels' two MFMA groupings, accumulation order included
+
+"groupings" emulates v_conv2..v_conv5 as conv_stream.hip runs them in the split dtype, under the MFMA accumulation
+model (one v_mfma_f32_16x16x32_f16 sums its 32 products exactly and rounds once into the fp32 accumulator): K-slices of
+16 channels in the kernel's order (slice = chunk * KS^2 + tap), taken in pairs t, t+1 with three roundings per pair:
+    pair:   [Ah Bh + Al Bh](t) | [Ah Bh + Al Bh](t+1) | Ah Bl (t) + Ah Bl (t+1)
+    planar: Ah Bh (t) + Ah Bh (t+1) | Al Bh (t) + Al Bh (t+1) | Ah Bl (t) + Ah Bl (t+1)
+(v_conv1 keeps the fp16x3 scheme above in both.)
 """
 import os
 import sys
@@ -78,6 +86,66 @@ def make_conv(scheme, layers):
     return conv
 
 
+def f32(t):
+    return t.to(torch.float32).to(torch.float64)
+
+
+def make_grouped_conv(grouping, fallback):
+    """conv_same for v_conv2..v_conv5 with the stream kernels' slice pairs and accumulator roundings."""
+    def conv(x, kernel, bias, strides, dtype):
+        kh, kw, cin, cout = kernel.shape
+        if not (x.shape[2] == x.shape[3] and x.shape[2] in (64, 32, 16, 8) and cin % 16 == 0):
+            return fallback(x, kernel, bias, strides, dtype)
+        w = torch.as_tensor(np.asarray(kernel, np.float32), dtype=torch.float64)
+        # weights x 2^e_n per output channel, max |w| 2^e_n in [2^14, 2^15) (capi.hip packing)
+        wmax = w.abs().amax(dim=(0, 1, 2)).clamp_min(1e-30)
+        wsc = torch.pow(2.0, 14 - torch.floor(torch.log2(wmax)))
+        wh, wl = split(w * wsc, 2, torch.float16)
+        n, _, hh, ww = x.shape
+        pad = (kh - 1) // 2
+        xh, xl = (F.pad(p, (pad, pad, pad, pad)) for p in split(f32(x), 2, torch.float16))
+        ntap = kh * kw
+
+        def prods(t):
+            c, tap = divmod(t, ntap)
+            ky, kx = divmod(tap, kw)
+            cs = slice(16 * c, 16 * c + 16)
+            ah = xh[:, cs, ky:ky + hh, kx:kx + ww].permute(0, 2, 3, 1).reshape(-1, 16)
+            al = xl[:, cs, ky:ky + hh, kx:kx + ww].permute(0, 2, 3, 1).reshape(-1, 16)
+            bh, bl = wh[ky, kx, cs, :], wl[ky, kx, cs, :]
+            return ah @ bh, al @ bh, ah @ bl
+
+        acc = torch.zeros(n * hh * ww, cout, dtype=torch.float64)
+        for t in range(0, (cin // 16) * ntap, 2):   # an even slice count (conv_stream.hip: divisible by 4)
+            hh0, lh0, hl0 = prods(t)
+            hh1, lh1, hl1 = prods(t + 1)
+            if grouping == "pair":
+                acc = f32(acc + (hh0 + lh0))
+                acc = f32(acc + (hh1 + lh1))
+            else:
+                acc = f32(acc + (hh0 + hh1))
+                acc = f32(acc + (lh0 + lh1))
+            acc = f32(acc + (hl0 + hl1))
+        y = f32(acc / wsc) + torch.as_tensor(bias, dtype=torch.float64)
+        return f32(y.reshape(n, hh, ww, cout).permute(0, 3, 1, 2))
+    return conv
+
+
+def main_groupings(N, seed, wd, mel, video, ref, rms):
+    orig = K.conv_same
+    v1 = make_conv("fp16x3", {"v_conv1"})
+    out = {}
+    for grouping in ("pair", "planar"):
+        K.conv_same = make_grouped_conv(grouping, v1)
+        try:
+            got = K.forward(wd, mel, video)
+        finally:
+            K.conv_same = orig
+        out[grouping] = float(np.sqrt(np.mean((got - ref) ** 2)))
+        print(f"{grouping:8s} v2-v5 abs rms {out[grouping]:.3e}  rel {out[grouping] / rms:.2e}", flush=True)
+    print(f"planar - pair {out['planar'] - out['pair']:+.3e}")
+
+
 def main():
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 37
@@ -100,6 +168,8 @@ def main():
                    "v1-v6": {"v_conv1", "v_conv2", "v_conv3", "v_conv4", "v_conv5", "v_conv6"}}
     orig = K.conv_same
     print(f"N={N} seed={seed} output rms {rms:.4g}")
+    if len(sys.argv) > 3 and sys.argv[3] == "groupings":
+        return main_groupings(N, seed, wd, mel, video, ref, rms)
     for sname in SCHEMES:
         for lname, ls in layers_sets.items():
             if sname == "fp32" and lname != "v1-v5":

@@ -1,6 +1,8 @@
-// Ablation timing of the split-f16 stream kernel (k_conv_stream<5,16,16,1,true,LAT,ABL,BP,true>, conv_stream.hip) at
+// Ablation timing of the split-f16 stream kernel (k_conv_stream<5,16,16,1,true,LAT,ABL,BP,true,PL>, conv_stream.hip) at
 // the v_conv2 bench shape (N=512, 64x64, 128 -> 128 real channels = 256 halves of [h | l] pairs, 5x5, BP 4).  Timing
 // only: outputs are meaningless for ABL != 0.  Random f16 data (MFMA power, hence clock, depends on it).
+// Every row is taken for both groupings in one process: the lane-swap form (PL = false, Options::no_planar) and the
+// planar slice pairs (PL = true), alternated twice.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -o /tmp/s16abl tools/stream_s16_ablate.hip && /tmp/s16abl
 //   (-DAVSE_S16_APLDS=1: the A'-from-LDS form of the third MFMA group)
 #include <cstdint>
@@ -20,10 +22,10 @@ int ensure_lds_attr(const void* fn, int bytes) {
 
 using namespace avse;
 
-template <int ABL, int LAT = 10, int BP = 4>
+template <bool PL, int ABL, int LAT = 10, int BP = 4>
 float run(const HaloArgs& a, int reps, int gx = 256) {
-    using G = StreamGeom<5, 16, 16, 1, LAT, BP, true>;
-    constexpr auto kern = k_conv_stream<5, 16, 16, 1, true, LAT, ABL, BP, true>;
+    using G = StreamGeom<5, 16, 16, 1, LAT, BP, true, PL>;
+    constexpr auto kern = k_conv_stream<5, 16, 16, 1, true, LAT, ABL, BP, true, PL>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS + 1024);
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -36,6 +38,67 @@ float run(const HaloArgs& a, int reps, int gx = 256) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
     return ms / reps;
+}
+
+template <bool PL>
+void suite(HaloArgs a, unsigned long long* prof) {
+    const int N = a.N, H = a.Hc, C = a.Co;
+    const char* const tag = PL ? "planar" : "swap  ";
+    a.prof = prof;
+    const double flop = 2.0 * N * H * H * C * C * 25;   // fp32 multiply-adds of the layer
+    const int reps = 10;
+    auto rep = [&](const char* name, float ms) {
+        std::printf("%s %-40s %8.4f ms  %7.1f TF/s (fp32 MAC)\n", tag, name, ms, flop / (ms * 1e-3) / 1e12);
+    };
+    rep("full", run<PL, 0>(a, reps));
+    rep("half the B fragment reads (256)", run<PL, 256>(a, reps));
+    rep("full", run<PL, 0>(a, reps));
+    rep("half the B fragment reads (256)", run<PL, 256>(a, reps));
+    rep("no halo pieces (1)", run<PL, 1>(a, reps));
+    rep("no weight streaming (2)", run<PL, 2>(a, reps));
+    rep("no loads (3)", run<PL, 3>(a, reps));
+    rep("no wait/barrier (4)", run<PL, 4>(a, reps));
+    rep("no frag reads (8)", run<PL, 8>(a, reps));
+    rep("no frag reads, no loads (11)", run<PL, 11>(a, reps));
+    rep(PL ? "MFMA only (15)" : "MFMA + permlane only (15)", run<PL, 15>(a, reps));
+    rep("no MFMAs (16)", run<PL, 16>(a, reps));
+    rep("full again", run<PL, 0>(a, reps));
+    // instrumented variants: cycles per slice of the compute / loader waves, and the effective shader clock =
+    // compute-wave cycles per CU (all of its slices) / kernel time
+    auto inst = [&](const char* name, float ms) {
+        std::vector<unsigned long long> hp(256 * 8 * 4);
+        (void)hipMemcpy(hp.data(), prof, hp.size() * 8, hipMemcpyDeviceToHost);
+        double s[2][3] = {}, steps[2] = {};
+        for (int b = 0; b < 256; ++b)
+            for (int wv = 0; wv < 8; ++wv) {
+                const int role = wv >= 4;
+                for (int k = 0; k < 3; ++k) s[role][k] += (double)hp[(b * 8 + wv) * 4 + k];
+                steps[role] += (double)hp[(b * 8 + wv) * 4 + 3];
+            }
+        const double cyc = (s[0][0] + s[0][1] + s[0][2]) / 4 / 256;   // per compute wave = per CU
+        std::printf("%s %-28s %7.4f ms  clock %.2f GHz | compute work %6.1f wait %5.1f bar %5.1f | loader work %6.1f "
+                    "wait %5.1f bar %6.1f (cycles/slice)\n", tag, name, ms, cyc / (ms * 1e6), s[0][0] / steps[0],
+                    s[0][1] / steps[0], s[0][2] / steps[0], s[1][0] / steps[1], s[1][1] / steps[1], s[1][2] / steps[1]);
+    };
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("full (128)", run<PL, 128>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("no pieces (129)", run<PL, 129>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("no weights (130)", run<PL, 130>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("no loads (131)", run<PL, 131>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("no frag reads (136)", run<PL, 136>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("L2-resident input (192)", run<PL, 192>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("full again (128)", run<PL, 128>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst(PL ? "MFMA only (143)" : "MFMA + permlane only (143)", run<PL, 143>(a, 1));
+    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
+    inst("no frag reads, no loads (139)", run<PL, 139>(a, 1));
+    rep("L2-resident input (64)", run<PL, 64>(a, reps));
 }
 
 int main() {
@@ -65,62 +128,11 @@ int main() {
     (void)hipMemcpy(sc, one.data(), C * 4, hipMemcpyHostToDevice);
     (void)hipMemset(sh, 0, C * 4);
     a.in = in; a.out = out; a.w = w; a.scale = sc; a.shift = sh;
-    const double flop = 2.0 * N * H * H * C * C * 25;   // fp32 multiply-adds of the layer
-    const int reps = 10;
-    auto rep = [&](const char* name, float ms) {
-        std::printf("%-40s %8.4f ms  %7.1f TF/s (fp32 MAC)\n", name, ms, flop / (ms * 1e-3) / 1e12);
-    };
-    rep("full", run<0>(a, reps));
-    rep("half the B fragment reads (256)", run<256>(a, reps));
-    rep("full", run<0>(a, reps));
-    rep("half the B fragment reads (256)", run<256>(a, reps));
-    rep("no halo pieces (1)", run<1>(a, reps));
-    rep("no weight streaming (2)", run<2>(a, reps));
-    rep("no loads (3)", run<3>(a, reps));
-    rep("no wait/barrier (4)", run<4>(a, reps));
-    rep("no frag reads (8)", run<8>(a, reps));
-    rep("no frag reads, no loads (11)", run<11>(a, reps));
-    rep("MFMA + permlane only (15)", run<15>(a, reps));
-    rep("no MFMAs (16)", run<16>(a, reps));
-    rep("full again", run<0>(a, reps));
     unsigned long long* prof;
     (void)hipMalloc(&prof, 256 * 8 * 4 * 8);
-    a.prof = prof;
-    // instrumented variants: cycles per slice of the compute / loader waves, and the effective shader clock =
-    // compute-wave cycles per CU (all of its slices) / kernel time
-    auto inst = [&](const char* name, float ms) {
-        std::vector<unsigned long long> hp(256 * 8 * 4);
-        (void)hipMemcpy(hp.data(), prof, hp.size() * 8, hipMemcpyDeviceToHost);
-        double s[2][3] = {}, steps[2] = {};
-        for (int b = 0; b < 256; ++b)
-            for (int wv = 0; wv < 8; ++wv) {
-                const int role = wv >= 4;
-                for (int k = 0; k < 3; ++k) s[role][k] += (double)hp[(b * 8 + wv) * 4 + k];
-                steps[role] += (double)hp[(b * 8 + wv) * 4 + 3];
-            }
-        const double cyc = (s[0][0] + s[0][1] + s[0][2]) / 4 / 256;   // per compute wave = per CU
-        std::printf("%-28s %7.4f ms  clock %.2f GHz | compute work %6.1f wait %5.1f bar %5.1f | loader work %6.1f "
-                    "wait %5.1f bar %6.1f (cycles/slice)\n", name, ms, cyc / (ms * 1e6), s[0][0] / steps[0],
-                    s[0][1] / steps[0], s[0][2] / steps[0], s[1][0] / steps[1], s[1][1] / steps[1], s[1][2] / steps[1]);
-    };
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("full (128)", run<128>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("no pieces (129)", run<129>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("no weights (130)", run<130>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("no loads (131)", run<131>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("no frag reads (136)", run<136>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("L2-resident input (192)", run<192>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("full again (128)", run<128>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("MFMA + permlane only (143)", run<143>(a, 1));
-    (void)hipMemset(prof, 0, 256 * 8 * 4 * 8);
-    inst("no frag reads, no loads (139)", run<139>(a, 1));
-    rep("L2-resident input (64)", run<64>(a, reps));
+    for (int r = 0; r < 2; ++r) {
+        suite<false>(a, prof);
+        suite<true>(a, prof);
+    }
     return 0;
 }
