@@ -89,7 +89,9 @@ SIGNATURES = {
     "avse_trainer_iterations": (_int, [_c_void_p, ctypes.POINTER(_i64)]),
 }
 AVSE_TRAIN_PARAMS, AVSE_TRAIN_GRADS, AVSE_TRAIN_ADAM_M, AVSE_TRAIN_ADAM_V = 0, 1, 2, 3
+AVSE_TRAIN_DEBUG_DZ = 4                                   # test aid: the dz scratch (avse_trainer_read)
 AVSE_TRAIN_GRADS_ONLY = 1
+AVSE_TRAIN_DEBUG_STOP, AVSE_TRAIN_DEBUG_GIN, AVSE_TRAIN_DEBUG_GHAT = 2, 4, 8   # test aids, each | (layer << 8)
 
 
 def source_digest():

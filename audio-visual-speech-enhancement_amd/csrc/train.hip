@@ -823,6 +823,7 @@ struct avse_trainer {
     long long n_fwd = 0, n_dg = 0;
     float *ones = nullptr, *zeros = nullptr;
     float *in_audio = nullptr, *in_video = nullptr, *concat = nullptr, *g6 = nullptr, *ghat = nullptr;
+    long long dz_floats = 0;  // size of the dz scratch (ghat): the largest pre-pool z of a max_n batch
     float* red = nullptr;     // column-reduction / loss partials
     long long red_floats = 0;
     float* wpart = nullptr;   // wgrad split partials
@@ -1141,6 +1142,7 @@ int alloc_tensors(avse_trainer* t) {
         wmax = std::max(wmax, (long long)T.L.kh * T.L.kw * T.L.cin * T.L.cout * mx);
     }
     if (int rc = talloc(t, &t->ghat, zmax)) return rc;
+    t->dz_floats = zmax;
     t->red_floats = std::max(red, 2LL * (2048 + 64) * 64 + 4096);   // colred's nblk * C <= (2048 + 64) * 64 (x2 MODE 2)
     if (int rc = talloc(t, &t->red, t->red_floats)) return rc;
     if (int rc = talloc(t, &t->kpart, kSplitTiles * 128LL * 128)) return rc;
@@ -1408,6 +1410,10 @@ int step_impl(avse_trainer* t, const float* audio, const float* video, const flo
         bool bias_fused = false;
         if (!L.bn) {
             dz = t->g6;   // dL/dy with the output's 8-channel stride
+            if ((flags & AVSE_TRAIN_DEBUG_STOP) && (flags >> 8) == i) {   // debug: no BN here, its dz is dL/dy itself
+                AVSE_HIP_CHECK(hipMemcpyAsync(t->ghat, t->g6, sizeof(float) * Mfull * T.zc, hipMemcpyDeviceToDevice, s));
+                return 0;
+            }
         } else {
             const int C = L.bn_channels;
             const long long M = Mfull * (L.cout / C);
@@ -1427,6 +1433,7 @@ int step_impl(avse_trainer* t, const float* audio, const float* video, const flo
             const long long total = N * (long long)aa.Hq * aa.Wq * C / (aa.pool ? 4 : 1);
             hipLaunchKernelGGL(k_act_bwd, dim3(grid_for(total)), dim3(256), 0, s, aa, (const float*)gbuf, gclip, gpix, gc, t->ghat);
             AVSE_HIP_CHECK(hipGetLastError());
+            if ((flags & AVSE_TRAIN_DEBUG_GHAT) && (flags >> 8) == i) return 0;   // debug: dL/d(BN output) of layer i in ghat
             if (int rc = colred<2, 2>(t, t->ghat, C, T.z, T.mean, T.inv, M, C, nullptr, nullptr, nullptr, nullptr,
                                       t->Gr + T.o_be, t->Gr + T.o_g, s)) return rc;
             bias_fused = (L.cout == C && T.zc == C);
@@ -1528,7 +1535,7 @@ int avse_trainer_step(avse_trainer* t, const float* audio, const float* video, c
 
 int avse_trainer_read(avse_trainer* t, int what, float* host_blob, int64_t n_floats) {
     if (!t || !host_blob) return tfail(AVSE_ERR_INVALID, "NULL argument");
-    if (n_floats != t->nparams && !(what == AVSE_TRAIN_DEBUG_DZ && n_floats <= t->nparams))
+    if (what == AVSE_TRAIN_DEBUG_DZ ? (n_floats < 0 || n_floats > t->dz_floats) : n_floats != t->nparams)
         return tfail(AVSE_ERR_INVALID, "blob size mismatch");
     const float* src = what == AVSE_TRAIN_PARAMS ? t->P : what == AVSE_TRAIN_GRADS ? t->Gr : what == AVSE_TRAIN_ADAM_M ? t->Mo
                        : what == AVSE_TRAIN_ADAM_V ? t->Vo : nullptr;

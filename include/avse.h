@@ -307,12 +307,19 @@ int avse_mse(avse_ctx* ctx, const float* pred, const float* target, int64_t n, f
  * Parameters, gradients and Adam moments are kept in the canonical blob layout of avse_weights_load. */
 typedef struct avse_trainer avse_trainer;
 enum avse_train_buffer { AVSE_TRAIN_PARAMS = 0, AVSE_TRAIN_GRADS = 1, AVSE_TRAIN_ADAM_M = 2, AVSE_TRAIN_ADAM_V = 3,
-                         AVSE_TRAIN_DEBUG_DZ = 4 /* test aid: the first n_floats of the dz scratch */ };
+                         /* test aid: the first n_floats of the dz scratch (as large as the largest pre-pool layer
+                          * output of a max_batch batch) */
+                         AVSE_TRAIN_DEBUG_DZ = 4 };
 /* AVSE_TRAIN_DEBUG_STOP | (layer << 8): test aid, end the backward pass right after layer's BN backward (its
- * dL/dz is then readable with AVSE_TRAIN_DEBUG_DZ; gradients of earlier layers are not computed) */
+ * dL/dz is then readable with AVSE_TRAIN_DEBUG_DZ; gradients of earlier layers are not computed).  d_deconv6 has no
+ * BatchNormalization: its dz, dL/dy with the output's 8-channel stride, is copied to the dz scratch */
 /* AVSE_TRAIN_DEBUG_GIN | (layer << 8): test aid, end the backward pass after layer's input gradient, copied to the
  * dz scratch */
-enum avse_train_flags { AVSE_TRAIN_GRADS_ONLY = 1, AVSE_TRAIN_DEBUG_STOP = 2, AVSE_TRAIN_DEBUG_GIN = 4 };
+/* AVSE_TRAIN_DEBUG_GHAT | (layer << 8): test aid, end the backward pass right after layer's activation backward
+ * (LeakyReLU slope, pool routing, dropout), before its BN backward: dL/d(BN output) is then in the dz scratch at the
+ * full pre-pool resolution, [N][hq][wq][C] */
+enum avse_train_flags { AVSE_TRAIN_GRADS_ONLY = 1, AVSE_TRAIN_DEBUG_STOP = 2, AVSE_TRAIN_DEBUG_GIN = 4,
+                        AVSE_TRAIN_DEBUG_GHAT = 8 };
 
 /* host_blob: initial parameters (avse_weights_load layout); max_batch: largest N passed to avse_trainer_step,
  * 1..1023 (activation tensors stay below 2^31 elements). */
@@ -333,7 +340,8 @@ int avse_trainer_step(avse_trainer* t, const float* audio, const float* video, c
                       const float* vnorm_mean, const float* vnorm_std, int64_t N, float lr, float dropout_rate,
                       uint32_t dropout_seed, int flags, float* loss, void* stream);
 
-/* Copy one of the trainer's blobs (avse_train_buffer) to the host; synchronises the device. */
+/* Copy one of the trainer's blobs (avse_train_buffer) to the host; synchronises the device.  n_floats is the blob
+ * size, except for AVSE_TRAIN_DEBUG_DZ (any count up to the size of the dz scratch). */
 int avse_trainer_read(avse_trainer* t, int what, float* host_blob, int64_t n_floats);
 /* Adam iterations applied so far (Keras `optimizer.iterations`). */
 int avse_trainer_iterations(avse_trainer* t, int64_t* iterations);

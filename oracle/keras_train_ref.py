@@ -59,10 +59,20 @@ def _bn_train(x, gamma, beta, channel_dim, stats, name):
     return (x - mean) / torch.sqrt(var + K.BN_EPS) * gamma.reshape(shape) + beta.reshape(shape)
 
 
-def train_forward(p, mel, video, target, rate, seed, stats, dt=torch.float64):
-    """p: {tensor name: leaf tensor of dtype dt}; video already normalised.  Returns the scalar MSE."""
+def train_forward(p, mel, video, target, rate, seed, stats, dt=torch.float64, taps=None):
+    """p: {tensor name: leaf tensor of dtype dt}; video already normalised.  Returns the scalar MSE.
+    taps: optional dict, filled with {layer: (x, z, bn)} — the layer's input, its pre-BN output and its BN output
+    (None without BN), as the graph's own tensors (NCHW; dense [N, features]; dec_dense2's bn NHWC) with
+    retain_grad() set, so that after backward() their .grad are dL/dx, dL/dz and dL/d(BN output)."""
     a = torch.as_tensor(np.asarray(mel), dtype=dt)[:, None]
     v = torch.as_tensor(np.asarray(video), dtype=dt).permute(0, 3, 1, 2)
+
+    def tap(name, x, z, y=None):
+        if taps is not None:
+            for t in (x, z, y):
+                if t is not None and t.requires_grad:
+                    t.retain_grad()
+            taps[name] = (x, z, y)
 
     def conv(x, name, s):
         kh, kw = p[name + "/kernel"].shape[:2]
@@ -77,39 +87,48 @@ def train_forward(p, mel, video, target, rate, seed, stats, dt=torch.float64):
         pt, pl = max(kh - s[0], 0) // 2, max(kw - s[1], 0) // 2
         return y[:, :, pt:pt + H * s[0], pl:pl + W * s[1]]
 
-    def bn(x, name, channel_dim=1):
-        return _bn_train(x, p[name + "_bn/gamma"], p[name + "_bn/beta"], channel_dim, stats, name)
+    def bn(x, name, channel_dim=1, src=None):
+        y = _bn_train(x, p[name + "_bn/gamma"], p[name + "_bn/beta"], channel_dim, stats, name)
+        tap(name, src[0], src[1], y)
+        return y
 
     for name, _, _, _, s, _, _, _ in K.AUDIO_ENCODER:
-        a = K.lrelu(bn(conv(a, name, s), name))
+        z = conv(a, name, s)
+        a = K.lrelu(bn(z, name, src=(a, z)))
     for name, _, _, _, s, _, _, _ in K.VIDEO_ENCODER:
-        v = F.max_pool2d(K.lrelu(bn(conv(v, name, s), name)), 2, 2)
+        z = conv(v, name, s)
+        v = F.max_pool2d(K.lrelu(bn(z, name, src=(v, z))), 2, 2)
         nhwc = (v.shape[0], v.shape[2], v.shape[3], v.shape[1])
         mask = torch.as_tensor(dropout_scale(seed, LAYER_INDEX[name], nhwc, rate), dtype=dt).permute(0, 3, 1, 2)
         v = v * mask
     N = a.shape[0]
     C, H, W = a.shape[1:]
     x = torch.cat([a.permute(0, 2, 3, 1).reshape(N, -1), v.permute(0, 2, 3, 1).reshape(N, -1)], dim=1)
-    x = K.lrelu(bn(x @ p["enc_dense/kernel"] + p["enc_dense/bias"], "enc_dense"))
-    x = K.lrelu(bn(x @ p["dec_dense1/kernel"] + p["dec_dense1/bias"], "dec_dense1"))
-    x = (x @ p["dec_dense2/kernel"] + p["dec_dense2/bias"]).reshape(N, H, W, C)
-    x = K.lrelu(bn(x, "dec_dense2", channel_dim=3)).permute(0, 3, 1, 2)
+    for name in ("enc_dense", "dec_dense1"):
+        z = x @ p[name + "/kernel"] + p[name + "/bias"]
+        x = K.lrelu(bn(z, name, src=(x, z)))
+    z = x @ p["dec_dense2/kernel"] + p["dec_dense2/bias"]
+    x = K.lrelu(bn(z.reshape(N, H, W, C), "dec_dense2", channel_dim=3, src=(x, z))).permute(0, 3, 1, 2)
     for name, _, _, _, s, has_bn, _, _ in K.AUDIO_DECODER:
-        x = deconv(x, name, s)
+        z = deconv(x, name, s)
         if has_bn:
-            x = K.lrelu(bn(x, name))
+            x = K.lrelu(bn(z, name, src=(x, z)))
+        else:
+            tap(name, x, z)
+            x = z
     y = x[:, 0]
     return ((y - torch.as_tensor(np.asarray(target), dtype=dt)) ** 2).mean()
 
 
-def gradients(tensors, mel, video, target, rate=0.25, seed=0, dtype=torch.float64):
+def gradients(tensors, mel, video, target, rate=0.25, seed=0, dtype=torch.float64, taps=None):
     """One training-mode forward + backward.  tensors: {name: array} (KerasModel.tensors).
-    Returns (loss, {name: gradient} for the trainable tensors, {name: (batch mean, batch var)} per BN layer)."""
+    Returns (loss, {name: gradient} for the trainable tensors, {name: (batch mean, batch var)} per BN layer).
+    taps: see train_forward."""
     p = {n: torch.tensor(np.asarray(a, dtype=np.float64), dtype=dtype,
                          requires_grad=not n.endswith(("moving_mean", "moving_variance")))
          for n, a in tensors.items()}
     stats = {}
-    loss = train_forward(p, mel, video, target, rate, seed, stats, dtype)
+    loss = train_forward(p, mel, video, target, rate, seed, stats, dtype, taps)
     loss.backward()
     grads = {n: (t.grad.double().numpy().copy() if t.grad is not None else np.zeros(t.shape)) for n, t in p.items()}
     return float(loss.detach()), grads, stats

@@ -5,9 +5,14 @@ Tolerances (float32 device arithmetic against float64 autograd through 20 layers
   * loss: relative 1e-5;
   * every gradient tensor: relative RMS <= 1e-2 — torch-CPU float32 itself lands at 1e-5..4e-3 against float64
     (v_conv1 / v_conv2 reduce over 65k-262k pixels), and an element whose BN output sits within float32 rounding
-    of zero takes the other LeakyReLU slope (measured: one such pixel of d_deconv5 moves every upstream gradient
-    by ~1.5e-3); a wrong tap, channel or mask shows up as O(1) — except the biases of layers followed by
-    BatchNormalization,
+    of zero takes the other LeakyReLU slope, or a pool tie the other winner, which moves every upstream gradient.
+    This gate is the integration check only: it cannot tell such a flip from a defect below ~1%.  The kernels
+    themselves are held to float32 rounding stage by stage in tests/test_gpu_train_local.py, where each expectation
+    is computed in float64 from the device's own upstream quantity, so no flip enters (measured there at N = 3, 2
+    and 16, all 20 layers: activation backward 4e-8, dbeta 3e-7, input gradients 2.3e-7, dW <= 1.8e-6 and
+    dz / dgamma <= 6.6e-6, dW 2.1e-5 and dz 1.2e-4 where the dense BatchNormalization of a 2-clip batch cancels;
+    profiles/train_local_checks.txt).  Here a wrong tap, channel or mask shows up as O(1) — except the biases of
+    layers followed by BatchNormalization,
     whose true gradient is exactly zero (BN removes the batch mean): there the float32 sum over the batch's pixels
     must stay below 1e-3 x the RMS of the same layer's kernel gradient;
   * BN moving statistics after the step: relative 1e-5;
@@ -110,7 +115,9 @@ def test_max_batch_1023_equals_repeated_small_batch(gpu):
         and N = 3 itself at ~0 — the signature of one LeakyReLU slope flip at a d_deconv5 BN output within fp32
         rounding of zero (the batch statistics of 6 rows round differently from those of 3), not of an
         accumulation error, which would grow with k.  The standard 1e-2 gate of the distinct-clip tests holds
-        for them (N = 1, 3, 4, 16 above)."""
+        for them (N = 1, 3, 4, 16 above).  That reading no longer rests on this test alone:
+        tests/test_gpu_train_local.py holds d_deconv5's BN backward, wgrad and dgrad to <= 2e-5 each at N = 3, 2
+        and 16 (1.7e-6 at N = 3), on the device's own upstream gradient (no flip can enter there)."""
     from avse_amd import ops
     from avse_amd.model import KerasModel
     model = KerasModel.init(seed=23, randomize=True)

@@ -15,7 +15,7 @@ from avse_amd import _lib, ops  # noqa: E402
 from avse_amd.model import KerasModel  # noqa: E402
 
 layer = int(sys.argv[1])
-mode = int(sys.argv[4]) if len(sys.argv) > 4 else 2   # 2: dz after the BN backward, 4: dL/d(input)
+mode = int(sys.argv[4]) if len(sys.argv) > 4 else 2   # 2: dz after the BN backward, 4: dL/d(input), 8: dL/d(BN output)
 count = int(sys.argv[2])
 rate = float(sys.argv[3]) if len(sys.argv) > 3 else 0.25
 dev = torch.device("cuda", 0)
