@@ -22,6 +22,7 @@ AVSE_BF16 = 1
 AVSE_F32_SPLIT = 2
 AVSE_PAD_REFLECT = 0
 AVSE_PAD_CONSTANT = 1
+AVSE_VIDEO_F32, AVSE_VIDEO_U8 = 0, 1       # avse_video_dtype: element type of a video argument (avse_*_video)
 AVSE_ERR_RANGE = 6
 AVSE_RANGE_RECOMPUTE, AVSE_RANGE_ERROR = 0, 1
 # range-guard bits (include/avse.h avse_forward_checked): bit i = plan layer i, 24 / 25 the split audio / video inputs
@@ -79,6 +80,17 @@ SIGNATURES = {
     "avse_weights_act_exponents": (_int, [_c_void_p, ctypes.POINTER(_int), _int]),
     "avse_forward_profile": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64,
                                     _c_void_p, _c_void_p, ctypes.POINTER(_flt)]),
+    # the *_video forms: (const void* video, int video_dtype) in place of (const float* video)
+    "avse_forward_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                  _c_void_p]),
+    "avse_forward_checked_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _i64,
+                                          _c_void_p, _c_void_p, _int, ctypes.POINTER(ctypes.c_uint32)]),
+    "avse_forward_profile_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _i64,
+                                          _c_void_p, _c_void_p, ctypes.POINTER(_flt)]),
+    "avse_video_stats_video": (_int, [_c_void_p, _c_void_p, _int, _i64, _int, _int, _int, _c_void_p, _c_void_p,
+                                      _c_void_p]),
+    "avse_trainer_step_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _c_void_p, _i64, _flt,
+                                       _flt, ctypes.c_uint32, _int, _c_void_p, _c_void_p]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

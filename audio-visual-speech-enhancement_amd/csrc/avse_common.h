@@ -368,11 +368,13 @@ struct HaloArgs {
     unsigned long long* prof;   // ablation harness only (ABL & 128): per-wave cycle counters, else unused
     unsigned* range_flag;    // split: range guard (ConvArgs::range_flag), nullable
     unsigned range_bit, range_in_bit;   // OUT_S16 stores / v_conv1's split of the (normalised) video input
+    int video_u8;            // V1: `video` points at uint8 [N][Hc][Wc][Ci] (AVSE_VIDEO_U8), not f32
 };
 
 int launch_conv_stream(const HaloArgs& a, hipStream_t s);   // conv_stream.hip (non-V1 variants)
 int launch_conv_v1r(const HaloArgs& a, hipStream_t s);      // conv_v1r.hip (v_conv1, kernel-row runs)
-int launch_video_prep(const float* video, const float* mean, const float* stdv, void* out, int64_t N,
+// video_u8: `video` is uint8 (AVSE_VIDEO_U8); converted exactly, then the float path's arithmetic
+int launch_video_prep(const void* video, int video_u8, const float* mean, const float* stdv, void* out, int64_t N,
                       int F, int dtype, hipStream_t s);
 int launch_audio_prep(const float* audio, void* out, int64_t npix, int dtype, hipStream_t s);
 // split dtype a_conv1 (one input channel) on the vector ALUs straight from the audio input (conv.hip k_aconv1_split)
@@ -400,5 +402,9 @@ constexpr int kVideoStatsMaxF = 8;
 size_t video_stats_scratch_bytes(int64_t S, int H, int W);
 int launch_video_stats(const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv, void* scratch,
                        hipStream_t s);
+// uint8 video: exact 64-bit integer sums of x and x^2 per pixel and chunk (the same scratch size), combined in chunk
+// order; mean and std are each rounded once to float32 from the exact integer moments
+int launch_video_stats_u8(const uint8_t* video, int64_t S, int H, int W, int F, float* mean, float* stdv, void* scratch,
+                          hipStream_t s);
 
 }  // namespace avse

@@ -150,7 +150,7 @@ struct avse_ctx {
     hipEvent_t fork = nullptr, join = nullptr;
     // avse_forward's replay cache: the whole forward captured once per argument set into a hipGraph
     struct Graph {
-        const void* key[9];
+        const void* key[10];   // forward_dispatch: weights, pointers, arena, range word, video dtype
         int64_t n;
         Options opt;
         hipGraphExec_t exec;
@@ -905,14 +905,15 @@ int build_layer(avse_weights* W, int li, const float* kernel, const float* bias,
     return 0;
 }
 
-HaloArgs halo_args(const GpuLayer& G, const void* in, const float* video, const float* vmean, const float* vstd,
-                   void* out, long long out_clip_stride, int out_pix_stride, int out_c_off, int64_t N,
+HaloArgs halo_args(const GpuLayer& G, const void* in, const void* video, int video_dtype, const float* vmean,
+                   const float* vstd, void* out, long long out_clip_stride, int out_pix_stride, int out_c_off, int64_t N,
                    const Options& opt) {
     HaloArgs a;
     std::memset(&a, 0, sizeof(a));
     a.variant = G.halo;
     a.in = in;
-    a.video = video;
+    a.video = reinterpret_cast<const float*>(video);   // V1 loaders: float, or bytes when video_u8
+    a.video_u8 = video_dtype == AVSE_VIDEO_U8;
     a.vmean = vmean;
     a.vstd = vstd;
     a.out = out;
@@ -1343,9 +1344,13 @@ void avse_weights_destroy(avse_weights* w) {
 namespace {
 // Stage order of avse_forward_profile (include/avse.h AVSE_NUM_STAGES).
 // rflag: the split dtype's range-guard word the kernels report into (avse_ctx::range)
-int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const float* video, const float* vmean,
+// vdt: avse_video_dtype of `video`
+int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt, const float* vmean,
                  const float* vstd, int64_t N, float* out, hipStream_t s, hipEvent_t* ev, unsigned* rflag) {
     if (!c || !W || !audio || !out) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (vdt != AVSE_VIDEO_F32 && vdt != AVSE_VIDEO_U8) return fail(AVSE_ERR_INVALID, "unknown video dtype");
+    if (vdt == AVSE_VIDEO_U8 && ((uintptr_t)video & 3))
+        return fail(AVSE_ERR_INVALID, "uint8 video must be 4-byte aligned (alignment of the base pointer)");
     if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be set or both NULL");
     if (!video && vmean) return fail(AVSE_ERR_INVALID, "video == NULL (all-zero video) takes no normaliser");
     if (N < 0 || N > (int64_t)(1 << 30) / (128 * 128)) return fail(AVSE_ERR_INVALID, "bad N");
@@ -1454,17 +1459,19 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const f
     if ((rc = mark())) return rc;   // video_prep stage: now the video encoder's first launch (k_conv path only)
     if ((rc = mark())) return rc;
     // video encoder (network.py:138-175) over n clips, activations at the arena offsets o, embedding into cat
-    auto video_encoder = [&](const float* vid, const float* vm, const float* vs, int64_t n, const size_t* o,
+    auto video_encoder = [&](const void* vid, int vid_dt, const float* vm, const float* vs, int64_t n, const size_t* o,
                              void* cat) -> int {
         auto vb = [&](int b) { return (void*)(c->arena + o[b]); };
         const int v_in[6] = {B_VIN, B_V1, B_V2, B_V3, B_V4, B_V5};
-        if (L(5).halo == HALO_NONE && (rc = launch_video_prep(vid, vm, vs, vb(B_VIN), n, P.F, gdt, s))) return rc;
+        if (L(5).halo == HALO_NONE &&
+            (rc = launch_video_prep(vid, vid_dt == AVSE_VIDEO_U8, vm, vs, vb(B_VIN), n, P.F, gdt, s)))
+            return rc;
         for (int i = 0; i < 6; ++i) {
             const GpuLayer& G = L(5 + i);
             if (G.halo != HALO_NONE) {
-                HaloArgs h = (i < 5) ? halo_args(G, vb(v_in[i]), vid, vm, vs, vb(v_in[i + 1]),
+                HaloArgs h = (i < 5) ? halo_args(G, vb(v_in[i]), vid, vid_dt, vm, vs, vb(v_in[i + 1]),
                                                  (long long)G.ho * G.wo * G.def.cout, G.def.cout, 0, n, opt)
-                                     : halo_args(G, vb(v_in[i]), vid, vm, vs, cat, CAT, G.def.cout, AEMB, n, opt);
+                                     : halo_args(G, vb(v_in[i]), vid, vid_dt, vm, vs, cat, CAT, G.def.cout, AEMB, n, opt);
                 if (split) {
                     // split-pair input (2 halves per channel) from the previous split layer; output split pairs for
                     // a next split layer, fp32 for a generic one (weights_load keeps the split layers a prefix)
@@ -1524,7 +1531,7 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const f
                 ev = nullptr;   // the one-off N = 1 encoder is not a profiled stage
                 rflag = c->range + 2;   // its own range word: the bits are kept with the cached embedding
                 if (split) AVSE_HIP_CHECK(hipMemsetAsync(rflag, 0, sizeof(unsigned), s));
-                rc = video_encoder(c->zero_video, nullptr, nullptr, 1, o1, c->arena + o1[B_CAT]);
+                rc = video_encoder(c->zero_video, AVSE_VIDEO_F32, nullptr, nullptr, 1, o1, c->arena + o1[B_CAT]);
                 ev = keep;
                 rflag = keep_flag;
                 stage = keep_stage;
@@ -1616,7 +1623,7 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const f
     }
     if (concurrent) AVSE_HIP_CHECK(hipEventRecord(c->join, sa));
     if (video) {
-        if ((rc = video_encoder(video, vmean, vstd, N, off, buf(B_CAT)))) return rc;
+        if ((rc = video_encoder(video, vdt, vmean, vstd, N, off, buf(B_CAT)))) return rc;
     } else {
         // all-zero video: broadcast the constant embedding computed above
         const size_t es = dt == AVSE_BF16 ? 2 : 4;
@@ -1735,13 +1742,19 @@ extern "C" {
 // are kept).  Opt-in (AVSE_GRAPH=1): a torch graph of the whole bench step (spectrogram + forward) measured 2.20 ->
 // 2.14 ms (tools/graph_probe.py), but replaying the forward alone inside the same step measured 2.234 vs 2.24-2.26 ms
 // direct (bench.py A/B, same box), so direct launches stay the default.
-static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, const float* video,
+static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
                             const float* vmean, const float* vstd, int64_t N, float* out, void* stream,
                             unsigned* rflag);
 
 int avse_forward(avse_ctx* c, const avse_weights* W, const float* audio, const float* video, const float* vmean,
                  const float* vstd, int64_t N, float* out, void* stream) {
-    if (int rc = forward_dispatch(c, W, audio, video, vmean, vstd, N, out, stream, c ? c->range : nullptr)) return rc;
+    return avse_forward_video(c, W, audio, video, AVSE_VIDEO_F32, vmean, vstd, N, out, stream);
+}
+
+int avse_forward_video(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
+                       const float* vmean, const float* vstd, int64_t N, float* out, void* stream) {
+    if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, c ? c->range : nullptr))
+        return rc;
     return avse::debug_poll(stream);
 }
 
@@ -1770,10 +1783,17 @@ int avse_range_snapshot(avse_ctx* c, void* stream, uint32_t* host_word) {
 
 int avse_forward_checked(avse_ctx* c, const avse_weights* W, const float* audio, const float* video, const float* vmean,
                          const float* vstd, int64_t N, float* out, void* stream, int mode, uint32_t* host_bits) {
+    return avse_forward_checked_video(c, W, audio, video, AVSE_VIDEO_F32, vmean, vstd, N, out, stream, mode, host_bits);
+}
+
+int avse_forward_checked_video(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
+                               const float* vmean, const float* vstd, int64_t N, float* out, void* stream, int mode,
+                               uint32_t* host_bits) {
     if (host_bits) *host_bits = 0;
     if (!c || !W) return fail(AVSE_ERR_INVALID, "NULL argument");
     if (mode != AVSE_RANGE_RECOMPUTE && mode != AVSE_RANGE_ERROR) return fail(AVSE_ERR_INVALID, "bad range mode");
-    if (W->dtype != AVSE_F32_SPLIT || N <= 0) return avse_forward(c, W, audio, video, vmean, vstd, N, out, stream);
+    if (W->dtype != AVSE_F32_SPLIT || N <= 0)
+        return avse_forward_video(c, W, audio, video, vdt, vmean, vstd, N, out, stream);
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1783,7 +1803,7 @@ int avse_forward_checked(avse_ctx* c, const avse_weights* W, const float* audio,
     unsigned* flag = c->range + 1;
     AVSE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned), s));
     // (option graph: the forward itself replays its hipGraph, so the launches after each wait are one graph launch)
-    if (int rc = forward_dispatch(c, W, audio, video, vmean, vstd, N, out, stream, flag)) return rc;
+    if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, flag)) return rc;
     AVSE_HIP_CHECK(hipMemcpyAsync(c->range_host + 1, flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     AVSE_HIP_CHECK(hipStreamSynchronize(s));
     const unsigned bits = c->range_host[1];
@@ -1805,21 +1825,21 @@ int avse_forward_checked(avse_ctx* c, const avse_weights* W, const float* audio,
         }
         twin = W->f32_twin;
     }
-    if (int rc = forward_impl(c, twin, audio, video, vmean, vstd, N, out, s, nullptr, nullptr)) return rc;
+    if (int rc = forward_impl(c, twin, audio, video, vdt, vmean, vstd, N, out, s, nullptr, nullptr)) return rc;
     return avse::debug_poll(stream);
 }
 
-static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, const float* video,
+static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
                             const float* vmean, const float* vstd, int64_t N, float* out, void* stream,
                             unsigned* rflag) {
     if (!c || !W || N <= 0 || !c->opt.graph)
-        return forward_impl(c, W, audio, video, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag);
+        return forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag);
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     if (W->device != c->device) return fail(AVSE_ERR_INVALID, "weights and context are on different devices");
     int rc = ensure_arena(c, N, W->dtype, W->plan, (hipStream_t)stream);   // no allocation inside the capture
     if (rc) return rc;
-    const void* key[9] = {(const void*)W->serial, audio, video, vmean, vstd, out, c->arena, (const void*)c->arena_bytes,
-                          rflag};
+    const void* key[10] = {(const void*)W->serial, audio, video, vmean, vstd, out, c->arena, (const void*)c->arena_bytes,
+                           rflag, (const void*)(uintptr_t)vdt};
     avse_ctx::Graph* hit = nullptr;
     for (auto& g : c->graphs)
         if (g.n == N && std::memcmp(&g.opt, &c->opt, sizeof(Options)) == 0 && std::memcmp(g.key, key, sizeof(key)) == 0)
@@ -1841,11 +1861,11 @@ static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* aud
         g.opt = c->opt;
         g.exec = nullptr;
         c->graphs.push_back(g);
-        return forward_impl(c, W, audio, video, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag);
+        return forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag);
     }
     if (!c->cap) AVSE_HIP_CHECK(hipStreamCreateWithFlags(&c->cap, hipStreamNonBlocking));
     AVSE_HIP_CHECK(hipStreamBeginCapture(c->cap, hipStreamCaptureModeRelaxed));
-    rc = forward_impl(c, W, audio, video, vmean, vstd, N, out, c->cap, nullptr, rflag);
+    rc = forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, c->cap, nullptr, rflag);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(c->cap, &graph);
     if (rc || ce != hipSuccess) {
@@ -1863,11 +1883,17 @@ static int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* aud
 
 int avse_forward_profile(avse_ctx* c, const avse_weights* W, const float* audio, const float* video,
                          const float* vmean, const float* vstd, int64_t N, float* out, void* stream, float* host_ms) {
+    return avse_forward_profile_video(c, W, audio, video, AVSE_VIDEO_F32, vmean, vstd, N, out, stream, host_ms);
+}
+
+int avse_forward_profile_video(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
+                               const float* vmean, const float* vstd, int64_t N, float* out, void* stream,
+                               float* host_ms) {
     if (!host_ms) return fail(AVSE_ERR_INVALID, "host_ms is NULL");
     if (c) AVSE_HIP_CHECK(hipSetDevice(c->device));
     hipEvent_t ev[AVSE_NUM_STAGES + 1];
     for (int i = 0; i <= AVSE_NUM_STAGES; ++i) AVSE_HIP_CHECK(hipEventCreate(&ev[i]));
-    int rc = forward_impl(c, W, audio, video, vmean, vstd, N, out, (hipStream_t)stream, ev, c ? c->range : nullptr);
+    int rc = forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, (hipStream_t)stream, ev, c ? c->range : nullptr);
     if (!rc) {
         AVSE_HIP_CHECK(hipEventSynchronize(ev[AVSE_NUM_STAGES]));
         for (int i = 0; i < AVSE_NUM_STAGES; ++i) {
@@ -1911,13 +1937,25 @@ int avse_mix_pairs(avse_ctx* c, const int16_t* speech, const int64_t* speech_off
 
 int avse_video_stats(avse_ctx* c, const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv,
                      void* stream) {
+    return avse_video_stats_video(c, video, AVSE_VIDEO_F32, S, H, W, F, mean, stdv, stream);
+}
+
+int avse_video_stats_video(avse_ctx* c, const void* video, int vdt, int64_t S, int H, int W, int F, float* mean,
+                           float* stdv, void* stream) {
     if (!c || !video || !mean || !stdv) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (vdt != AVSE_VIDEO_F32 && vdt != AVSE_VIDEO_U8) return fail(AVSE_ERR_INVALID, "unknown video dtype");
+    if (vdt == AVSE_VIDEO_U8 && ((uintptr_t)video & 3))
+        return fail(AVSE_ERR_INVALID, "uint8 video must be 4-byte aligned (alignment of the base pointer)");
     if (S <= 0 || H <= 0 || W <= 0 || F <= 0) return fail(AVSE_ERR_INVALID, "bad video shape (every extent positive)");
     if (F > kVideoStatsMaxF) return fail(AVSE_ERR_UNSUPPORTED, "more than 8 frames per slice not supported");
     if ((int64_t)H * W * F >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "H * W * F must be below 2^31");
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     if (int rc = ensure_prep(c, video_stats_scratch_bytes(S, H, W), (hipStream_t)stream)) return rc;
-    return launch_video_stats(video, S, H, W, F, mean, stdv, c->prep, (hipStream_t)stream);
+    if (vdt == AVSE_VIDEO_U8)
+        return launch_video_stats_u8(reinterpret_cast<const uint8_t*>(video), S, H, W, F, mean, stdv, c->prep,
+                                     (hipStream_t)stream);
+    return launch_video_stats(reinterpret_cast<const float*>(video), S, H, W, F, mean, stdv, c->prep,
+                              (hipStream_t)stream);
 }
 
 int avse_debug_scratch(avse_ctx* c, int64_t N, int dtype, void** base, int64_t* offsets) {

@@ -557,19 +557,20 @@ __global__ void k_splitk_reduce_tiles(ConvArgs a) {
 }
 
 // video [N][128][128][F] f32 -> (x - mean) / std -> T [N][128][128][8] (channels F..7 zero; F <= 8)
-template <typename T>
-__global__ void k_video_prep(const float* __restrict__ v, const float* __restrict__ mean, const float* __restrict__ stdv,
+// VT: the video's element type, float or uint8_t (AVSE_VIDEO_U8: float(byte) is exact, the rest is the float path)
+template <typename T, typename VT = float>
+__global__ void k_video_prep(const VT* __restrict__ v, const float* __restrict__ mean, const float* __restrict__ stdv,
                              T* __restrict__ out, long long npix, int F) {
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
         const int hw = (int)(p % (128 * 128));
-        const float* src = v + p * F;
+        const VT* src = v + p * F;
         float m = 0.f, s = 1.f;
         const bool norm = mean != nullptr;
         if (norm) { m = mean[hw]; s = stdv[hw]; }
         T o[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            float x = c < F ? src[c] : 0.f;
+            float x = c < F ? (float)src[c] : 0.f;
             if (norm && c < F) x = (x - m) / s;
             o[c] = from_f<T>(x);
         }
@@ -849,12 +850,18 @@ int launch_broadcast_row(const void* src, void* dst, int64_t rows, int64_t row_b
     return 0;
 }
 
-int launch_video_prep(const float* video, const float* mean, const float* stdv, void* out, int64_t N, int F, int dtype,
-                      hipStream_t s) {
+int launch_video_prep(const void* video, int video_u8, const float* mean, const float* stdv, void* out, int64_t N, int F,
+                      int dtype, hipStream_t s) {
     const long long npix = (long long)N * 128 * 128;
     if (F < 1 || F > 8) { set_error("video frames per slice must be 1..8"); return 1; }
-    if (dtype == 1) hipLaunchKernelGGL(k_video_prep<bf16_t>, dim3(grid_for(npix, 256)), dim3(256), 0, s, video, mean, stdv, (bf16_t*)out, npix, F);
-    else hipLaunchKernelGGL(k_video_prep<float>, dim3(grid_for(npix, 256)), dim3(256), 0, s, video, mean, stdv, (float*)out, npix, F);
+    const dim3 grid(grid_for(npix, 256));
+    const float* vf = reinterpret_cast<const float*>(video);
+    const uint8_t* vb = reinterpret_cast<const uint8_t*>(video);
+    if (video_u8) {
+        if (dtype == 1) hipLaunchKernelGGL((k_video_prep<bf16_t, uint8_t>), grid, dim3(256), 0, s, vb, mean, stdv, (bf16_t*)out, npix, F);
+        else hipLaunchKernelGGL((k_video_prep<float, uint8_t>), grid, dim3(256), 0, s, vb, mean, stdv, (float*)out, npix, F);
+    } else if (dtype == 1) hipLaunchKernelGGL(k_video_prep<bf16_t>, grid, dim3(256), 0, s, vf, mean, stdv, (bf16_t*)out, npix, F);
+    else hipLaunchKernelGGL(k_video_prep<float>, grid, dim3(256), 0, s, vf, mean, stdv, (float*)out, npix, F);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }

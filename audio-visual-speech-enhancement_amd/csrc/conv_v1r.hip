@@ -39,6 +39,39 @@ __device__ __forceinline__ void barrier_raw() { asm volatile("s_barrier" ::: "me
 // B-operand lane groups, tools/lds_swizzle_search.py)
 __device__ __forceinline__ int wsw(int co) { return 2 * ((co >> 2) & 1); }
 
+// VT (template, the loader waves' video element type): float, or unsigned char for uint8 crops (HaloArgs::video_u8).
+// A uint8 window pixel is NF bytes at byte offset pix * NF of its clip, which is not dword aligned: it lies inside the
+// two aligned dwords at (pix * NF) & ~3 and + 4 (NF = 5 at any offset mod 4; NF = 6 at offset 0 or 2), loaded through
+// the same per-clip resource (H W NF is a multiple of 4: no aligned dword straddles a clip, and the clip base is
+// 4-byte aligned because the C-ABI refuses any other video pointer).  The loader keeps the two dwords and the byte
+// shift per pixel (3 VGPRs per register set where the float loader holds NF) and unpacks them when the window is
+// stored: a byte funnel shift (v_alignbyte_b32) brings bytes s .. s + 3 into one dword, a shift the rest, and
+// v_cvt_f32_ubyte0..3 convert — exactly, so everything downstream is the float path's code on the same values.
+template <typename VT>
+constexpr bool kU8 = std::is_same<VT, unsigned char>::value;
+template <int NF, int M>
+__device__ __forceinline__ void u8_pixel(unsigned lo, unsigned hi, int s, float (&f)[M]) {
+    static_assert(M >= NF && M <= 6, "frames");
+    const unsigned a = __builtin_amdgcn_alignbyte(hi, lo, (unsigned)s);   // bytes s .. s + 3 of (hi:lo)
+    const unsigned b = hi >> (8 * s);                                     // bytes s + 4 .. 7
+    f[0] = (float)(a & 0xffu);
+    f[1] = (float)((a >> 8) & 0xffu);
+    f[2] = (float)((a >> 16) & 0xffu);
+    f[3] = (float)(a >> 24);
+    f[4] = (float)(b & 0xffu);
+    if constexpr (M > 5) f[5] = NF == 6 ? (float)((b >> 8) & 0xffu) : 0.f;
+}
+// the two aligned dwords of window pixel `pix` (offset kOOB, which the resource answers with zeros, outside the image)
+template <int NF>
+__device__ __forceinline__ void u8_load(__amdgpu_buffer_rsrc_t vrs, int pix, int ok, unsigned& lo, unsigned& hi,
+                                        int& s) {
+    const int boff = pix * NF;
+    const int voff = ok ? boff & ~3 : kOOB;
+    lo = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 0, 0);
+    hi = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(vrs, voff + 4, 0, 0);
+    s = boff & 3;
+}
+
 // NF (template): video frames per clip, 5 (25 / 29.97 fps) or 6 (30 fps: the 12-byte window pixel's sixth half
 // holds a real frame instead of the zero, and the weights' k = kx * 6 + 5 rows are the sixth frame's)
 constexpr int TH = 16, TW = 16, KS = 5, PAD = 2;
@@ -63,7 +96,7 @@ static_assert(HSLOT % 16 == 0 && LDS_BYTES <= 160 * 1024, "LDS");
 
 // ABL: ablation mask for tools/v1r_ablate.hip only (0 in the library): 1 = loaders skip the output pass,
 // 2 = loaders skip the per-tile window work, 4 = no MFMAs, 8 = no barrier in the tile loop
-template <int ABL = 0, int NF = 5>
+template <int ABL = 0, int NF = 5, typename VT = float>
 __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
     static_assert(NF == 5 || NF == 6, "frames");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
@@ -113,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
                 if (off >= HH * HWP * PB || (off / PB) % HWP >= HW) reinterpret_cast<int*>(halo)[i] = 0;
             }
         }
-        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * 4;
+        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * (long long)sizeof(VT);
         const bool norm = a.vmean != nullptr;
         const __amdgpu_buffer_rsrc_t mrs = make_rsrc(norm ? a.vmean : a.video, (long long)a.Hc * a.Wc * 4);
         const __amdgpu_buffer_rsrc_t srs = make_rsrc(norm ? a.vstd : a.video, (long long)a.Hc * a.Wc * 4);
@@ -122,6 +155,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
         f32x4 v4[2][PPL];
         float v1[2][PPL], v5[2][PPL], pm[2][PPL], ps[2][PPL];
         int pok[2][PPL];
+        unsigned u0[2][PPL], u1[2][PPL];   // VT uint8: the pixel's two aligned dwords and its byte shift (u8_load)
+        int ub[2][PPL];
         auto win_load = [&](auto set, int k) {
             constexpr int Q = decltype(set)::value;
             int clip, oy0, ox0;
@@ -136,10 +171,14 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
                 const int ok = (int)(P < HPIX) & (int)((unsigned)iy < (unsigned)a.Hc) & (int)((unsigned)ix < (unsigned)a.Wc);
                 const int pix = iy * a.Wc + ix;
                 const int voff = ok ? pix * NF * 4 : kOOB, moff = ok ? pix * 4 : kOOB;
-                v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
-                v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
-                if constexpr (NF == 6)
-                    v5[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 20, 0));
+                if constexpr (kU8<VT>) {
+                    u8_load<NF>(vrs, pix, ok, u0[Q][e], u1[Q][e], ub[Q][e]);
+                } else {
+                    v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
+                    v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
+                    if constexpr (NF == 6)
+                        v5[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 20, 0));
+                }
                 pm[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, moff, 0, 0));
                 ps[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, moff, 0, 0));
                 pok[Q][e] = ok;
@@ -154,7 +193,15 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
                 if (P >= HPIX) continue;
                 // v_rcp_f32 (1 ulp) and packed conversions: the loader shares its SIMD's issue with the MFMA wave
                 const float rs = __builtin_amdgcn_rcpf(ps[Q][e]);
-                float f[6] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e], NF == 6 ? v5[Q][e] : 0.f};
+                float f[6];
+                if constexpr (kU8<VT>) {
+                    u8_pixel<NF>(u0[Q][e], u1[Q][e], ub[Q][e], f);
+                } else {
+                    const float g[6] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e],
+                                        NF == 6 ? v5[Q][e] : 0.f};
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) f[i] = g[i];
+                }
 #pragma unroll
                 for (int i = 0; i < NF; ++i) {
                     const float n = norm ? (f[i] - pm[Q][e]) * rs : f[i];
@@ -371,7 +418,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // CW compute waves + 4 loader waves.  CW = 4: compute wave w owns conv rows 4w .. 4w+3 x all 128 channels (one
 // compute wave per SIMD); CW = 8: rows 4 (w & 3) .. x channels 64 (w >> 2) .. +63 — two compute waves per SIMD, so one
 // wave's MFMAs cover the other's LDS waits (half the accumulators, the A fragments read by both)
-template <int CW, int NF = 5>
+template <int CW, int NF = 5, typename VT = float>
 __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
     static_assert(CW == 4 || CW == 8, "compute waves");
     static_assert(NF == 5 || NF == 6, "frames");
@@ -421,13 +468,15 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
                 if (off >= HH * HWP * PB || (off / PB) % HWP >= HW) reinterpret_cast<int*>(halo)[i] = 0;
             }
         }
-        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * 4;
+        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * (long long)sizeof(VT);
         const bool norm = a.vmean != nullptr;
         const __amdgpu_buffer_rsrc_t mrs = make_rsrc(norm ? a.vmean : a.video, (long long)a.Hc * a.Wc * 4);
         const __amdgpu_buffer_rsrc_t srs = make_rsrc(norm ? a.vstd : a.video, (long long)a.Hc * a.Wc * 4);
         f32x4 v4[2][PPL];
         float v1[2][PPL], v5[2][PPL], pm[2][PPL], ps[2][PPL];
         int pok[2][PPL];
+        unsigned u0[2][PPL], u1[2][PPL];   // VT uint8: the pixel's two aligned dwords and its byte shift (u8_load)
+        int ub[2][PPL];
         auto win_load = [&](auto set, int k) {
             constexpr int Q = decltype(set)::value;
             int clip, oy0, ox0;
@@ -442,10 +491,14 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
                 const int ok = (int)(P < HPIX) & (int)((unsigned)iy < (unsigned)a.Hc) & (int)((unsigned)ix < (unsigned)a.Wc);
                 const int pix = iy * a.Wc + ix;
                 const int voff = ok ? pix * NF * 4 : kOOB, moff = ok ? pix * 4 : kOOB;
-                v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
-                v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
-                if constexpr (NF == 6)
-                    v5[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 20, 0));
+                if constexpr (kU8<VT>) {
+                    u8_load<NF>(vrs, pix, ok, u0[Q][e], u1[Q][e], ub[Q][e]);
+                } else {
+                    v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
+                    v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
+                    if constexpr (NF == 6)
+                        v5[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 20, 0));
+                }
                 pm[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, moff, 0, 0));
                 ps[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, moff, 0, 0));
                 pok[Q][e] = ok;
@@ -459,7 +512,15 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
             for (int e = 0; e < PPL; ++e) {
                 const int P = L + 256 * e;
                 if (P >= HPIX) continue;
-                float f[6] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e], NF == 6 ? v5[Q][e] : 0.f};
+                float f[6];
+                if constexpr (kU8<VT>) {
+                    u8_pixel<NF>(u0[Q][e], u1[Q][e], ub[Q][e], f);
+                } else {
+                    const float g[6] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e],
+                                        NF == 6 ? v5[Q][e] : 0.f};
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) f[i] = g[i];
+                }
 #pragma unroll
                 for (int i = 0; i < NF; ++i) {
                     const float n = norm ? (f[i] - pm[Q][e]) / ps[Q][e] : f[i];
@@ -662,7 +723,7 @@ constexpr int LDS_P = VP_WIMG + NWS * VP_SLOT + SSH;
 static_assert(LDS_P <= 160 * 1024 && VP_SLOT % 16 == 0, "LDS (packed split v_conv1)");
 static_assert(VP_R >= HW * 8 && VP_S0 >= VP_R + TW * 8 && VP_S1 >= VP_S0 + TW * 8 && VP_PITCH >= VP_S1 + TW * 8, "row");
 
-template <int CW>
+template <int CW, typename VT = float>
 __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
     static_assert(CW == 4 || CW == 8, "compute waves");
     constexpr int NF = 5;
@@ -715,13 +776,15 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
                 *reinterpret_cast<unsigned*>(p + 4) = 0u;
             }
         }
-        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * 4;
+        const long long clip_bytes = (long long)a.Hc * a.Wc * NF * (long long)sizeof(VT);
         const bool norm = a.vmean != nullptr;
         const __amdgpu_buffer_rsrc_t mrs = make_rsrc(norm ? a.vmean : a.video, (long long)a.Hc * a.Wc * 4);
         const __amdgpu_buffer_rsrc_t srs = make_rsrc(norm ? a.vstd : a.video, (long long)a.Hc * a.Wc * 4);
         f32x4 v4[2][PPL];
         float v1[2][PPL], pm[2][PPL], ps[2][PPL];
         int pok[2][PPL];
+        unsigned u0[2][PPL], u1[2][PPL];   // VT uint8: the pixel's two aligned dwords and its byte shift (u8_load)
+        int ub[2][PPL];
         auto win_load = [&](auto set, int k) {
             constexpr int Q = decltype(set)::value;
             int clip, oy0, ox0;
@@ -736,8 +799,12 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
                 const int ok = (int)(P < HPIX) & (int)((unsigned)iy < (unsigned)a.Hc) & (int)((unsigned)ix < (unsigned)a.Wc);
                 const int pix = iy * a.Wc + ix;
                 const int voff = ok ? pix * NF * 4 : kOOB, moff = ok ? pix * 4 : kOOB;
-                v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
-                v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
+                if constexpr (kU8<VT>) {
+                    u8_load<NF>(vrs, pix, ok, u0[Q][e], u1[Q][e], ub[Q][e]);
+                } else {
+                    v4[Q][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, 0, 0));
+                    v1[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, voff, 16, 0));
+                }
                 pm[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, moff, 0, 0));
                 ps[Q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, moff, 0, 0));
                 pok[Q][e] = ok;
@@ -750,7 +817,14 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
             for (int e = 0; e < PPL; ++e) {
                 const int P = L + 256 * e;
                 if (P >= HPIX) continue;
-                float f[5] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e]};
+                float f[5];
+                if constexpr (kU8<VT>) {
+                    u8_pixel<NF>(u0[Q][e], u1[Q][e], ub[Q][e], f);
+                } else {
+                    const float g[5] = {v4[Q][e][0], v4[Q][e][1], v4[Q][e][2], v4[Q][e][3], v1[Q][e]};
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) f[i] = g[i];
+                }
                 _Float16 h[5], l[5];
 #pragma unroll
                 for (int i = 0; i < NF; ++i) {
@@ -966,59 +1040,61 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
 #ifndef AVSE_V1S_CW
 #define AVSE_V1S_CW 8
 #endif
-int launch_conv_v1r(const HaloArgs& a, hipStream_t s) {
-    if (a.variant == HALO_V1P) {
-        constexpr int CW = AVSE_V1S_CW;
-        if (int rc = ensure_lds_attr((const void*)k_conv_v1p<CW>, LDS_P)) return rc;
-        if (!a.split || a.Hc % TH || a.Wc % TW || a.Co != 128 || a.Ci != 5 || !a.w || a.out_mode != OUT_S16) {
-            set_error("v_conv1 packed split kernel: unexpected layer shape, packing or output format");
-            return 3;
-        }
-        int dev = 0, ncu = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int tiles = a.N * (a.Hc / TH) * (a.Wc / TW);
-        int gx = ncu >= 8 ? ncu / 8 * 8 : ncu;
-        if (gx > tiles) gx = tiles;
-        hipLaunchKernelGGL((k_conv_v1p<CW>), dim3(gx), dim3(64 * (CW + 4)), LDS_P, s, a);
-        AVSE_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (a.split) {
-        constexpr int CW = AVSE_V1S_CW;
-        const void* kf = a.Ci == 6 ? (const void*)k_conv_v1s<CW, 6> : (const void*)k_conv_v1s<CW, 5>;
-        if (int rc = ensure_lds_attr(kf, LDS_S)) return rc;
-        if (a.Hc % TH || a.Wc % TW || a.Co != 128 || (a.Ci != 5 && a.Ci != 6) || !a.w || a.out_mode != OUT_S16) {
-            set_error("v_conv1 split kernel: unexpected layer shape, packing or output format");
-            return 3;
-        }
-        int dev = 0, ncu = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int tiles = a.N * (a.Hc / TH) * (a.Wc / TW);
-        int gx = ncu >= 8 ? ncu / 8 * 8 : ncu;
-        if (gx > tiles) gx = tiles;
-        if (a.Ci == 6) hipLaunchKernelGGL((k_conv_v1s<CW, 6>), dim3(gx), dim3(64 * (CW + 4)), LDS_S, s, a);
-        else hipLaunchKernelGGL((k_conv_v1s<CW, 5>), dim3(gx), dim3(64 * (CW + 4)), LDS_S, s, a);
-        AVSE_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    const void* kf = a.Ci == 6 ? (const void*)k_conv_v1r<0, 6> : (const void*)k_conv_v1r<0, 5>;
-    if (int rc = ensure_lds_attr(kf, LDS_LAUNCH)) return rc;
-    if (a.Hc % TH || a.Wc % TW || a.Co != 128 || (a.Ci != 5 && a.Ci != 6) || !a.w) {
-        set_error("v_conv1 row-run kernel: unexpected layer shape or missing packing");
-        return 3;
-    }
+namespace {
+// one persistent workgroup per CU (a multiple of the 8 XCDs), at most one per tile
+template <typename K>
+int launch_v1(K kern, int lds, int threads, const HaloArgs& a, hipStream_t s) {
+    if (int rc = ensure_lds_attr((const void*)kern, lds)) return rc;
     int dev = 0, ncu = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     const int tiles = a.N * (a.Hc / TH) * (a.Wc / TW);
     int gx = ncu >= 8 ? ncu / 8 * 8 : ncu;
     if (gx > tiles) gx = tiles;
-    if (a.Ci == 6) hipLaunchKernelGGL((k_conv_v1r<0, 6>), dim3(gx), dim3(512), LDS_LAUNCH, s, a);
-    else hipLaunchKernelGGL((k_conv_v1r<0, 5>), dim3(gx), dim3(512), LDS_LAUNCH, s, a);
+    hipLaunchKernelGGL(kern, dim3(gx), dim3(threads), lds, s, a);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
+}
+}  // namespace
+
+int launch_conv_v1r(const HaloArgs& a, hipStream_t s) {
+    typedef unsigned char u8;
+    // uint8 video: the loaders read whole dwords of a clip, so the base must be dword aligned (the clips are: H W Ci is
+    // a multiple of 4 for the 16 x 16 tiling)
+    if (a.video_u8 && ((uintptr_t)a.video & 3)) {
+        set_error("v_conv1: uint8 video must be 4-byte aligned");
+        return 3;
+    }
+    if (a.variant == HALO_V1P) {
+        constexpr int CW = AVSE_V1S_CW;
+        if (!a.split || a.Hc % TH || a.Wc % TW || a.Co != 128 || a.Ci != 5 || !a.w || a.out_mode != OUT_S16) {
+            set_error("v_conv1 packed split kernel: unexpected layer shape, packing or output format");
+            return 3;
+        }
+        return a.video_u8 ? launch_v1(k_conv_v1p<CW, u8>, LDS_P, 64 * (CW + 4), a, s)
+                          : launch_v1(k_conv_v1p<CW>, LDS_P, 64 * (CW + 4), a, s);
+    }
+    if (a.split) {
+        constexpr int CW = AVSE_V1S_CW;
+        if (a.Hc % TH || a.Wc % TW || a.Co != 128 || (a.Ci != 5 && a.Ci != 6) || !a.w || a.out_mode != OUT_S16) {
+            set_error("v_conv1 split kernel: unexpected layer shape, packing or output format");
+            return 3;
+        }
+        if (a.video_u8)
+            return a.Ci == 6 ? launch_v1(k_conv_v1s<CW, 6, u8>, LDS_S, 64 * (CW + 4), a, s)
+                             : launch_v1(k_conv_v1s<CW, 5, u8>, LDS_S, 64 * (CW + 4), a, s);
+        return a.Ci == 6 ? launch_v1(k_conv_v1s<CW, 6>, LDS_S, 64 * (CW + 4), a, s)
+                         : launch_v1(k_conv_v1s<CW, 5>, LDS_S, 64 * (CW + 4), a, s);
+    }
+    if (a.Hc % TH || a.Wc % TW || a.Co != 128 || (a.Ci != 5 && a.Ci != 6) || !a.w) {
+        set_error("v_conv1 row-run kernel: unexpected layer shape or missing packing");
+        return 3;
+    }
+    if (a.video_u8)
+        return a.Ci == 6 ? launch_v1(k_conv_v1r<0, 6, u8>, LDS_LAUNCH, 512, a, s)
+                         : launch_v1(k_conv_v1r<0, 5, u8>, LDS_LAUNCH, 512, a, s);
+    return a.Ci == 6 ? launch_v1(k_conv_v1r<0, 6>, LDS_LAUNCH, 512, a, s)
+                     : launch_v1(k_conv_v1r<0, 5>, LDS_LAUNCH, 512, a, s);
 }
 
 }  // namespace avse

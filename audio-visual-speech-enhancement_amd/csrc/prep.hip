@@ -298,6 +298,53 @@ __global__ __launch_bounds__(kThreads) void k_video_moments_finish(const float* 
     stdv[pix] = (float)__dsqrt_rn(var);
 }
 
+// uint8 video: grid as k_video_moments, one pixel per thread.  Sums of bytes and of their squares are exact in 64-bit
+// integers (255^2 S F < 2^64 for any video that fits in memory), so there is no pivot and no staging: a thread reads its
+// pixel's F consecutive bytes of each slice (a wave reads one contiguous 64 F-byte run) and the partials are integers.
+__global__ __launch_bounds__(kThreads) void k_video_moments_u8(const uint8_t* __restrict__ video, int64_t S, int HW, int F,
+                                                               int chunk_len, u64* __restrict__ partial) {
+    const int pix = blockIdx.x * kPix + threadIdx.x;
+    if (pix >= HW) return;
+    const int64_t P = (int64_t)HW * F;
+    const int64_t s0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t s1 = s0 + chunk_len < S ? s0 + chunk_len : S;
+    const uint8_t* src = video + s0 * P + (int64_t)pix * F;
+    u64 sx = 0, sx2 = 0;
+    for (int64_t s = s0; s < s1; ++s, src += P) {
+        unsigned a = 0, a2 = 0;   // one slice: at most 8 x 255^2
+#pragma unroll
+        for (int f = 0; f < kVideoStatsMaxF; ++f)
+            if (f < F) {
+                const unsigned x = src[f];
+                a += x;
+                a2 += x * x;
+            }
+        sx += a;
+        sx2 += a2;
+    }
+    partial[((int64_t)blockIdx.y * 2 + 0) * HW + pix] = sx;
+    partial[((int64_t)blockIdx.y * 2 + 1) * HW + pix] = sx2;
+}
+
+// mean = Sx / n and var = (n Sx2 - Sx^2) / n^2 from the exact integer moments (the numerator in 128 bits), each rounded
+// once to float64 by the division and once more to float32
+__global__ __launch_bounds__(kThreads) void k_video_moments_u8_finish(const u64* __restrict__ partial, int n_chunks,
+                                                                      int64_t S, int HW, int F, float* __restrict__ mean,
+                                                                      float* __restrict__ stdv) {
+    const int pix = blockIdx.x * kThreads + threadIdx.x;
+    if (pix >= HW) return;
+    u64 sx = 0, sx2 = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        sx += partial[((int64_t)c * 2 + 0) * HW + pix];
+        sx2 += partial[((int64_t)c * 2 + 1) * HW + pix];
+    }
+    const u64 n = (u64)S * (u64)F;
+    const unsigned __int128 num = (unsigned __int128)n * sx2 - (unsigned __int128)sx * sx;   // >= 0 (Cauchy-Schwarz)
+    const double numd = (double)(u64)(num >> 64) * 18446744073709551616.0 + (double)(u64)num;
+    mean[pix] = (float)__ddiv_rn((double)sx, (double)n);
+    stdv[pix] = (float)__dsqrt_rn(__ddiv_rn(numd, (double)n * (double)n));
+}
+
 }  // namespace
 
 size_t mix_pairs_scratch_bytes(int64_t n_pairs) { return (size_t)n_pairs * (4 * sizeof(u64) + sizeof(double)); }
@@ -362,6 +409,22 @@ int launch_video_stats(const float* video, int64_t S, int H, int W, int F, float
     AVSE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_video_moments_finish, dim3((unsigned)((HW + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
                        video, partial, nc, S, HW, F, mean, stdv);
+    AVSE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_video_stats_u8(const uint8_t* video, int64_t S, int H, int W, int F, float* mean, float* stdv, void* scratch,
+                          hipStream_t s) {
+    int nc, cl;
+    video_stats_plan(S, &nc, &cl);
+    const int HW = H * W;
+    u64* partial = reinterpret_cast<u64*>(scratch);   // video_stats_scratch_bytes: 2 x 8 bytes per chunk and pixel
+    static_assert(sizeof(u64) == sizeof(double), "scratch size");
+    hipLaunchKernelGGL(k_video_moments_u8, dim3((unsigned)((HW + kPix - 1) / kPix), (unsigned)nc), dim3(kThreads), 0, s,
+                       video, S, HW, F, cl, partial);
+    AVSE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_video_moments_u8_finish, dim3((unsigned)((HW + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                       (const u64*)partial, nc, S, HW, F, mean, stdv);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }

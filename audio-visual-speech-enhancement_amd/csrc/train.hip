@@ -87,14 +87,16 @@ __global__ __launch_bounds__(256) void k_pack(float* __restrict__ wfwd, float* _
 }
 
 // video [N][128][128][F] -> (x - mean) / std (VideoNormalizer, data_processor.py:208-212) -> [N][128][128][8]
-__global__ void k_prep_video(const float* __restrict__ v, const float* __restrict__ mean, const float* __restrict__ stdv,
+// VT: float, or uint8_t crops (AVSE_VIDEO_U8; float(byte) is exact, so both give the same bits for the same pixels)
+template <typename VT = float>
+__global__ void k_prep_video(const VT* __restrict__ v, const float* __restrict__ mean, const float* __restrict__ stdv,
                              float* __restrict__ out, long long npix, int hw, int F) {
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
         const int q = (int)(p % hw);
         const float m = mean ? mean[q] : 0.f, s = stdv ? stdv[q] : 1.f;
         float o[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) o[c] = c >= F ? 0.f : mean ? (v[p * F + c] - m) / s : v[p * F + c];
+        for (int c = 0; c < 8; ++c) o[c] = c >= F ? 0.f : mean ? ((float)v[p * F + c] - m) / s : (float)v[p * F + c];
         float4* d = reinterpret_cast<float4*>(out + p * 8);
         d[0] = make_float4(o[0], o[1], o[2], o[3]);
         d[1] = make_float4(o[4], o[5], o[6], o[7]);
@@ -1343,8 +1345,9 @@ int wgrad(avse_trainer* t, const TLayer& T, const float* dz, int64_t N, hipStrea
     return 0;
 }
 
-int step_impl(avse_trainer* t, const float* audio, const float* video, const float* target, const float* vmean,
-              const float* vstd, int64_t N, float lr, float drop, uint32_t seed, int flags, float* loss, hipStream_t s) {
+int step_impl(avse_trainer* t, const float* audio, const void* video, int video_dtype, const float* target,
+              const float* vmean, const float* vstd, int64_t N, float lr, float drop, uint32_t seed, int flags,
+              float* loss, hipStream_t s) {
     // ---- weight packings from the current parameters ----
     hipLaunchKernelGGL(k_pack, dim3((unsigned)t->n_pack_tiles), dim3(256), 0, s, t->wfwd, t->wdg, (const float*)t->P,
                        (const PackTile*)t->pack_tiles);
@@ -1353,8 +1356,12 @@ int step_impl(avse_trainer* t, const float* audio, const float* video, const flo
     // ---- inputs ----
     const long long spec = (long long)kMels * t->plan.T;
     hipLaunchKernelGGL(k_prep_audio, dim3(grid_for(N * spec)), dim3(256), 0, s, audio, t->in_audio, (long long)N * spec);
-    hipLaunchKernelGGL(k_prep_video, dim3(grid_for(N * 16384)), dim3(256), 0, s, video, vmean, vstd, t->in_video,
-                       (long long)N * 16384, 16384, t->plan.F);
+    if (video_dtype == AVSE_VIDEO_U8)
+        hipLaunchKernelGGL(k_prep_video<uint8_t>, dim3(grid_for(N * 16384)), dim3(256), 0, s, (const uint8_t*)video, vmean,
+                           vstd, t->in_video, (long long)N * 16384, 16384, t->plan.F);
+    else
+        hipLaunchKernelGGL(k_prep_video<float>, dim3(grid_for(N * 16384)), dim3(256), 0, s, (const float*)video, vmean, vstd,
+                           t->in_video, (long long)N * 16384, 16384, t->plan.F);
     AVSE_HIP_CHECK(hipGetLastError());
     // ---- forward ----
     for (int i = 0; i < kNumLayers; ++i) {
@@ -1524,12 +1531,22 @@ void avse_trainer_destroy(avse_trainer* t) {
 int avse_trainer_step(avse_trainer* t, const float* audio, const float* video, const float* target, const float* vnorm_mean,
                       const float* vnorm_std, int64_t N, float lr, float dropout_rate, uint32_t dropout_seed, int flags,
                       float* loss, void* stream) {
+    return avse_trainer_step_video(t, audio, video, AVSE_VIDEO_F32, target, vnorm_mean, vnorm_std, N, lr, dropout_rate,
+                                   dropout_seed, flags, loss, stream);
+}
+
+int avse_trainer_step_video(avse_trainer* t, const float* audio, const void* video, int video_dtype, const float* target,
+                            const float* vnorm_mean, const float* vnorm_std, int64_t N, float lr, float dropout_rate,
+                            uint32_t dropout_seed, int flags, float* loss, void* stream) {
     if (!t || !audio || !video || !target) return tfail(AVSE_ERR_INVALID, "NULL argument");
+    if (video_dtype != AVSE_VIDEO_F32 && video_dtype != AVSE_VIDEO_U8) return tfail(AVSE_ERR_INVALID, "unknown video dtype");
+    if (video_dtype == AVSE_VIDEO_U8 && ((uintptr_t)video & 3))
+        return tfail(AVSE_ERR_INVALID, "uint8 video must be 4-byte aligned (alignment of the base pointer)");
     if (N < 1 || N > t->max_n) return tfail(AVSE_ERR_INVALID, "batch size outside [1, max_batch]");
     if ((vnorm_mean == nullptr) != (vnorm_std == nullptr)) return tfail(AVSE_ERR_INVALID, "vnorm_mean / vnorm_std: both or neither");
     if (!(dropout_rate >= 0.f && dropout_rate < 1.f)) return tfail(AVSE_ERR_INVALID, "dropout_rate must be in [0, 1)");
     AVSE_HIP_CHECK(hipSetDevice(t->device));
-    return step_impl(t, audio, video, target, vnorm_mean, vnorm_std, N, lr, dropout_rate, dropout_seed, flags, loss,
+    return step_impl(t, audio, video, video_dtype, target, vnorm_mean, vnorm_std, N, lr, dropout_rate, dropout_seed, flags, loss,
                      (hipStream_t)stream);
 }
 

@@ -170,6 +170,11 @@ class VideoNormalizer(object):
     def __init__(self, video_samples):
         # video_samples: slices x height x width x frames_per_slice
         v = video_samples.cpu().numpy() if isinstance(video_samples, torch.Tensor) else video_samples
+        if v.dtype == np.uint8:
+            # uint8 crops: numpy's float64 moments, rounded once to the float32 images every consumer takes
+            self.__mean_image = np.mean(v, axis=(0, 3), dtype=np.float64).astype(np.float32)
+            self.__std_image = np.std(v, axis=(0, 3), dtype=np.float64).astype(np.float32)
+            return
         self.__mean_image = np.mean(v, axis=(0, 3))
         self.__std_image = np.std(v, axis=(0, 3))
 
@@ -193,7 +198,8 @@ class VideoNormalizer(object):
         """The fit of __init__ for a [S, H, W, F] float32 ROCm tensor, on the device: one streaming read
         (ops.video_stats, float64 sums per pixel) instead of a copy to the host and two numpy passes.  The images
         are np.mean / np.std over axes (0, 3) evaluated in float64 and rounded once to float32 — within a float32
-        ulp or two of __init__'s float32 numpy arithmetic, not its bits."""
+        ulp or two of __init__'s float32 numpy arithmetic, not its bits.  A uint8 tensor is summed in exact integers
+        (avse_video_stats_video)."""
         mean, std = ops.video_stats(video_tensor)
         return cls.from_stats(mean.cpu().numpy(), std.cpu().numpy())
 
@@ -211,13 +217,15 @@ class VideoNormalizer(object):
         return ops.to_device(self.__mean_image, device), ops.to_device(self.__std_image, device)
 
     def normalize(self, video_samples):
-        """In place, like data_processor.py:208-212."""
+        """In place, like data_processor.py:208-212.  float32 only: uint8 video cannot hold the result, it takes the
+        normaliser fused instead (pass this object to predict, or its device_stats() as vnorm_mean / vnorm_std)."""
         if isinstance(video_samples, torch.Tensor) and video_samples.is_cuda:
             m, s = self.device_stats(video_samples.device)
             ops.video_normalize_(video_samples, m, s)
             return
         if not (isinstance(video_samples, np.ndarray) and video_samples.dtype == np.float32):
-            raise TypeError("normalize expects a float32 numpy array or a ROCm tensor (it works in place)")
+            raise TypeError("normalize expects a float32 numpy array or a ROCm tensor (it works in place); uint8 video "
+                            "takes the normaliser fused, by passing it to predict")
         v = ops.to_device(video_samples)
         m, s = self.device_stats(v.device)
         ops.video_normalize_(v, m, s)

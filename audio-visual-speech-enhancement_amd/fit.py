@@ -62,24 +62,30 @@ def _device(x, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
-def validation_loss(model, mixed, video, speech, batch=256):
-    """Model.evaluate on the validation set: inference-mode MSE over every element (ops.forward, fp32)."""
+def validation_loss(model, mixed, video, speech, batch=256, vnorm_mean=None, vnorm_std=None):
+    """Model.evaluate on the validation set: inference-mode MSE over every element (ops.forward, fp32); vnorm_*: the
+    normaliser of a raw (e.g. uint8) video set, fused."""
     dw = ops.DeviceWeights(model, "float32", mixed.device)
     total, n = 0.0, mixed.shape[0]
     for a in range(0, n, batch):
         b = min(n, a + batch)
-        pred = ops.forward(dw, mixed[a:b], video[a:b])
+        pred = ops.forward(dw, mixed[a:b], video[a:b], vnorm_mean, vnorm_std)
         total += float(ops.mse(pred, speech[a:b]).item()) * (b - a)
     return total / max(n, 1)
 
 
 def fit(model, train, validation, model_cache_path=None, batch_size=16, epochs=1000, lr=5e-4, dropout=0.25,
-        seed=0, device=None, verbose=1, save=None):
+        seed=0, device=None, verbose=1, save=None, normalizer=None):
     """train / validation: (mixed [N, 80, 20], video [N, 128, 128, 5] (normalised), speech [N, 80, 20]).
+    normalizer (a VideoNormalizer, optional): the video sets are raw crops, float32 or uint8 (kept uint8 on the
+    device), and its images go to every Trainer.step and validation forward as vnorm_mean / vnorm_std.
     Returns (final KerasModel, history = [{'epoch', 'loss', 'val_loss', 'lr'}])."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    tm, tv, ts = (_device(x, dev) for x in train)
-    vm, vv, vs = (_device(x, dev) for x in validation)
+    tm, ts = (_device(x, dev) for x in (train[0], train[2]))
+    vm, vs = (_device(x, dev) for x in (validation[0], validation[2]))
+    # uint8 crops stay uint8 on the device (a quarter of the HBM), everything else becomes float32
+    tv, vv = ops.video_to_device(train[1], dev), ops.video_to_device(validation[1], dev)
+    nm, nsd = normalizer.device_stats(dev) if normalizer is not None else (None, None)
     n = tm.shape[0]
     trainer = ops.Trainer(model, max_batch=batch_size, device=dev)
     rng = np.random.default_rng(seed)
@@ -90,13 +96,13 @@ def fit(model, train, validation, model_cache_path=None, batch_size=16, epochs=1
         losses = []
         for a in range(0, n, batch_size):
             idx = perm[a:a + batch_size]
-            loss = trainer.step(tm.index_select(0, idx), tv.index_select(0, idx), ts.index_select(0, idx), lr=lr,
+            loss = trainer.step(tm.index_select(0, idx), tv.index_select(0, idx), ts.index_select(0, idx), nm, nsd, lr=lr,
                                 dropout=dropout, seed=(seed * 1000003 + step) & 0xFFFFFFFF)
             losses.append(loss * idx.numel())
             step += 1
         train_loss = float(torch.stack(losses).sum().item()) / n
         current = trainer.model()
-        val_loss = validation_loss(current, vm, vv, vs)
+        val_loss = validation_loss(current, vm, vv, vs, vnorm_mean=nm, vnorm_std=nsd)
         history.append({"epoch": epoch, "loss": train_loss, "val_loss": val_loss, "lr": lr})
         if verbose:
             print("epoch %d: loss %.6f - val_loss %.6f - lr %.3g" % (epoch + 1, train_loss, val_loss, lr))

@@ -45,17 +45,20 @@ class SpeechEnhancementNetwork(object):
 
     def train(self, train_mixed_spectrograms, train_video_samples, train_speech_spectrograms,
               validation_mixed_spectrograms, validation_video_samples, validation_speech_spectrograms,
-              model_cache_path, tensorboard_dir=None, batch_size=16, epochs=1000, lr=5e-4, seed=0, verbose=1):
+              model_cache_path, tensorboard_dir=None, batch_size=16, epochs=1000, lr=5e-4, seed=0, verbose=1,
+              video_normalizer=None):
         """network.py:177-206: Model.fit(batch_size=16, epochs=1000) with ModelCheckpoint(model_cache_path),
         ReduceLROnPlateau(val_loss, 0.5, patience 5), EarlyStopping(val_loss, min_delta 0.01, patience 10) on the
         Adam(5e-4) / MSE compilation of network.py:35-36.  Video samples are expected normalised (as the
         reference's speech_enhancer.train does in place).  tensorboard_dir is accepted and unused (no
-        TensorFlow).  The trained parameters replace this network's; returns the per-epoch history."""
+        TensorFlow).  video_normalizer (optional): the video samples are raw crops — uint8 sets, which cannot be
+        normalised in place — and every training step and validation forward applies this normaliser fused.
+        The trained parameters replace this network's; returns the per-epoch history."""
         from .fit import fit
         model, history = fit(self.__model, (train_mixed_spectrograms, train_video_samples, train_speech_spectrograms),
                              (validation_mixed_spectrograms, validation_video_samples, validation_speech_spectrograms),
                              model_cache_path=model_cache_path, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed,
-                             device=self.__device, verbose=verbose)
+                             device=self.__device, verbose=verbose, normalizer=video_normalizer)
         self.__model = model
         self.__dw = None
         return history
@@ -64,7 +67,7 @@ class SpeechEnhancementNetwork(object):
         """Device-tensor forward: [N, 80, T] x [N, 128, 128, F] -> [N, 80, T] (no squeeze).  checked (default: on for
         float32_split weights, whose range guard is then read before returning) as in ops.forward."""
         a = ops.to_device(mixed_spectrograms, self.__device)
-        v = None if video_samples is None else ops.to_device(video_samples, a.device)   # None: all-zero video
+        v = None if video_samples is None else ops.video_to_device(video_samples, a.device)   # None: all-zero video
         m = s = None
         if video_normalizer is not None:
             m, s = video_normalizer.device_stats(a.device)

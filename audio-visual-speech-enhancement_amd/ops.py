@@ -28,6 +28,38 @@ def _dev_f32(t, name, shape=None):
     return t
 
 
+def _dev_video(t, name, shape=None):
+    """A video argument: a float32 or uint8 device tensor, checked like _dev_f32 -> its avse_video_dtype.  uint8 crops
+    (include/avse.h AVSE_VIDEO_U8) are converted in the kernels, exactly, so they give the float32 call's bits."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8):
+        _dev_f32(t, name, shape)
+        return _lib.AVSE_VIDEO_F32
+    if not t.is_cuda:
+        raise TypeError(f"{name} must be a ROCm device tensor")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if shape is not None and tuple(t.shape[-len(shape):]) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [..., {shape}]")
+    return _lib.AVSE_VIDEO_U8
+
+
+def _check_video(rc, what, video):
+    """_lib.check for the avse_*_video calls: the library's refusal of a uint8 video that is not 4-byte aligned (the
+    one argument error the checks above leave to it) is the caller's ValueError, like the other shape errors."""
+    if rc == 1 and video is not None and video.dtype == torch.uint8 and video.data_ptr() % 4:
+        raise ValueError(f"{what}: {_lib.load().avse_last_error().decode(errors='replace')}")
+    _lib.check(rc, what)
+
+
+def video_to_device(x, device=None):
+    """to_device for video: uint8 crops (numpy or tensor) stay uint8, everything else becomes float32."""
+    if (x.dtype == torch.uint8) if isinstance(x, torch.Tensor) else (np.asarray(x).dtype == np.uint8):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        return t.to(dev).contiguous()
+    return to_device(x, device)
+
+
 def n_frames(n_samples, hop, n_fft):
     """Centred STFT frame count (librosa.stft, center=True): 1 + (L + 2*(n_fft//2) - n_fft) // hop."""
     return 1 + (n_samples + 2 * (n_fft // 2) - n_fft) // hop
@@ -175,8 +207,9 @@ class DeviceWeights:
 def _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std):
     _dev_f32(audio, "audio", (80, weights.T))
     N = audio.shape[0]
+    vdt = _lib.AVSE_VIDEO_F32      # video=None: either dtype
     if video is not None:
-        _dev_f32(video, "video", (128, 128, weights.F))
+        vdt = _dev_video(video, "video", (128, 128, weights.F))
         if video.shape[0] != N:
             raise ValueError("audio and video batch sizes differ")
     if (vnorm_mean is None) != (vnorm_std is None):
@@ -190,12 +223,13 @@ def _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std):
     if len(devs) != 1:
         raise ValueError(f"weights live on cuda:{weights.ctx.device_index} but audio / video are on "
                          f"{audio.device} / {None if video is None else video.device}")
-    return N
+    return N, vdt
 
 
 def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, checked=False, on_range="recompute"):
     """K2-K5: network forward.  audio [N, 80, 20], video [N, 128, 128, 5] float32 device tensors
-    (video un-normalised when vnorm_* are given).  Returns [N, 80, 20] float32.  ([N, 80, T] / [N, 128, 128, F]
+    (video un-normalised when vnorm_* are given; video may also be the crops' uint8 values, 4-byte aligned: the
+    result is the float32 call's, bit for bit).  Returns [N, 80, 20] float32.  ([N, 80, T] / [N, 128, 128, F]
     for weights of another network shape, e.g. T = 24 at 29.97 fps.)
 
     video=None means an all-zero video input (BASELINE configs[2], the audio branch alone): the video
@@ -208,7 +242,7 @@ def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, ch
     _lib.RangeError (on_range="error"); not allowed while the stream is capturing.  weights.last_range_bits holds the
     guard bits of the last checked call (0: every pair in range).  The synchronous reference-shaped API
     (network.SpeechEnhancementNetwork.predict / evaluate, the CLI predict) opts in for float32_split weights."""
-    N = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std)
+    N, vdt = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std)
     if out is None:
         out = torch.empty((N, 80, weights.T), dtype=torch.float32, device=audio.device)
     _dev_f32(out, "out", (80, weights.T))
@@ -220,19 +254,19 @@ def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, ch
         if checked:
             mode = {"recompute": _lib.AVSE_RANGE_RECOMPUTE, "error": _lib.AVSE_RANGE_ERROR}[on_range]
             bits = ctypes.c_uint32()
-            rc = _lib.load().avse_forward_checked(weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video),
-                                                  _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), N, _lib.ptr(out),
-                                                  _lib.stream_handle(audio.device), mode, ctypes.byref(bits))
+            rc = _lib.load().avse_forward_checked_video(
+                weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+                _lib.ptr(vnorm_std), N, _lib.ptr(out), _lib.stream_handle(audio.device), mode, ctypes.byref(bits))
             weights.last_range_bits = bits.value
-            _lib.check(rc, "avse_forward_checked")
+            _check_video(rc, "avse_forward_checked", video)
             if bits.value:
                 import warnings
                 warnings.warn(f"float32_split forward of {N} clips: {_lib.range_bit_names(bits.value)} left the f16 pair "
                               "range; the batch was recomputed on the exact-fp32 kernels", RuntimeWarning, stacklevel=2)
         else:
-            _lib.check(_lib.load().avse_forward(weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video),
-                                                _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), N, _lib.ptr(out),
-                                                _lib.stream_handle(audio.device)), "avse_forward")
+            _check_video(_lib.load().avse_forward_video(
+                weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+                _lib.ptr(vnorm_std), N, _lib.ptr(out), _lib.stream_handle(audio.device)), "avse_forward", video)
     return out
 
 
@@ -286,19 +320,22 @@ class RangePipeline:
 
 def forward_profile(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None):
     """forward() with HIP events between kernel launches (synchronises); returns (out, {stage: ms})."""
-    N = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std)
+    N, vdt = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std)
     if out is None:
         out = torch.empty((N, 80, weights.T), dtype=torch.float32, device=audio.device)
     ms = (ctypes.c_float * _lib.AVSE_NUM_STAGES)()
     with torch.cuda.device(audio.device):
-        _lib.check(_lib.load().avse_forward_profile(weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video),
-                                                    _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), N, _lib.ptr(out),
-                                                    _lib.stream_handle(audio.device), ms), "avse_forward_profile")
+        _check_video(_lib.load().avse_forward_profile_video(
+            weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+            _lib.ptr(vnorm_std), N, _lib.ptr(out), _lib.stream_handle(audio.device), ms), "avse_forward_profile", video)
     return out, dict(zip(_lib.STAGE_NAMES, [float(x) for x in ms]))
 
 
 def video_normalize_(video, mean, std):
     """In place: video[s, :, :, f] = (video[s, :, :, f] - mean) / std (data_processor.py:208-212)."""
+    if isinstance(video, torch.Tensor) and video.dtype == torch.uint8:
+        raise TypeError("video must be float32, got torch.uint8: uint8 video cannot be normalised in place; it takes "
+                        "the normaliser fused, by passing it to predict (ops.forward's vnorm_mean / vnorm_std)")
     _dev_f32(video, "video")
     _dev_f32(mean, "mean")
     _dev_f32(std, "std")
@@ -316,8 +353,9 @@ def video_normalize_(video, mean, std):
 def video_stats(video):
     """VideoNormalizer's fit (data_processor.py:203-206) on the device: video [S, H, W, F] float32 device tensor ->
     (mean [H, W], std [H, W]) float32 device tensors, np.mean / np.std over axes (0, 3) from one streaming read
-    (float64 sums about each pixel's first value, include/avse.h avse_video_stats)."""
-    _dev_f32(video, "video")
+    (float64 sums about each pixel's first value, include/avse.h avse_video_stats).  uint8 video (4-byte aligned):
+    exact integer sums (avse_video_stats_video)."""
+    vdt = _dev_video(video, "video")
     if video.dim() != 4:
         raise ValueError("video must be [slices, height, width, frames_per_slice]")
     S, H, W, F = video.shape
@@ -327,8 +365,9 @@ def video_stats(video):
     std = torch.empty((H, W), dtype=torch.float32, device=video.device)
     ctx = _lib.context(video.device)
     with torch.cuda.device(video.device):
-        _lib.check(_lib.load().avse_video_stats(ctx.handle, _lib.ptr(video), S, H, W, F, _lib.ptr(mean), _lib.ptr(std),
-                                                _lib.stream_handle(video.device)), "avse_video_stats")
+        _check_video(_lib.load().avse_video_stats_video(ctx.handle, _lib.ptr(video), vdt, S, H, W, F, _lib.ptr(mean),
+                                                        _lib.ptr(std), _lib.stream_handle(video.device)),
+                     "avse_video_stats", video)
     return mean, std
 
 
@@ -477,10 +516,11 @@ class Trainer:
     def step(self, audio, video, target, vnorm_mean=None, vnorm_std=None, lr=5e-4, dropout=0.25, seed=0,
              grads_only=False):
         """One fit step on a batch: audio / target [N, 80, 20], video [N, 128, 128, 5] (raw crops when vnorm_* are
-        given) float32 device tensors.  Returns the batch MSE before the update as a 0-dim device tensor."""
+        given) float32 device tensors; video may also be uint8 crops (4-byte aligned, with vnorm_* for a normalised
+        fit).  Returns the batch MSE before the update as a 0-dim device tensor."""
         _dev_f32(audio, "audio", (80, self.T))
         _dev_f32(target, "target", (80, self.T))
-        _dev_f32(video, "video", (128, 128, self.F))
+        vdt = _dev_video(video, "video", (128, 128, self.F))
         N = audio.shape[0]
         if video.shape[0] != N or target.shape[0] != N:
             raise ValueError("audio, video and target batch sizes differ")
@@ -492,11 +532,11 @@ class Trainer:
         if len(devs) != 1:
             raise ValueError("trainer and batch tensors must share one device")
         with torch.cuda.device(audio.device):
-            _lib.check(_lib.load().avse_trainer_step(
-                self.handle, _lib.ptr(audio), _lib.ptr(video), _lib.ptr(target), _lib.ptr(vnorm_mean),
+            _check_video(_lib.load().avse_trainer_step_video(
+                self.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(target), _lib.ptr(vnorm_mean),
                 _lib.ptr(vnorm_std), N, float(lr), float(dropout), int(seed) & 0xFFFFFFFF,
                 _lib.AVSE_TRAIN_GRADS_ONLY if grads_only else 0, _lib.ptr(self._loss),
-                _lib.stream_handle(audio.device)), "avse_trainer_step")
+                _lib.stream_handle(audio.device)), "avse_trainer_step", video)
         return self._loss.clone()
 
     def _read(self, what):

@@ -36,7 +36,7 @@ class Enhancer:
 
     def __call__(self, signals, video, vmean=None, vstd=None, timings=None):
         """signals [U, L] float32 (int16-scale samples, padded / truncated to S slices like
-        preprocess_audio_signal), video [U, S, 128, 128, frames] float32 raw mouth crops; vmean / vstd the
+        preprocess_audio_signal), video [U, S, 128, 128, frames] float32 or uint8 raw mouth crops; vmean / vstd the
         VideoNormalizer images.  Returns [U, hop * (S * spf - 1)] float32 enhanced speech.
         `timings`, when a dict, receives the stages' HIP-event milliseconds (adds synchronisation)."""
         if signals.dim() != 2 or video.dim() != 5 or video.shape[0] != signals.shape[0]:

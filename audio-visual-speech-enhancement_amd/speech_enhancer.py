@@ -19,6 +19,10 @@ Differences (host plumbing outside the hot path):
   * preprocess `--batch N` mixes and transforms the audio of up to N pairs per device call
     (data_processor.preprocess_audio_pairs; the cache it writes equals the default per-sample loop's), and train
     `--device-normalizer` fits the video normaliser with one streaming read on the device (VideoNormalizer.fit_device);
+  * preprocess `--video-u8` keeps the mouth crops as the 8-bit values they are (uint8 in the Sample and the .npz cache,
+    a quarter of the float32 bytes); train and predict take such a cache as it is: the kernels convert on load, predict
+    fuses the normaliser as always, and train passes it to every step instead of normalising the set in place.  The
+    results equal those of the float32 cache of the same crops.  Default: float32 crops and caches;
   * predict runs ONE forward per sample: the printed loss (speech_enhancer.py:76-77, an MSE over the
     sample like Model.evaluate) is computed from the same prediction that is reconstructed (the reference
     runs evaluate and predict, two forwards of the same input);
@@ -51,9 +55,28 @@ Sample = namedtuple("Sample", ["speaker_id", "video_file_path", "speech_file_pat
 
 
 # ------------------------------------------------------------------------ preprocessing (host side)
-def preprocess_video_sample(video_file_path, slice_duration_ms, mouth_height=128, mouth_width=128):
-    """Stand-in for data_processor.py:12-32 on pre-cropped mouth stacks -> ([S, H, W, frames], fps)."""
-    frames = np.load(video_file_path, allow_pickle=False).astype(np.float32)       # [F, H, W]
+def crops_as_uint8(frames, what="video"):
+    """--video-u8: the crop stack as uint8 without changing a value.  An integer array is taken as it is when its
+    values lie in 0..255, a float array only when every value is an integer in 0..255; anything else is a ValueError
+    (the caller's catch-and-skip then drops the sample)."""
+    frames = np.asarray(frames)
+    if frames.dtype == np.uint8:
+        return frames
+    if not (np.issubdtype(frames.dtype, np.integer) or np.issubdtype(frames.dtype, np.floating)):
+        raise ValueError(f"{what}: --video-u8 takes integer or float crops, got {frames.dtype}")
+    if frames.size and not (frames.min() >= 0 and frames.max() <= 255):     # False for NaN too
+        raise ValueError(f"{what}: --video-u8 takes values in 0..255")
+    out = frames.astype(np.uint8)
+    if not np.array_equal(out, frames):
+        raise ValueError(f"{what}: --video-u8 takes whole-number values, found fractions")
+    return out
+
+
+def preprocess_video_sample(video_file_path, slice_duration_ms, mouth_height=128, mouth_width=128, video_u8=False):
+    """Stand-in for data_processor.py:12-32 on pre-cropped mouth stacks -> ([S, H, W, frames], fps).  video_u8: the
+    crops stay uint8 (crops_as_uint8), else they become float32 as in the reference."""
+    frames = np.load(video_file_path, allow_pickle=False)       # [F, H, W]
+    frames = crops_as_uint8(frames, video_file_path) if video_u8 else frames.astype(np.float32)
     if frames.shape[1:] != (mouth_height, mouth_width):
         raise ValueError(f"{video_file_path}: expected [F, {mouth_height}, {mouth_width}] mouth crops")
     fps_path = os.path.splitext(video_file_path)[0] + ".fps"
@@ -86,9 +109,9 @@ def preprocess_audio_pair(speech_file_path, noise_file_path, slice_duration_ms, 
     return stacks[0], stacks[1], stacks[2], mixture
 
 
-def preprocess_sample(speech_entry, noise_file_path, slice_duration_ms=200):
+def preprocess_sample(speech_entry, noise_file_path, slice_duration_ms=200, video_u8=False):
     """data_processor.py:156-177."""
-    video_samples, fps = preprocess_video_sample(speech_entry.video_path, slice_duration_ms)
+    video_samples, fps = preprocess_video_sample(speech_entry.video_path, slice_duration_ms, **_u8_kw(video_u8))
     mixed, speech, noise, mixed_signal = preprocess_audio_pair(speech_entry.audio_path, noise_file_path,
                                                                slice_duration_ms, video_samples.shape[0], fps)
     n = min(video_samples.shape[0], mixed.shape[0])
@@ -96,7 +119,12 @@ def preprocess_sample(speech_entry, noise_file_path, slice_duration_ms=200):
                   video_samples[:n], mixed[:n], speech[:n], noise[:n], mixed_signal, fps)
 
 
-def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200):
+def _u8_kw(video_u8):
+    """The video_u8 keyword, passed on only when set: a default run calls its helpers exactly as before."""
+    return {"video_u8": True} if video_u8 else {}
+
+
+def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200, video_u8=False):
     """preprocess_sample for a group of entries with the audio of all pairs in one
     data_processor.preprocess_audio_pairs call (device-side mixing, one STFT launch per geometry).  Catch-and-skip as
     preprocess_data: an entry whose files do not load is skipped; when the batched call fails (a multi-channel or
@@ -104,7 +132,7 @@ def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200):
     loaded = []
     for entry, noise in zip(speech_entries, noise_file_paths):
         try:
-            video_samples, fps = preprocess_video_sample(entry.video_path, slice_duration_ms)
+            video_samples, fps = preprocess_video_sample(entry.video_path, slice_duration_ms, **_u8_kw(video_u8))
             loaded.append((entry, noise, video_samples, fps, AudioSignal.from_wav_file(entry.audio_path),
                            AudioSignal.from_wav_file(noise)))
         except Exception as e:  # noqa: BLE001 — mirrors try_preprocess_sample
@@ -120,7 +148,7 @@ def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200):
     for k, (entry, noise, video_samples, fps, _, _) in enumerate(loaded):
         if audio is None:
             try:
-                samples.append(preprocess_sample(entry, noise, slice_duration_ms))
+                samples.append(preprocess_sample(entry, noise, slice_duration_ms, **_u8_kw(video_u8)))
             except Exception as e:  # noqa: BLE001
                 print("failed to preprocess %s (%s)" % ((entry, noise), e))
             continue
@@ -131,17 +159,19 @@ def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200):
     return samples
 
 
-def preprocess_data(speech_entries, noise_file_paths, batch=0):
+def preprocess_data(speech_entries, noise_file_paths, batch=0, video_u8=False):
     """data_processor.py:180-198 (catch-and-skip per sample; the GPU does the spectrograms, so no Pool).
-    batch > 0: groups of up to `batch` consecutive pairs through preprocess_batch (same samples, same order)."""
+    batch > 0: groups of up to `batch` consecutive pairs through preprocess_batch (same samples, same order).
+    video_u8: the samples' video stays uint8 (--video-u8)."""
     samples = []
     if batch > 0:
         for a in range(0, len(speech_entries), batch):
-            samples.extend(preprocess_batch(speech_entries[a:a + batch], noise_file_paths[a:a + batch]))
+            samples.extend(preprocess_batch(speech_entries[a:a + batch], noise_file_paths[a:a + batch],
+                                            **_u8_kw(video_u8)))
         return samples
     for entry, noise in zip(speech_entries, noise_file_paths):
         try:
-            samples.append(preprocess_sample(entry, noise))
+            samples.append(preprocess_sample(entry, noise, **_u8_kw(video_u8)))
         except Exception as e:  # noqa: BLE001 — mirrors try_preprocess_sample
             print("failed to preprocess %s (%s)" % ((entry, noise), e))
     return samples
@@ -205,20 +235,21 @@ def preprocess(args):
     layout = Layout(args.base_dir)
     speech_entries, noise_file_paths = pair_speech_with_noise(args.dataset_dir, selected_speakers(args),
                                                               args.noise_dirs, limit=1000, shuffle=True)
-    samples = preprocess_data(speech_entries, noise_file_paths, batch=args.batch)
+    samples = preprocess_data(speech_entries, noise_file_paths, batch=args.batch, **_u8_kw(args.video_u8))
     save_preprocessed_blob(layout.preprocessed(args.data_name), samples)
     print("preprocessed %d samples" % len(samples))
 
 
 def train(args):
     """speech_enhancer.py:31-58: sample sets, VideoNormalizer fitted on the training video and applied in place to
-    both sets, the normaliser saved, network built, fit with the model checkpointed every epoch, saved."""
+    both sets, the normaliser saved, network built, fit with the model checkpointed every epoch, saved.  A uint8 set
+    (preprocess --video-u8) cannot be normalised in place: the fit applies the normaliser in every step instead."""
     layout = Layout(args.base_dir)
     samples = load_preprocessed_blobs([layout.preprocessed(d) for d in args.train_data_names])
     video, mixed, speech = make_sample_set(samples)
     if args.device_normalizer:
         from . import ops
-        normalizer = data_processor.VideoNormalizer.fit_device(ops.to_device(video))   # one upload, one streaming read
+        normalizer = data_processor.VideoNormalizer.fit_device(ops.video_to_device(video))   # one upload, one streaming read
     else:
         normalizer = data_processor.VideoNormalizer(video)
     normalizer.save(layout.normalizer_file(args.model))
@@ -226,10 +257,14 @@ def train(args):
     if not args.init_only:
         vsamples = load_preprocessed_blobs([layout.preprocessed(d) for d in args.validation_data_names])
         vvideo, vmixed, vspeech = make_sample_set(vsamples)
-        normalizer.normalize(video)
-        normalizer.normalize(vvideo)
-        network.train(mixed, video, speech, vmixed, vvideo, vspeech, layout.model_file(args.model),
-                      epochs=args.epochs, seed=args.seed)
+        if video.dtype == np.uint8 or vvideo.dtype == np.uint8:
+            network.train(mixed, video, speech, vmixed, vvideo, vspeech, layout.model_file(args.model),
+                          epochs=args.epochs, seed=args.seed, video_normalizer=normalizer)
+        else:
+            normalizer.normalize(video)
+            normalizer.normalize(vvideo)
+            network.train(mixed, video, speech, vmixed, vvideo, vspeech, layout.model_file(args.model),
+                          epochs=args.epochs, seed=args.seed)
     network.save(layout.model_file(args.model))
 
 
@@ -270,7 +305,8 @@ class BatchPredictor:
         U = len(group)
         S, nm, T = group[0].mixed_spectrograms.shape
         mixed = torch.from_numpy(np.stack([g.mixed_spectrograms for g in group]).astype(np.float32)).to(dev)
-        video = torch.from_numpy(np.stack([g.video_samples for g in group]).astype(np.float32)).to(dev)
+        video = np.stack([g.video_samples for g in group])      # uint8 crops (--video-u8) go up as they are
+        video = torch.from_numpy(video if video.dtype == np.uint8 else video.astype(np.float32)).to(dev)
         speech = torch.from_numpy(np.stack([g.speech_spectrograms for g in group]).astype(np.float32)).to(dev)
         m = s = None
         if self.video_normalizer is not None:
@@ -409,6 +445,8 @@ def main(argv=None):
     p.add_argument("-is", "--ignored_speakers", nargs="+", type=str)
     p.add_argument("--batch", type=int, default=0,
                    help="preprocess the audio of up to N pairs per device call (0: one pair at a time)")
+    p.add_argument("--video-u8", action="store_true",
+                   help="keep the mouth crops as uint8 in the cache (a quarter of the bytes; same results)")
     p.set_defaults(func=preprocess)
 
     t = sub.add_parser("train")

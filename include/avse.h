@@ -65,6 +65,12 @@ enum avse_status {
  *                   AVSE_ERR_RANGE); after plain avse_forward calls avse_range_status tells whether any did. */
 enum avse_dtype { AVSE_F32 = 0, AVSE_BF16 = 1, AVSE_F32_SPLIT = 2 };
 enum avse_pad_mode { AVSE_PAD_REFLECT = 0, AVSE_PAD_CONSTANT = 1 };
+/* Element type of a video argument of the avse_*_video entry points: float32, or the mouth crops' own 8-bit grayscale
+ * values [N][128][128][F] uint8 (a quarter of the bytes to store and upload).  float(uint8) is exact and every kernel
+ * converts on load, so a uint8 call returns the bits of the float32 call on the same pixel values.  A uint8 video
+ * pointer must be 4-byte aligned (the loaders read whole dwords; every clip of H W F bytes is then aligned too):
+ * AVSE_ERR_INVALID otherwise. */
+enum avse_video_dtype { AVSE_VIDEO_F32 = 0, AVSE_VIDEO_U8 = 1 };
 
 typedef struct avse_ctx avse_ctx;
 typedef struct avse_weights avse_weights;
@@ -205,6 +211,11 @@ int avse_forward(avse_ctx* ctx, const avse_weights* w, const float* audio, const
                  const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
                  void* stream);
 
+/* avse_forward (replaces the same reference calls) with the video in video_dtype (avse_video_dtype): video
+ * [N][128][128][F] float32 or uint8, NULL as avse_forward for either dtype.  AVSE_VIDEO_F32 is avse_forward itself. */
+int avse_forward_video(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video, int video_dtype,
+                       const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out, void* stream);
+
 /* avse_forward for AVSE_F32_SPLIT weights with the range guard read back: waits for `stream` after the forward (not
  * capturable) and, when a stored activation or a split input left the f16 pair range (|x| >= 65520 or NaN; bit i of
  * *host_bits = plan layer i, a_conv1 = 0 .. d_deconv5 = 18; bit 24 the audio input, bit 25 the video input):
@@ -217,6 +228,13 @@ enum avse_range_mode { AVSE_RANGE_RECOMPUTE = 0, AVSE_RANGE_ERROR = 1 };
 int avse_forward_checked(avse_ctx* ctx, const avse_weights* w, const float* audio, const float* video,
                          const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out, void* stream,
                          int mode, uint32_t* host_bits);
+
+/* avse_forward_checked (the checked form of the reference's Model.predict, network.py:208-212) with the video in
+ * video_dtype; the exact-fp32 recompute reads the same uint8 input, and bit 25 reports what the float32 call reports
+ * for the same pixel values. */
+int avse_forward_checked_video(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video,
+                               int video_dtype, const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
+                               void* stream, int mode, uint32_t* host_bits);
 
 /* Range-guard bits (as avse_forward_checked's) raised by the AVSE_F32_SPLIT forwards of plain avse_forward /
  * avse_forward_profile calls on this context since the last avse_range_status; waits for `stream` (the stream those
@@ -250,7 +268,14 @@ int avse_forward_profile(avse_ctx* ctx, const avse_weights* w, const float* audi
                          const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
                          void* stream, float* host_ms);
 
-/* VideoNormalizer.normalize (data_processor.py:208-212), in place on device:
+/* avse_forward_profile (the reference's Model.predict, network.py:208-212, timed per stage) with the video in
+ * video_dtype. */
+int avse_forward_profile_video(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video,
+                               int video_dtype, const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
+                               void* stream, float* host_ms);
+
+/* VideoNormalizer.normalize (data_processor.py:208-212), in place on device (float32 only: uint8 video takes the
+ * normaliser fused into the forward, vnorm_mean / vnorm_std):
  *   video[s, :, :, f] = (video[s, :, :, f] - mean) / std   for video [S][H][W][F]. */
 int avse_video_normalize(avse_ctx* ctx, float* video, int64_t S, int H, int W, int F,
                          const float* mean, const float* std, void* stream);
@@ -290,6 +315,14 @@ int avse_mix_pairs(avse_ctx* ctx, const int16_t* speech, const int64_t* speech_o
  * once to float32 (within 1 float32 ulp of numpy's float64 result rounded to float32).  Scratch as avse_mix_pairs. */
 int avse_video_stats(avse_ctx* ctx, const float* video, int64_t S, int H, int W, int F, float* mean, float* std,
                      void* stream);
+
+/* avse_video_stats (replaces VideoNormalizer.__init__, data_processor.py:203-206) with the video in video_dtype.
+ * AVSE_VIDEO_U8: per pixel the sums of the bytes and of their squares in 64-bit integers (exact for any S), per chunk
+ * of slices, combined in chunk order; mean = Sx / n and std = sqrt((n Sx2 - Sx^2) / n^2), the numerator exact in 128
+ * bits, each rounded once to float64 and once to float32 (within 1 float32 ulp of numpy's float64 result rounded to
+ * float32); two calls agree bit for bit. */
+int avse_video_stats_video(avse_ctx* ctx, const void* video, int video_dtype, int64_t S, int H, int W, int F,
+                           float* mean, float* std, void* stream);
 
 /* SpeechEnhancementNetwork.evaluate's loss (network.py:214-220, Keras mean_squared_error over
  * every element): *loss = mean((pred - target)^2) over n values; loss is a device float. */
@@ -339,6 +372,13 @@ void avse_trainer_destroy(avse_trainer* t);
 int avse_trainer_step(avse_trainer* t, const float* audio, const float* video, const float* target,
                       const float* vnorm_mean, const float* vnorm_std, int64_t N, float lr, float dropout_rate,
                       uint32_t dropout_seed, int flags, float* loss, void* stream);
+
+/* avse_trainer_step (one Model.fit step of network.py:177-206, with the VideoNormalizer.normalize of
+ * speech_enhancer.py:52-53 fused) with the video in video_dtype: a uint8 set is trained on with vnorm_* given, since it
+ * cannot be normalised in place. */
+int avse_trainer_step_video(avse_trainer* t, const float* audio, const void* video, int video_dtype,
+                            const float* target, const float* vnorm_mean, const float* vnorm_std, int64_t N, float lr,
+                            float dropout_rate, uint32_t dropout_seed, int flags, float* loss, void* stream);
 
 /* Copy one of the trainer's blobs (avse_train_buffer) to the host; synchronises the device.  n_floats is the blob
  * size, except for AVSE_TRAIN_DEBUG_DZ (any count up to the size of the dz scratch). */
