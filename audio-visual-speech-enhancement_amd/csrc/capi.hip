@@ -432,8 +432,14 @@ int ensure_spec_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, 
     return 0;
 }
 
-// pinv(mel) = M^T (M M^T)^{-1} in double (M is full row rank, cond ~4.5 for the reference's
-// filterbanks; equal to np.linalg.pinv's SVD form to ~1e-13), plus the inverse-DFT tables.
+// pinv(mel) as np.linalg.pinv computes it (data_processor.py:112): from the singular value decomposition, dropping
+// the singular values at or below 1e-15 of the largest.  The reference's own banks are full row rank (cond ~4.5), for
+// which this is M^T (M M^T)^{-1}; a bank with more bands than the bins can tell apart is not (n_fft 401 with 80 bands:
+// an FFT bin lands on a band edge and leaves singular values of 3e-6 and 2e-20 of the largest), and there the
+// Gram-matrix inverse this replaced followed the dropped direction (waveform 7e-4 from the oracle's).
+// One-sided Jacobi (Hestenes) on the rows of M, in double: plane rotations J make the rows of A = J M mutually
+// orthogonal, so sigma_i = |a_i|, M = J^T diag(sigma) (a_i / sigma_i) and pinv(M)[k][m] = sum_i a_i[k] J[i][m] /
+// sigma_i^2 over the kept i.  Small singular values come out to high relative accuracy.  Also the inverse-DFT tables.
 int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, double fmax) {
     IstftTables& t = c->istft;
     if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
@@ -442,44 +448,58 @@ int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin,
     t = IstftTables();
     const int nb = 1 + n_fft / 2, N = 2 * (nb - 1);
     const std::vector<double> M = mel_filterbank(sr, n_fft, n_mels, fmin, fmax);
-    // G = M M^T, then Gauss-Jordan inverse with partial pivoting
-    std::vector<double> G((size_t)n_mels * n_mels), Gi((size_t)n_mels * n_mels, 0.0);
-    for (int i = 0; i < n_mels; ++i)
-        for (int j = 0; j < n_mels; ++j) {
-            double s = 0;
-            for (int k = 0; k < nb; ++k) s += M[(size_t)i * nb + k] * M[(size_t)j * nb + k];
-            G[(size_t)i * n_mels + j] = s;
-        }
-    for (int i = 0; i < n_mels; ++i) Gi[(size_t)i * n_mels + i] = 1.0;
-    for (int col = 0; col < n_mels; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < n_mels; ++r)
-            if (std::fabs(G[(size_t)r * n_mels + col]) > std::fabs(G[(size_t)piv * n_mels + col])) piv = r;
-        if (std::fabs(G[(size_t)piv * n_mels + col]) < 1e-300) return fail(AVSE_ERR_UNSUPPORTED, "mel filterbank is rank deficient");
-        if (piv != col)
-            for (int j = 0; j < n_mels; ++j) {
-                std::swap(G[(size_t)piv * n_mels + j], G[(size_t)col * n_mels + j]);
-                std::swap(Gi[(size_t)piv * n_mels + j], Gi[(size_t)col * n_mels + j]);
+    std::vector<double> A(M), J((size_t)n_mels * n_mels, 0.0);
+    for (int i = 0; i < n_mels; ++i) J[(size_t)i * n_mels + i] = 1.0;
+    // 5-8 sweeps for a full-rank bank; the rounding noise of a zero direction keeps rotating until the cap
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < n_mels - 1; ++p)
+            for (int q = p + 1; q < n_mels; ++q) {
+                double* ap = &A[(size_t)p * nb];
+                double* aq = &A[(size_t)q * nb];
+                double alpha = 0, beta = 0, gamma = 0;
+                for (int k = 0; k < nb; ++k) {
+                    alpha += ap[k] * ap[k];
+                    beta += aq[k] * aq[k];
+                    gamma += ap[k] * aq[k];
+                }
+                if (std::fabs(gamma) <= 1e-15 * std::sqrt(alpha * beta)) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double az = std::fabs(zeta);   // (zeta^2 overflows past 1e154: tan = 1 / (2 zeta) there)
+                const double tn = az > 1e100 ? 0.5 / zeta : (zeta >= 0 ? 1.0 : -1.0) / (az + std::sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / std::sqrt(1.0 + tn * tn), sn = cs * tn;
+                for (int k = 0; k < nb; ++k) {
+                    const double x = ap[k], y = aq[k];
+                    ap[k] = cs * x - sn * y;
+                    aq[k] = sn * x + cs * y;
+                }
+                double* jp = &J[(size_t)p * n_mels];
+                double* jq = &J[(size_t)q * n_mels];
+                for (int m = 0; m < n_mels; ++m) {
+                    const double x = jp[m], y = jq[m];
+                    jp[m] = cs * x - sn * y;
+                    jq[m] = sn * x + cs * y;
+                }
             }
-        const double d = G[(size_t)col * n_mels + col];
-        for (int j = 0; j < n_mels; ++j) { G[(size_t)col * n_mels + j] /= d; Gi[(size_t)col * n_mels + j] /= d; }
-        for (int r = 0; r < n_mels; ++r) {
-            if (r == col) continue;
-            const double f = G[(size_t)r * n_mels + col];
-            if (f == 0) continue;
-            for (int j = 0; j < n_mels; ++j) {
-                G[(size_t)r * n_mels + j] -= f * G[(size_t)col * n_mels + j];
-                Gi[(size_t)r * n_mels + j] -= f * Gi[(size_t)col * n_mels + j];
-            }
-        }
+        if (!rotated) break;
     }
-    // pinv[k][m] = sum_j M[j][k] Gi[j][m]; stored transposed [m][k]
+    std::vector<double> sig2(n_mels);
+    double smax2 = 0;
+    for (int i = 0; i < n_mels; ++i) {
+        double a2 = 0;
+        for (int k = 0; k < nb; ++k) a2 += A[(size_t)i * nb + k] * A[(size_t)i * nb + k];
+        sig2[i] = a2;
+        smax2 = std::max(smax2, a2);
+    }
+    // pinv[k][m] = sum_i a_i[k] J[i][m] / sigma_i^2 over sigma_i > 1e-15 sigma_max; stored transposed [m][k]
     std::vector<float> pinvT((size_t)n_mels * nb);
     for (int m = 0; m < n_mels; ++m)
         for (int k = 0; k < nb; ++k) {
-            double s = 0;
-            for (int j = 0; j < n_mels; ++j) s += M[(size_t)j * nb + k] * Gi[(size_t)j * n_mels + m];
-            pinvT[(size_t)m * nb + k] = (float)s;
+            double sum = 0;
+            for (int i = 0; i < n_mels; ++i)
+                if (sig2[i] > 1e-30 * smax2) sum += A[(size_t)i * nb + k] * J[(size_t)i * n_mels + m] / sig2[i];
+            pinvT[(size_t)m * nb + k] = (float)sum;
         }
     std::vector<float2> tw(N);
     std::vector<float> win(N);
@@ -496,10 +516,10 @@ int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin,
     AVSE_HIP_CHECK(hipMemcpy(t.window, win.data(), sizeof(float) * N, hipMemcpyHostToDevice));
     // Tridiagonal form for the fused kernel: every bin covered by at most two filters j0, j0 + 1 => M M^T
     // has no entry beyond the first off-diagonals, and pinv(M) a = M^T y with (M M^T) y = a (Thomas, no
-    // pivoting: the Gram matrix is symmetric positive definite).  Recomputed in double from G (Gi above
-    // overwrote its working copy).
+    // pivoting: the Gram matrix is symmetric positive definite).
     {
-        bool ok = true;
+        // (only for a well-conditioned bank, cond < 1e6: the Gram solve squares the condition number)
+        bool ok = *std::min_element(sig2.begin(), sig2.end()) > 1e-12 * smax2;
         std::vector<float4> bins(nb);
         for (int k = 0; k < nb && ok; ++k) {
             int j0 = -1, cnt = 0;

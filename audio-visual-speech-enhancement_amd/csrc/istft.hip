@@ -150,17 +150,17 @@ __global__ __launch_bounds__(64) void k_istft640(IstftArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_istft_fused (n_fft 640, hop 160): one persistent 8-wave block per output chunk of OF = 21 hops
-// (3,360 samples) of one utterance.  The chunk's samples are the overlap-add of frames
-// [21 b - 1, 21 b + 22] (24 frames, 3 of them shared with each neighbour and recomputed), so the
+// k_istft_fused (n_fft 640, hop 160): one persistent 11-wave block per output chunk of OF = 30 hops
+// (4,800 samples) of one utterance.  The chunk's samples are the overlap-add of frames
+// [30 b - 1, 30 b + 31] (FW = 33 frames, 3 of them shared with each neighbour and recomputed), so the
 // frames never leave LDS: the unfused path wrote 2,560 B per frame to a scratch buffer and re-read it in
 // k_ola, and its per-bin 80-term dense pinv dot (25.7K global-load MACs per frame) was the dominant cost
 // (2.4 ms for 10k clips).  Per chunk:
-//   1. amp = 10^(dB/20) for the 24 frames -> LDS [24][80]
-//   2. y = (M M^T)^{-1} amp for all 24 frames as one fp32 MFMA product with the host-inverted Gram matrix
+//   1. amp = 10^(dB/20) for the 33 frames -> LDS [33][81]
+//   2. y = (M M^T)^{-1} amp for all 33 frames as one fp32 MFMA product with the host-inverted Gram matrix
 //      (round 2: a Thomas recurrence, one lane per frame)
 //   3. X[k] = M[j0][k] y[j0] + M[j0+1][k] y[j0+1] (pinv(M) amp = M^T y), times the mixture's unit phase,
-//      read bin-major / frame-minor (24-frame runs of the [bin][frame] STFT); folded into the 320-point
+//      read bin-major / frame-minor (33-frame runs of the [bin][frame] STFT); folded into the 320-point
 //      complex sequence Z' of the real inverse FFT, both halves (k, 320 - k) by one lane
 //   4. the in-register 20 x 16 DFTs of K1 (3 frames per wave) -> windowed time samples in the frame's slot
 //   5. overlap-add in increasing frame order x 1 / window sum-square (a per-position table in the interior)
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64) void k_istft640(IstftArgs a) {
 constexpr int OF = AVSE_ISTFT_OF;            // output hops per chunk
 constexpr int FW = OF + 3;                   // frames per chunk (n_fft / hop - 1 = 3 extra)
 static_assert(FW % FPG == 0, "whole waves of 3 frames");
-constexpr int IWAVES = FW / FPG;             // 8
+constexpr int IWAVES = FW / FPG;             // 11
 constexpr int NMEL = 80;                     // bands (host-checked: the fused kernel runs only for n_mels == 80)
 
 __device__ __forceinline__ void ibarrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

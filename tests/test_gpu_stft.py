@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from audio_edge_inputs import clamp_conditions, oracle_pre, segments_533_input, sliced_segments_input
 from conftest import synth_audio
 from oracle import librosa_ref as R
 
@@ -44,10 +45,13 @@ def test_segments_match_oracle(gpu, pad_mode):
 
 def test_sliced_segments_drop_last_frame_but_keep_its_max(gpu):
     ops = _ops()
-    rng = np.random.default_rng(2)
-    x = synth_audio(rng, 16, 3200)
-    # make the LAST frame the loudest so the top_db floor depends on the dropped frame
-    x[:, -300:] *= 8
+    # the LAST frame is the loudest, so the top_db floor depends on the dropped frame — and the rest of the utterance is
+    # quiet enough for the clamp to reach it (audio_edge_inputs.wide: 34-50 % of the elements at the floor, the oracle
+    # 2-5 dB away from "maximum over the kept frames only"; a plain synth_audio tail x 8 left the clamped share at 0,
+    # so nothing here depended on the maximum)
+    x = sliced_segments_input()
+    for u in range(16):
+        clamp_conditions(oracle_pre(x[u], 640, 160)[0], 80.0, 20, dropped=True)
     got = ops.spectrogram(torch.from_numpy(x).to(gpu), frames_per_slice=20).cpu().numpy()
     assert got.shape == (16, 1, 80, 20)
     for u in range(16):
@@ -164,9 +168,9 @@ def test_533_segments_match_oracle(gpu, pad_mode):
     in-kernel), unsliced and sliced to 24 frames (the dropped 25th frame still sets the top_db floor: it is made the
     loudest)."""
     ops = _ops()
-    rng = np.random.default_rng(12)
-    x = synth_audio(rng, 48, 3200)
-    x[:8, -200:] *= 8
+    x = segments_533_input()     # audio_edge_inputs.wide: the clamp is at work and its floor is set by frame 24
+    for u in range(48):
+        clamp_conditions(oracle_pre(x[u], 533, 133)[0], 80.0, 24, dropped=True)
     d = torch.from_numpy(x).to(gpu)
     got = ops.spectrogram(d, n_fft=533, hop_length=133, pad_mode=pad_mode).cpu().numpy()
     sl = ops.spectrogram(d, n_fft=533, hop_length=133, pad_mode=pad_mode, frames_per_slice=24).cpu().numpy()
