@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <string>
 
+#include "layer_geom.h"
+#include "options.h"
+
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -23,29 +26,6 @@ int ctx_device_index(const struct ::avse_ctx* c);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for `fn` on the CURRENT device, once per (kernel, device)
 // (thread-safe; capi.hip).  Every launcher that needs more than 64 KB of dynamic LDS calls it first.
 int ensure_lds_attr(const void* fn, int bytes);
-
-// Kernel-path switches of one context.  Defaults are the production path; every field exists for an A/B
-// experiment or a layer-by-layer parity test.  Initialised once from the AVSE_* environment at
-// avse_ctx_create, changed with avse_ctx_set_option; launch code never reads the environment.
-struct Options {
-    int no_gemm = 0;          // AVSE_NO_GEMM: v_conv6 + dense layers on k_conv + split-K reduce (not k_gemm)
-    int no_audenc = 0;        // AVSE_NO_AUDENC: audio encoder layer by layer (not k_aud_enc)
-    int no_dechead = 0;       // AVSE_NO_DECHEAD: d_deconv1..3 layer by layer (not k_dec_head)
-    int no_dectail = 0;       // AVSE_NO_DECTAIL: d_deconv4..6 layer by layer (not k_dec_tail)
-    int unfused_tail = 0;     // AVSE_UNFUSED_TAIL: d_deconv6 as its own kernel (d_deconv5 activation materialised)
-    int no_halo = 0;          // AVSE_NO_HALO: video convs on k_conv (read when weights are loaded)
-    int mfma32 = 0;           // AVSE_MFMA32: 32x32x16 compute waves in the stream convolutions
-    int serial = 0;           // AVSE_SERIAL: one stream for the whole forward
-    int graph = 0;            // AVSE_GRAPH: avse_forward replays a hipGraph per argument set
-    int gemm_ksplit_cap = 0;  // AVSE_GEMM_KSPLIT: cap k_gemm's split-K factor (0 = no cap)
-    int dense_istft = 0;      // AVSE_DENSE_ISTFT: ISTFT through the dense pinv + scratch frames + k_ola (not fused)
-    int no_act_scale = 0;     // AVSE_NO_ACT_SCALE: split weights loaded without per-layer activation exponents
-    int no_win = 0;           // AVSE_NO_WIN: split stride-1 gather layers on k_conv, not the windowed conv_win.hip
-    int no_v1p = 0;           // AVSE_NO_V1P: split 5-frame v_conv1 on k_conv_v1s (K 160), not k_conv_v1p (K 128; read at load)
-    int no_a1valu = 0;        // AVSE_NO_A1VALU: split a_conv1 on k_conv after audio_prep, not k_aconv1_split
-    int no_planar = 0;        // AVSE_NO_PLANAR: split stream convs on the slice-by-slice [Ah | Al] grouping with lane swaps
-    int side_prio = 0;        // AVSE_SIDE_PRIO: audio side stream priority (0 default, 1 least, 2 greatest; read when created)
-};
 
 #define AVSE_HIP_CHECK(expr)                                                                   \
     do {                                                                                       \
@@ -174,17 +154,6 @@ struct IstftArgs {
 int launch_istft(const IstftArgs& a, hipStream_t s);
 
 // ---- implicit-GEMM convolution ----------------------------------------------------------
-constexpr int MAX_TAPS = 25;
-constexpr int MAX_PHASES = 4;
-
-struct ConvPhase {
-    int py, px;          // output phase offset (deconv); 0 for forward convs
-    int ntaps;
-    int kpad;            // ntaps * cin padded to the k-slab (multiple of 32)
-    long long w_off;     // element offset of this phase's packed weights [cout][kpad]
-    int tap_off;         // offset of this phase's (dy, dx) pairs in ConvArgs::taps
-};
-
 struct ConvArgs {
     const void* in;      // T [N][Hi][Wi][Ci] (clip stride in_clip_stride)
     void* out;           // T
@@ -341,7 +310,6 @@ int launch_aud_enc(const AudEncArgs& a, hipStream_t s);
 int launch_dec_tail(const DecTailArgs& a, hipStream_t s);
 
 // ---- tiled bf16 video convolutions: conv_v1r.hip (v_conv1), conv_stream.hip (v_conv2..v_conv5) ----
-enum HaloVariant { HALO_NONE = -1, HALO_V1 = 0, HALO_K5 = 1, HALO_K3_16 = 2, HALO_K3_8 = 3, HALO_V1P = 4 };
 // output element format of the tiled video convolutions: bf16; split f16 pairs (per pixel and 16 channels,
 // [h(16) | l(16)] with h = f16(x), l = f16(x - h): the next split layer's input); f32
 enum HaloOut { OUT_BF16 = 0, OUT_S16 = 1, OUT_F32 = 2 };

@@ -1,6 +1,6 @@
-// libavse C-ABI (include/avse.h): contexts, librosa-equivalent tables, weight folding/packing and
-// the layer plan of /root/reference/network.py, executed as a sequence of HIP kernel launches on
-// the caller's stream.
+// libavse C-ABI (include/avse.h): contexts, the device copies of the librosa-equivalent tables (spec_tables.cpp) and
+// of the folded / packed weights (weight_pack.cpp), and the layer plan of /root/reference/network.py, executed as a
+// sequence of HIP kernel launches on the caller's stream.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -16,6 +16,8 @@
 #include "../../include/avse.h"
 #include "avse_common.h"
 #include "netplan.h"
+#include "spec_tables.h"
+#include "weight_pack.h"
 
 namespace avse {
 static thread_local std::string g_err;
@@ -43,44 +45,6 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-// ---------------------------------------------------------------------------------------------
-// librosa-equivalent host tables (double precision, rounded to float once)
-// ---------------------------------------------------------------------------------------------
-double hz_to_mel(double f) {  // Slaney (htk=False)
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
-    const double logstep = std::log(6.4) / 27.0;
-    if (f >= min_log_hz) return min_log_mel + std::log(f / min_log_hz) / logstep;
-    return f / f_sp;
-}
-double mel_to_hz(double m) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
-    const double logstep = std::log(6.4) / 27.0;
-    if (m >= min_log_mel) return min_log_hz * std::exp(logstep * (m - min_log_mel));
-    return f_sp * m;
-}
-
-// librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm=1) -> [n_mels][n_bins] (double)
-std::vector<double> mel_filterbank(int sr, int n_fft, int n_mels, double fmin, double fmax) {
-    const int nb = 1 + n_fft / 2;
-    std::vector<double> w((size_t)n_mels * nb, 0.0);
-    std::vector<double> fftf(nb), melf(n_mels + 2);
-    for (int k = 0; k < nb; ++k) fftf[k] = (nb == 1) ? 0.0 : (double)k * ((double)sr / 2) / (double)(nb - 1);
-    const double lo = hz_to_mel(fmin), hi = hz_to_mel(fmax);
-    for (int i = 0; i < n_mels + 2; ++i) melf[i] = mel_to_hz(lo + (hi - lo) * (double)i / (double)(n_mels + 1));
-    for (int i = 0; i < n_mels; ++i) {
-        const double d0 = melf[i + 1] - melf[i], d1 = melf[i + 2] - melf[i + 1];
-        const double enorm = 2.0 / (melf[i + 2] - melf[i]);
-        for (int k = 0; k < nb; ++k) {
-            const double lower = -(melf[i] - fftf[k]) / d0;
-            const double upper = (melf[i + 2] - fftf[k]) / d1;
-            double v = std::fmin(lower, upper);
-            if (v < 0) v = 0;
-            w[(size_t)i * nb + k] = v * enorm;
-        }
-    }
-    return w;
-}
-
 struct SpecTables {
     int sr = -1, n_fft = -1, n_mels = -1;
     double fmin = 0, fmax = 0;
@@ -89,30 +53,13 @@ struct SpecTables {
     MelTable mel;
 };
 
-// ---------------------------------------------------------------------------------------------
-// network plan (network.py:17-175)
-// ---------------------------------------------------------------------------------------------
-uint16_t f2h(float f) {   // f32 -> f16 bits, round to nearest even (hipcc's host _Float16 conversion)
-    const _Float16 h = (_Float16)f;
-    uint16_t u;
-    std::memcpy(&u, &h, 2);
-    return u;
-}
-float h2f(uint16_t u) {
-    _Float16 h;
-    std::memcpy(&h, &u, 2);
-    return (float)h;
-}
-
-uint16_t f2bf(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffff) ? 0x40 : 0));
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 }  // namespace
+
+// the host-only tables' element types are uploaded as the HIP vector types the kernels read
+static_assert(sizeof(Tap) == sizeof(int2) && offsetof(Tap, dy) == offsetof(int2, x) && offsetof(Tap, dx) == offsetof(int2, y),
+              "Tap must be layout-compatible with int2");
+static_assert(sizeof(Cplx) == sizeof(float2) && offsetof(Cplx, im) == offsetof(float2, y), "Cplx must match float2");
+static_assert(sizeof(MelBin) == sizeof(float4) && offsetof(MelBin, j0) == offsetof(float4, z), "MelBin must match float4");
 
 struct IstftTables {
     int sr = -1, n_fft = -1, n_mels = -1;
@@ -174,7 +121,7 @@ struct GpuLayer {
     float* shift = nullptr;
     int2* taps = nullptr;
     int halo = HALO_NONE;     // halo-tiled kernel variant (bf16 video convs)
-    void* w_halo = nullptr;   // bf16 packing for conv_stream.hip / conv_v1r.hip (see build_layer)
+    void* w_halo = nullptr;   // packing for conv_stream.hip / conv_v1r.hip (weight_pack.h)
     void* w_dense = nullptr;  // a_conv1 only (bf16): [Cout][32], k = ky * kw + kx, for conv_aud.hip
     float* w_f32 = nullptr;   // a_conv1 only (split): [kh * kw][Cout] f32 x 2^e_n, for conv.hip k_aconv1_split
     float* scale_h = nullptr; // |scale| for w_halo: channels with a negative BN scale have negated weights
@@ -375,553 +322,83 @@ int ensure_prep(avse_ctx* c, size_t need, hipStream_t s) {
     return 0;
 }
 
+// hipMalloc + copy of a host table into *out (D: the device-side element type of the same layout)
+template <typename D, typename T>
+int table_to_device(const std::vector<T>& h, D** out) {
+    static_assert(sizeof(D) == sizeof(T), "element layout");
+    AVSE_HIP_CHECK(hipMalloc(out, sizeof(T) * h.size()));
+    AVSE_HIP_CHECK(hipMemcpy(*out, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int ensure_spec_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, double fmax) {
     SpecTables& t = c->spec;
     if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
     (void)hipFree(t.twiddle); (void)hipFree(t.window); (void)hipFree(t.mel.start); (void)hipFree(t.mel.width); (void)hipFree(t.mel.weight);
     t = SpecTables();
-    std::vector<float2> tw(n_fft);
-    std::vector<float> win(n_fft);
-    for (int k = 0; k < n_fft; ++k) {
-        const double ang = -2.0 * M_PI * (double)k / (double)n_fft;
-        tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        win[k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)n_fft));
-    }
-    const int nb = 1 + n_fft / 2;
-    std::vector<double> fb = mel_filterbank(sr, n_fft, n_mels, fmin, fmax);
-    std::vector<int> st(n_mels), wd(n_mels);
-    int maxw = 1;
-    for (int m = 0; m < n_mels; ++m) {
-        int lo = -1, hi = -1;
-        for (int k = 0; k < nb; ++k)
-            if (fb[(size_t)m * nb + k] > 0) { if (lo < 0) lo = k; hi = k; }
-        // bands start at an even bin (a leading zero weight when the first non-zero bin is odd): the STFT kernels
-        // read a band's magnitudes as 8-B pairs (half the LDS instructions and bank-conflict cycles of 4-B reads)
-        lo = lo < 0 ? -1 : (lo & ~1);
-        st[m] = lo < 0 ? 0 : lo;
-        wd[m] = lo < 0 ? 0 : hi - lo + 1;
-        if (wd[m] > maxw) maxw = wd[m];
-    }
-    if (maxw <= 24) maxw = 24;   // rows padded to the STFT kernel's compile-time band width (16-B staging copies)
-    std::vector<float> wt((size_t)n_mels * maxw, 0.f);
-    for (int m = 0; m < n_mels; ++m)
-        for (int j = 0; j < wd[m]; ++j) wt[(size_t)m * maxw + j] = (float)fb[(size_t)m * nb + st[m] + j];
-    AVSE_HIP_CHECK(hipMalloc(&t.twiddle, sizeof(float2) * n_fft));
-    AVSE_HIP_CHECK(hipMalloc(&t.window, sizeof(float) * n_fft));
-    AVSE_HIP_CHECK(hipMalloc(&t.mel.start, sizeof(int) * n_mels));
-    AVSE_HIP_CHECK(hipMalloc(&t.mel.width, sizeof(int) * n_mels));
-    AVSE_HIP_CHECK(hipMalloc(&t.mel.weight, sizeof(float) * wt.size()));
-    AVSE_HIP_CHECK(hipMemcpy(t.twiddle, tw.data(), sizeof(float2) * n_fft, hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.window, win.data(), sizeof(float) * n_fft, hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.mel.start, st.data(), sizeof(int) * n_mels, hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.mel.width, wd.data(), sizeof(int) * n_mels, hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.mel.weight, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice));
+    const DftTables dft = dft_tables(n_fft);
+    const MelBands mb = mel_bands(sr, n_fft, n_mels, fmin, fmax);
+    if (int rc = table_to_device(dft.twiddle, &t.twiddle)) return rc;
+    if (int rc = table_to_device(dft.window, &t.window)) return rc;
+    if (int rc = table_to_device(mb.start, &t.mel.start)) return rc;
+    if (int rc = table_to_device(mb.width, &t.mel.width)) return rc;
+    if (int rc = table_to_device(mb.weight, &t.mel.weight)) return rc;
     t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
-    // k_spec_seg's mel pass j covers items 64 j .. 64 j + 63 = bands (item / 3): the widest of those bands (aligned
-    // start) in 4-bin quads; the rows stay padded to maxw, so a pass reads only the quads its bands can use
-    for (int j = 0; j < 4; ++j) {
-        int w = 0;
-        for (int it = 64 * j; it < 64 * j + 64 && it / 3 < n_mels; ++it) w = std::max(w, wd[it / 3]);
-        t.mel.seg_nq[j] = std::min((w + 3) / 4, maxw / 4);
-        // k_spec_seg reads 16-B quads from 4-aligned band starts (st & ~3: a further 0 or 2 leading zero weights)
-        int w4 = 0;
-        for (int it = 64 * j; it < 64 * j + 64 && it / 3 < n_mels; ++it) w4 = std::max(w4, (st[it / 3] & 3) + wd[it / 3]);
-        t.mel.seg_nq4[j] = std::min((w4 + 3) / 4, (maxw + 4) / 4);
-    }
-    t.mel.n_mels = n_mels; t.mel.n_bins = nb; t.mel.max_width = maxw;
+    std::memcpy(t.mel.seg_nq, mb.seg_nq, sizeof(t.mel.seg_nq));
+    std::memcpy(t.mel.seg_nq4, mb.seg_nq4, sizeof(t.mel.seg_nq4));
+    t.mel.n_mels = n_mels; t.mel.n_bins = mb.n_bins; t.mel.max_width = mb.max_width;
     return 0;
 }
 
-// pinv(mel) as np.linalg.pinv computes it (data_processor.py:112): from the singular value decomposition, dropping
-// the singular values at or below 1e-15 of the largest.  The reference's own banks are full row rank (cond ~4.5), for
-// which this is M^T (M M^T)^{-1}; a bank with more bands than the bins can tell apart is not (n_fft 401 with 80 bands:
-// an FFT bin lands on a band edge and leaves singular values of 3e-6 and 2e-20 of the largest), and there the
-// Gram-matrix inverse this replaced followed the dropped direction (waveform 7e-4 from the oracle's).
-// One-sided Jacobi (Hestenes) on the rows of M, in double: plane rotations J make the rows of A = J M mutually
-// orthogonal, so sigma_i = |a_i|, M = J^T diag(sigma) (a_i / sigma_i) and pinv(M)[k][m] = sum_i a_i[k] J[i][m] /
-// sigma_i^2 over the kept i.  Small singular values come out to high relative accuracy.  Also the inverse-DFT tables.
+// pinv(mel), the inverse-DFT tables and, where the bank allows it, the fused kernel's tridiagonal form (spec_tables.cpp)
 int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, double fmax) {
     IstftTables& t = c->istft;
     if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
     (void)hipFree(t.pinvT); (void)hipFree(t.twiddle); (void)hipFree(t.window);
     (void)hipFree(t.bins); (void)hipFree(t.gram_inv);
     t = IstftTables();
-    const int nb = 1 + n_fft / 2, N = 2 * (nb - 1);
-    const std::vector<double> M = mel_filterbank(sr, n_fft, n_mels, fmin, fmax);
-    std::vector<double> A(M), J((size_t)n_mels * n_mels, 0.0);
-    for (int i = 0; i < n_mels; ++i) J[(size_t)i * n_mels + i] = 1.0;
-    // 5-8 sweeps for a full-rank bank; the rounding noise of a zero direction keeps rotating until the cap
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < n_mels - 1; ++p)
-            for (int q = p + 1; q < n_mels; ++q) {
-                double* ap = &A[(size_t)p * nb];
-                double* aq = &A[(size_t)q * nb];
-                double alpha = 0, beta = 0, gamma = 0;
-                for (int k = 0; k < nb; ++k) {
-                    alpha += ap[k] * ap[k];
-                    beta += aq[k] * aq[k];
-                    gamma += ap[k] * aq[k];
-                }
-                if (std::fabs(gamma) <= 1e-15 * std::sqrt(alpha * beta)) continue;
-                rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double az = std::fabs(zeta);   // (zeta^2 overflows past 1e154: tan = 1 / (2 zeta) there)
-                const double tn = az > 1e100 ? 0.5 / zeta : (zeta >= 0 ? 1.0 : -1.0) / (az + std::sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / std::sqrt(1.0 + tn * tn), sn = cs * tn;
-                for (int k = 0; k < nb; ++k) {
-                    const double x = ap[k], y = aq[k];
-                    ap[k] = cs * x - sn * y;
-                    aq[k] = sn * x + cs * y;
-                }
-                double* jp = &J[(size_t)p * n_mels];
-                double* jq = &J[(size_t)q * n_mels];
-                for (int m = 0; m < n_mels; ++m) {
-                    const double x = jp[m], y = jq[m];
-                    jp[m] = cs * x - sn * y;
-                    jq[m] = sn * x + cs * y;
-                }
-            }
-        if (!rotated) break;
-    }
-    std::vector<double> sig2(n_mels);
-    double smax2 = 0;
-    for (int i = 0; i < n_mels; ++i) {
-        double a2 = 0;
-        for (int k = 0; k < nb; ++k) a2 += A[(size_t)i * nb + k] * A[(size_t)i * nb + k];
-        sig2[i] = a2;
-        smax2 = std::max(smax2, a2);
-    }
-    // pinv[k][m] = sum_i a_i[k] J[i][m] / sigma_i^2 over sigma_i > 1e-15 sigma_max; stored transposed [m][k]
-    std::vector<float> pinvT((size_t)n_mels * nb);
-    for (int m = 0; m < n_mels; ++m)
-        for (int k = 0; k < nb; ++k) {
-            double sum = 0;
-            for (int i = 0; i < n_mels; ++i)
-                if (sig2[i] > 1e-30 * smax2) sum += A[(size_t)i * nb + k] * J[(size_t)i * n_mels + m] / sig2[i];
-            pinvT[(size_t)m * nb + k] = (float)sum;
-        }
-    std::vector<float2> tw(N);
-    std::vector<float> win(N);
-    for (int k = 0; k < N; ++k) {
-        const double ang = -2.0 * M_PI * (double)k / (double)N;
-        tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        win[k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)N));
-    }
-    AVSE_HIP_CHECK(hipMalloc(&t.pinvT, sizeof(float) * pinvT.size()));
-    AVSE_HIP_CHECK(hipMalloc(&t.twiddle, sizeof(float2) * N));
-    AVSE_HIP_CHECK(hipMalloc(&t.window, sizeof(float) * N));
-    AVSE_HIP_CHECK(hipMemcpy(t.pinvT, pinvT.data(), sizeof(float) * pinvT.size(), hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.twiddle, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-    AVSE_HIP_CHECK(hipMemcpy(t.window, win.data(), sizeof(float) * N, hipMemcpyHostToDevice));
-    // Tridiagonal form for the fused kernel: every bin covered by at most two filters j0, j0 + 1 => M M^T
-    // has no entry beyond the first off-diagonals, and pinv(M) a = M^T y with (M M^T) y = a (Thomas, no
-    // pivoting: the Gram matrix is symmetric positive definite).
-    {
-        // (only for a well-conditioned bank, cond < 1e6: the Gram solve squares the condition number)
-        bool ok = *std::min_element(sig2.begin(), sig2.end()) > 1e-12 * smax2;
-        std::vector<float4> bins(nb);
-        for (int k = 0; k < nb && ok; ++k) {
-            int j0 = -1, cnt = 0;
-            for (int j = 0; j < n_mels; ++j)
-                if (M[(size_t)j * nb + k] != 0.0) {
-                    if (j0 < 0) j0 = j;
-                    else if (j != j0 + 1) ok = false;
-                    ++cnt;
-                }
-            if (cnt > 2) ok = false;
-            const float w0 = j0 >= 0 ? (float)M[(size_t)j0 * nb + k] : 0.f;
-            const float w1 = (j0 >= 0 && j0 + 1 < n_mels) ? (float)M[(size_t)(j0 + 1) * nb + k] : 0.f;
-            int j0b = j0;
-            float j0f;
-            std::memcpy(&j0f, &j0b, 4);
-            bins[k] = make_float4(w0, w1, j0f, 0.f);
-        }
-        if (ok) {
-            auto gram = [&](int i, int j) {
-                double acc = 0;
-                for (int k = 0; k < nb; ++k) acc += M[(size_t)i * nb + k] * M[(size_t)j * nb + k];
-                return acc;
-            };
-            // M M^T must be tridiagonal (adjacent Slaney triangles overlap, nothing else does) and its LU pivots
-            // non-zero: the checks that make M^T (M M^T)^{-1} = pinv(M) computable from the band-local pieces
-            double cprev = 0;
-            for (int i = 0; i < n_mels && ok; ++i) {
-                for (int j = 0; j < i - 1 && ok; ++j)
-                    if (gram(i, j) != 0.0) ok = false;
-                const double ai = i > 0 ? gram(i, i - 1) : 0.0, bi = gram(i, i);
-                const double ci = i + 1 < n_mels ? gram(i, i + 1) : 0.0;
-                const double piv = bi - ai * cprev;
-                if (!(std::fabs(piv) > 1e-300)) { ok = false; break; }
-                cprev = ci / piv;
-            }
-            if (ok) {
-                AVSE_HIP_CHECK(hipMalloc(&t.bins, sizeof(float4) * nb));
-                AVSE_HIP_CHECK(hipMemcpy(t.bins, bins.data(), sizeof(float4) * nb, hipMemcpyHostToDevice));
-                if (n_mels == 80) {
-                    // (M M^T)^{-1} by Gauss-Jordan in double (the Gram matrix is symmetric positive definite, cond ~20):
-                    // the fused kernel solves all frames of a chunk at once as a [frames x 80] x [80 x 80] fp32 MFMA
-                    // product (round 2: one Thomas recurrence per frame and lane)
-                    const int n = n_mels;
-                    std::vector<double> g((size_t)n * n), inv((size_t)n * n, 0.0);
-                    for (int i = 0; i < n; ++i) {
-                        inv[(size_t)i * n + i] = 1.0;
-                        for (int j = std::max(0, i - 1); j <= std::min(n - 1, i + 1); ++j) g[(size_t)i * n + j] = gram(i, j);
-                    }
-                    for (int c = 0; c < n && ok; ++c) {
-                        const double piv = g[(size_t)c * n + c];
-                        if (!(std::fabs(piv) > 1e-300)) { ok = false; break; }
-                        for (int j = 0; j < n; ++j) { g[(size_t)c * n + j] /= piv; inv[(size_t)c * n + j] /= piv; }
-                        for (int r = 0; r < n; ++r) {
-                            if (r == c) continue;
-                            const double f = g[(size_t)r * n + c];
-                            if (f == 0.0) continue;
-                            for (int j = 0; j < n; ++j) {
-                                g[(size_t)r * n + j] -= f * g[(size_t)c * n + j];
-                                inv[(size_t)r * n + j] -= f * inv[(size_t)c * n + j];
-                            }
-                        }
-                    }
-                    if (ok) {
-                        std::vector<float> fi(inv.begin(), inv.end());
-                        AVSE_HIP_CHECK(hipMalloc(&t.gram_inv, sizeof(float) * n * n));
-                        AVSE_HIP_CHECK(hipMemcpy(t.gram_inv, fi.data(), sizeof(float) * n * n, hipMemcpyHostToDevice));
-                    }
-                }
-            }
-        }
-    }
+    const IstftHostTables h = istft_tables(sr, n_fft, n_mels, fmin, fmax);
+    const DftTables dft = dft_tables(2 * (n_fft / 2));
+    if (int rc = table_to_device(h.pinvT, &t.pinvT)) return rc;
+    if (int rc = table_to_device(dft.twiddle, &t.twiddle)) return rc;
+    if (int rc = table_to_device(dft.window, &t.window)) return rc;
+    if (!h.bins.empty())
+        if (int rc = table_to_device(h.bins, &t.bins)) return rc;
+    if (!h.gram_inv.empty())
+        if (int rc = table_to_device(h.gram_inv, &t.gram_inv)) return rc;
     t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
     return 0;
 }
 
-// AVSE_F32_SPLIT activation exponents.  The split layers carry activations as f16 pairs, whose ~22 significant bits
-// hold for |x| in [2^-3, 65504): below 2^-3 the lo piece is an f16 subnormal (absolute quantum 2^-24), from 65520 the
-// hi piece overflows (the range guard then reports it).  A BatchNormalization layer's output per channel is
-// gamma xhat + beta with xhat standardised by the moving statistics, so the layer's magnitude is ~ M = max_c (|beta_c| +
-// |gamma_c|).  Layers with M in [2^-2, 2^8] keep exponent 0 (the common case: BN keeps activations O(1), and every
-// stored value is then exactly the unscaled pair); any other layer stores the pairs of x 2^e with M 2^e in (4, 8], so a
-// layer of tiny activations keeps its 22 bits and a layer of huge ones its headroom below 65504 (folded into the
-// layer's own scale / shift and the next layer's scale, build_layer).  The two concat halves (a_conv5, v_conv6) share
-// one exponent, the smaller (enc_dense reads them as one K); d_deconv5 feeds the fp32 d_deconv6 dot (exponent 0).
-void act_exponents(const NetPlan& P, const float* blob, int* e) {
-    const float* p = blob;
-    for (int i = 0; i < kNumLayers; ++i) {
-        const LayerDef& L = P.L[i];
-        p += (size_t)L.kh * L.kw * L.cin * L.cout + L.cout;
-        e[i] = 0;
-        if (!L.bn) continue;
-        const float* g = p;
-        const float* b = p + L.bn_channels;
-        p += 4 * (size_t)L.bn_channels;
-        double m = 0.0;
-        for (int c = 0; c < L.bn_channels; ++c) m = std::max(m, std::fabs((double)b[c]) + std::fabs((double)g[c]));
-        if (!(m > 0.0) || !std::isfinite(m) || (m >= 0.25 && m <= 256.0)) continue;
-        int e2 = 0;
-        (void)std::frexp(m, &e2);                      // m <= 2^e2
-        e[i] = std::max(-24, std::min(24, 3 - e2));    // m 2^e in (4, 8]
-    }
-    e[4] = e[10] = std::min(e[4], e[10]);
-    e[18] = e[19] = 0;
-}
-
-// the exponent of the activations layer i reads (act_exponents; the network inputs: 0)
-int act_exp_in(const int* e, int i) {
-    if (i == 0 || i == 5) return 0;
-    if (i == 11) return e[4];
-    return e[i - 1];
-}
-
-// Build phase/tap tables + packed [Cout][Kpad] weights for one layer.
+// Pack one layer on the host (weight_pack.cpp: geometry, folded scale / shift, every weight layout) and upload it.
 int build_layer(avse_weights* W, int li, const float* kernel, const float* bias, const float* bn,
                 const Options& opt, int e_in = 0, int e_out = 0) {
     const LayerDef& L = W->plan.L[li];
+    const PackedLayer P = pack_layer(L, kernel, bias, bn, W->dtype, opt, e_in, e_out);
+    if (P.geom.status != GEOM_OK) return fail(AVSE_ERR_UNSUPPORTED, geom_message(P.geom.status));
     GpuLayer& G = W->layers[li];
     G.def = L;
-    const int CHUNK_ELEMS = 8;   // channel padding so a 16-B chunk never straddles a tap (bf16: 8)
-    G.cin_pad = (L.cin % CHUNK_ELEMS) ? ((L.cin + CHUNK_ELEMS - 1) / CHUNK_ELEMS) * CHUNK_ELEMS : L.cin;
-    const int Cp = G.cin_pad;
-    std::vector<int2> taps;
-    std::vector<float> packed;
-    std::vector<std::vector<std::pair<int, int>>> phase_taps;   // (ky, kx) per tap
-    if (L.kind == DENSE) {
-        G.hq = G.wq = G.ho = G.wo = 1;
-        G.nphase = 1;
-        phase_taps.push_back({{0, 0}});
-        taps.push_back(make_int2(0, 0));
-        G.ph[0] = ConvPhase{0, 0, 1, 0, 0, 0};
-    } else if (L.kind == CONV) {
-        const int pt = same_pad_before(L.hin, L.kh, L.sh), pl = same_pad_before(L.win, L.kw, L.sw);
-        G.hq = same_out(L.hin, L.sh);
-        G.wq = same_out(L.win, L.sw);
-        G.ho = L.pool ? G.hq / 2 : G.hq;
-        G.wo = L.pool ? G.wq / 2 : G.wq;
-        G.nphase = 1;
-        std::vector<std::pair<int, int>> pt_list;
-        for (int ky = 0; ky < L.kh; ++ky)
-            for (int kx = 0; kx < L.kw; ++kx) {
-                pt_list.push_back({ky, kx});
-                taps.push_back(make_int2(ky - pt, kx - pl));
-            }
-        phase_taps.push_back(pt_list);
-        G.ph[0] = ConvPhase{0, 0, (int)pt_list.size(), 0, 0, 0};
-    } else {  // DECONV: TF conv2d_transpose 'SAME' to in*s, crop at pad_before = max(k - s, 0) / 2
-        const int pt = std::max(L.kh - L.sh, 0) / 2, pl = std::max(L.kw - L.sw, 0) / 2;
-        G.hq = L.hin;
-        G.wq = L.win;
-        G.ho = L.hin * L.sh;
-        G.wo = L.win * L.sw;
-        G.nphase = L.sh * L.sw;
-        if (G.nphase > MAX_PHASES) return fail(AVSE_ERR_UNSUPPORTED, "deconv stride too large");
-        for (int py = 0; py < L.sh; ++py)
-            for (int px = 0; px < L.sw; ++px) {
-                std::vector<std::pair<int, int>> pt_list;
-                const int toff = (int)taps.size();
-                for (int ky = 0; ky < L.kh; ++ky) {
-                    const int ry = py + pt - ky;
-                    if (((ry % L.sh) + L.sh) % L.sh) continue;
-                    for (int kx = 0; kx < L.kw; ++kx) {
-                        const int rx = px + pl - kx;
-                        if (((rx % L.sw) + L.sw) % L.sw) continue;
-                        pt_list.push_back({ky, kx});
-                        taps.push_back(make_int2(ry / L.sh, rx / L.sw));
-                    }
-                }
-                const int p = py * L.sw + px;
-                G.ph[p] = ConvPhase{py, px, (int)pt_list.size(), 0, 0, toff};
-                phase_taps.push_back(pt_list);
-            }
-    }
-    // pack weights per phase: W[n][j*Cp + c]
-    long long woff = 0;
-    for (int p = 0; p < G.nphase; ++p) {
-        const auto& pl_ = phase_taps[p];
-        const int kpad = (((int)pl_.size() * Cp + 31) / 32) * 32;
-        G.ph[p].kpad = kpad;
-        G.ph[p].w_off = woff;
-        packed.resize((size_t)(woff + (long long)L.cout * kpad), 0.f);
-        for (int n = 0; n < L.cout; ++n)
-            for (size_t j = 0; j < pl_.size(); ++j) {
-                const int ky = pl_[j].first, kx = pl_[j].second;
-                for (int c = 0; c < L.cin; ++c) {
-                    float v;
-                    if (L.kind == DENSE) v = kernel[(size_t)c * L.cout + n];
-                    else if (L.kind == CONV) v = kernel[(((size_t)ky * L.kw + kx) * L.cin + c) * L.cout + n];
-                    else v = kernel[(((size_t)ky * L.kw + kx) * L.cout + n) * L.cin + c];
-                    packed[(size_t)woff + (size_t)n * kpad + j * Cp + c] = v;
-                }
-            }
-        woff += (long long)L.cout * kpad;
-    }
-    // fold bias + BN into scale/shift
-    std::vector<float> scale(L.cout), shift(L.cout);
-    for (int n = 0; n < L.cout; ++n) {
-        if (L.bn) {
-            const int c = n % L.bn_channels;
-            const float* g = bn;
-            const float* b = bn + L.bn_channels;
-            const float* mu = bn + 2 * L.bn_channels;
-            const float* var = bn + 3 * L.bn_channels;
-            const double s = (double)g[c] / std::sqrt((double)var[c] + (double)kBnEps);
-            scale[n] = (float)s;
-            shift[n] = (float)(((double)bias[n] - (double)mu[c]) * s + (double)b[c]);
-        } else {
-            scale[n] = 1.f;
-            shift[n] = bias[n];
-        }
-    }
+    G.cin_pad = P.geom.cin_pad;
+    G.hq = P.geom.hq; G.wq = P.geom.wq; G.ho = P.geom.ho; G.wo = P.geom.wo;
+    G.nphase = P.geom.nphase;
+    std::copy(P.geom.ph, P.geom.ph + MAX_PHASES, G.ph);
+    G.halo = P.halo;
+    const std::vector<Tap>& taps = P.geom.taps;
+    std::memcpy(G.htaps, taps.data(), sizeof(Tap) * std::min(taps.size(), (size_t)(MAX_TAPS * MAX_PHASES)));
+    // each non-empty buffer becomes one device allocation owned by W
+    auto up = [&](const auto& h, auto** out) { return h.empty() ? 0 : upload(W, h, out); };
+    float* w32 = nullptr;
+    uint16_t *w16 = nullptr, *w_halo = nullptr, *w_dense = nullptr;
+    Tap* dtaps = nullptr;
     int rc;
-    const bool split = W->dtype == AVSE_F32_SPLIT;
-    if (split && (e_in || e_out)) {
-        // activation exponents (act_exponents): this layer reads pairs of x 2^e_in and stores pairs of y 2^e_out, so
-        // y 2^e_out = LReLU(acc 2^-e_in scale 2^e_out + shift 2^e_out) — powers of two: exact, and they commute with
-        // LeakyReLU and max pooling
-        for (int n = 0; n < L.cout; ++n) {
-            scale[n] = std::ldexp(scale[n], e_out - e_in);
-            shift[n] = std::ldexp(shift[n], e_out);
-        }
-    }
-    std::vector<float> scale_g = scale;   // the generic kernel's epilogue scale (split: with the weight exponents undone)
-    if (W->dtype == AVSE_BF16) {
-        std::vector<uint16_t> pb(packed.size());
-        for (size_t i = 0; i < packed.size(); ++i) pb[i] = f2bf(packed[i]);
-        uint16_t* d;
-        if ((rc = upload(W, pb, &d))) return rc;
-        G.w = d;
-    } else if (split) {
-        // conv.hip k_conv<float, .., S16>: each 16-k slab row of [Cout][kpad] becomes [Bh(16) | Bl(16)] f16 (the same
-        // bytes), output channel n scaled by 2^e_n (max |w| 2^e_n in [2^14, 2^15), as the video layers' packing)
-        std::vector<int> ex(L.cout, 0);
-        for (int n = 0; n < L.cout; ++n) {
-            float mx = 0.f;
-            for (int p = 0; p < G.nphase; ++p)
-                for (int k = 0; k < G.ph[p].kpad; ++k)
-                    mx = std::max(mx, std::fabs(packed[(size_t)G.ph[p].w_off + (size_t)n * G.ph[p].kpad + k]));
-            int e2 = 0;
-            if (mx > 0.f) (void)std::frexp(mx, &e2);
-            ex[n] = mx > 0.f ? 15 - e2 : 0;
-            scale_g[n] = std::ldexp(scale[n], -ex[n]);
-        }
-        if (L.kind == CONV && L.cin == 1) {   // a_conv1: f32 taps with the same per-channel power of two
-            std::vector<float> wf((size_t)L.kh * L.kw * L.cout);
-            for (int t = 0; t < L.kh * L.kw; ++t)
-                for (int n = 0; n < L.cout; ++n) wf[(size_t)t * L.cout + n] = std::ldexp(kernel[(size_t)t * L.cout + n], ex[n]);
-            if ((rc = upload(W, wf, &G.w_f32))) return rc;
-        }
-        std::vector<uint16_t> sp(2 * packed.size(), 0);
-        for (int p = 0; p < G.nphase; ++p)
-            for (int n = 0; n < L.cout; ++n)
-                for (int k = 0; k < G.ph[p].kpad; ++k) {
-                    const size_t src = (size_t)G.ph[p].w_off + (size_t)n * G.ph[p].kpad + k;
-                    const size_t dst = 2 * ((size_t)G.ph[p].w_off + (size_t)n * G.ph[p].kpad) + (size_t)(k / 16) * 32 + k % 16;
-                    const float v = std::ldexp(packed[src], ex[n]);
-                    const uint16_t h = f2h(v);
-                    sp[dst] = h;
-                    sp[dst + 16] = f2h(v - h2f(h));
-                }
-        uint16_t* d;
-        if ((rc = upload(W, sp, &d))) return rc;
-        G.w = d;
-    } else {
-        float* d;
-        if ((rc = upload(W, packed, &d))) return rc;
-        G.w = d;
-    }
-    if (W->dtype == AVSE_BF16 && L.kind == CONV && L.cin == 1 && L.kh * L.kw <= 32) {
-        // conv_aud.hip's a_conv1: the single input channel's taps as a dense 32-deep K (25 real)
-        std::vector<uint16_t> dw((size_t)L.cout * 32, 0);
-        for (int n = 0; n < L.cout; ++n)
-            for (int t = 0; t < L.kh * L.kw; ++t) dw[(size_t)n * 32 + t] = f2bf(kernel[(size_t)t * L.cout + n]);
-        uint16_t* d;
-        if ((rc = upload(W, dw, &d))) return rc;
-        G.w_dense = d;
-    }
-    if ((rc = upload(W, scale_g, &G.scale))) return rc;
-    if ((rc = upload(W, shift, &G.shift))) return rc;
-    if ((rc = upload(W, taps, &G.taps))) return rc;
-    for (size_t t = 0; t < taps.size() && t < (size_t)(MAX_TAPS * MAX_PHASES); ++t) G.htaps[t] = taps[t];
-
-    // packing for the bf16 video conv kernels: conv_stream.hip [slice][Cout][32], slice = (cg*4 + cc)*KS^2
-    // + tap; conv_v1r.hip (v_conv1) [kernel row][Cout][32].  Options::no_halo keeps the generic k_conv.
-    // Split dtype: the same kernels on split-f16 operands (see below).
-    if ((W->dtype == AVSE_BF16 || split) && L.kind == CONV && L.pool && L.hin >= 8 && !opt.no_halo) {
-        const int ntap = L.kh * L.kw;
-        if ((L.cin == 5 || L.cin == 6) && L.kh == 5)   // conv_v1r.hip: 5 (25 / 29.97 fps) or 6 frames (30)
-            G.halo = split && L.cin == 5 && L.kw == 5 && L.cout == 128 && !opt.no_v1p ? HALO_V1P : HALO_V1;
-        else if (L.cin % 128) G.halo = HALO_NONE;
-        else if (L.kh == 5) G.halo = HALO_K5;
-        else if (L.hin >= 16) G.halo = HALO_K3_16;
-        else G.halo = HALO_K3_8;
-        // Sign fold: a channel whose folded BN scale is negative gets negated weights and |scale|, so
-        // every epilogue scale is >= 0 and 2x2 max pooling commutes exactly with scale/shift (the kernels
-        // pool the raw accumulators, then apply one FMA).  bf16 negation and fp32 sums are exact.
-        std::vector<float> sgn(L.cout), scale_h(L.cout);
-        for (int n = 0; n < L.cout; ++n) {
-            sgn[n] = scale[n] < 0.f ? -1.f : 1.f;
-            scale_h[n] = std::fabs(scale[n]);
-        }
-        if (G.halo == HALO_NONE) return 0;
-        if (split) {
-            // split-f16 operands: output channel n's (sign-folded) weights scaled by 2^e_n, e_n = 14 - ceil(log2 max|w|),
-            // so that hi = f16(w 2^e) stays below 2^15 and lo = f16(w 2^e - hi) keeps full precision for every weight
-            // above 2^-10 of the channel's largest; the BN scale takes 2^-e_n back (powers of two: exact)
-            const int ntap = L.kh * L.kw;
-            std::vector<int> ex(L.cout, 0);
-            for (int n = 0; n < L.cout; ++n) {
-                float mx = 0.f;
-                for (int t = 0; t < ntap; ++t)
-                    for (int c = 0; c < L.cin; ++c) mx = std::max(mx, std::fabs(kernel[((size_t)t * L.cin + c) * L.cout + n]));
-                int e2 = 0;
-                if (mx > 0.f) (void)std::frexp(mx, &e2);   // mx = f 2^e2, f in [0.5, 1)
-                ex[n] = mx > 0.f ? 15 - e2 : 0;              // max|w| 2^e in [2^14, 2^15)
-                scale_h[n] = std::ldexp(scale_h[n], -ex[n]);
-            }
-            auto wsc = [&](int n, float v) { return std::ldexp(sgn[n] * v, ex[n]); };
-            std::vector<uint16_t> sp;
-            if (G.halo == HALO_V1P) {
-                // conv_v1r.hip k_conv_v1p: [piece h / l][K-slice s][Cout][32]; k-group g = 4 s + kg (8 k each):
-                //   s = 0..2, kg = ky (0..3), and s = 3, kg = s' (0..2) for ky = 4, of type s' / s:
-                //   0: kx 0, 1 x frames 0..3;  1: kx 2, 3 x frames 0..3;  2: kx 4 x frames 0..3, then kx 0..3 x frame 4;
-                //   s = 3, kg = 3: (ky 0..4, kx 4) x frame 4, three zeros
-                const size_t img = (size_t)4 * L.cout * 32;
-                sp.assign(2 * img, 0);
-                auto wt = [&](int n, int ky, int kx, int f) { return wsc(n, kernel[((size_t)(ky * 5 + kx) * 5 + f) * L.cout + n]); };
-                for (int g = 0; g < 16; ++g)
-                    for (int n = 0; n < L.cout; ++n)
-                        for (int j = 0; j < 8; ++j) {
-                            const int sl = g >> 2, kg = g & 3;
-                            const int t = sl < 3 ? sl : kg, ky = sl < 3 ? kg : 4;
-                            float v = 0.f;
-                            if (t == 0) v = wt(n, ky, j >> 2, j & 3);
-                            else if (t == 1) v = wt(n, ky, 2 + (j >> 2), j & 3);
-                            else if (t == 2) v = j < 4 ? wt(n, ky, 4, j) : wt(n, ky, j - 4, 4);
-                            else if (j < 5) v = wt(n, j, 4, 4);
-                            const uint16_t h = f2h(v);
-                            const size_t o = ((size_t)(g >> 2) * L.cout + n) * 32 + (g & 3) * 8 + j;
-                            sp[o] = h;
-                            sp[img + o] = f2h(v - h2f(h));
-                        }
-            } else if (G.halo == HALO_V1) {
-                // conv_v1r.hip k_conv_v1s: [piece h / l][kernel row ky][Cout][32], k = kx * 6 + frame
-                const size_t img = (size_t)L.kh * L.cout * 32;
-                sp.assign(2 * img, 0);
-                for (int ky = 0; ky < L.kh; ++ky)
-                    for (int n = 0; n < L.cout; ++n)
-                        for (int kx = 0; kx < L.kw; ++kx)
-                            for (int f = 0; f < L.cin; ++f) {
-                                const float v = wsc(n, kernel[((size_t)(ky * L.kw + kx) * L.cin + f) * L.cout + n]);
-                                const uint16_t h = f2h(v);
-                                const size_t o = ((size_t)ky * L.cout + n) * 32 + kx * 6 + f;
-                                sp[o] = h;
-                                sp[img + o] = f2h(v - h2f(h));
-                            }
-            } else {
-                // conv_stream.hip (S16): slice = chunk * KS^2 + tap over 16-channel chunks; row n = [Bh(16) | Bl(16)]
-                const int nsteps = (L.cin / 16) * ntap;
-                sp.assign((size_t)nsteps * L.cout * 32, 0);
-                for (int st = 0; st < nsteps; ++st)
-                    for (int n = 0; n < L.cout; ++n)
-                        for (int kk = 0; kk < 16; ++kk) {
-                            const int tap = st % ntap, c = (st / ntap) * 16 + kk;
-                            const float v = wsc(n, kernel[((size_t)tap * L.cin + c) * L.cout + n]);
-                            const uint16_t h = f2h(v);
-                            sp[((size_t)st * L.cout + n) * 32 + kk] = h;
-                            sp[((size_t)st * L.cout + n) * 32 + 16 + kk] = f2h(v - h2f(h));
-                        }
-            }
-            if ((rc = upload(W, scale_h, &G.scale_h))) return rc;
-            uint16_t* d;
-            if ((rc = upload(W, sp, &d))) return rc;
-            G.w_halo = d;
-            return 0;
-        }
-        if ((rc = upload(W, scale_h, &G.scale_h))) return rc;
-        std::vector<uint16_t> hp;
-        if (G.halo == HALO_V1) {
-            // conv_v1r.hip: slice ky, k = kx * 6 + frame (k = 30, 31 zero; frame 5 too with 5 frames)
-            hp.assign((size_t)L.kh * L.cout * 32, 0);
-            for (int ky = 0; ky < L.kh; ++ky)
-                for (int n = 0; n < L.cout; ++n)
-                    for (int kx = 0; kx < L.kw; ++kx)
-                        for (int f = 0; f < L.cin; ++f)
-                            hp[((size_t)ky * L.cout + n) * 32 + kx * 6 + f] =
-                                f2bf(sgn[n] * kernel[((size_t)(ky * L.kw + kx) * L.cin + f) * L.cout + n]);
-        } else {
-            const int nsteps = (L.cin / 128) * 4 * ntap;   // (4 chunks of 32 channels per 128) x taps
-            hp.assign((size_t)nsteps * L.cout * 32, 0);
-            for (int st = 0; st < nsteps; ++st)
-                for (int n = 0; n < L.cout; ++n)
-                    for (int kk = 0; kk < 32; ++kk) {
-                        const int tap = st % ntap, chunk = st / ntap;   // chunk = cg*4 + cc
-                        const int c = chunk * 32 + kk;
-                        hp[((size_t)st * L.cout + n) * 32 + kk] =
-                            f2bf(sgn[n] * kernel[((size_t)tap * L.cin + c) * L.cout + n]);
-                    }
-        }
-        uint16_t* d;
-        if ((rc = upload(W, hp, &d))) return rc;
-        G.w_halo = d;
-    }
+    if ((rc = up(P.w32, &w32)) || (rc = up(P.w16, &w16)) || (rc = up(P.w_halo, &w_halo)) || (rc = up(P.w_dense, &w_dense)) ||
+        (rc = up(P.w_f32, &G.w_f32)) || (rc = up(P.scale, &G.scale)) || (rc = up(P.shift, &G.shift)) ||
+        (rc = up(P.scale_h, &G.scale_h)) || (rc = up(taps, &dtaps)))
+        return rc;
+    G.w = w32 ? (void*)w32 : (void*)w16;
+    G.w_halo = w_halo;
+    G.w_dense = w_dense;
+    G.taps = reinterpret_cast<int2*>(dtaps);
     return 0;
 }
 

@@ -26,7 +26,7 @@
 //   * the input window streams per 32-channel chunk through 3 LDS slots of 64-byte pixel rows: chunk g+2
 //     arrives while chunk g computes, across tile boundaries too.
 //
-// K order per tile: slice = chunk * KS^2 + tap, chunk = 32 input channels (host packing in capi.hip,
+// K order per tile: slice = chunk * KS^2 + tap, chunk = 32 input channels (host packing in weight_pack.cpp,
 // [slice][Cout][32] bf16).  M order: a 32-row MFMA block is 4 x 8 conv pixels; rows 4q..4q+3 are 2x2
 // pool window q, and a lane's accumulator registers 4g..4g+3 are four such rows, so BN scale/shift,
 // max pool and LeakyReLU happen in registers.

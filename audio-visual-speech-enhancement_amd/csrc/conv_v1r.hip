@@ -704,7 +704,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
 //   R  at 160: x (0..15): frame 4 of pixels x .. x + 3 of the row           (8 B)
 //   S0 at 288: x (0..15), rows y' < 16: frame 4 of pixels (y' .. y' + 3, x + 4)
 //   S1 at 416: x (0..15), rows y' < 16: frame 4 of pixel (y' + 4, x + 4), three zeros
-// and the groups, g = 4 slice + kg (kg = lane >> 4; the B image's k order, capi.hip build_layer HALO_V1P):
+// and the groups, g = 4 slice + kg (kg = lane >> 4; the B image's k order, weight_pack.cpp pack_v1p):
 //   slice 0, kg = ky (0..3): P(py + ky, px), P(py + ky, px + 1)        kx 0, 1 x frames 0..3
 //   slice 1, kg = ky:        P(py + ky, px + 2), P(py + ky, px + 3)    kx 2, 3 x frames 0..3
 //   slice 2, kg = ky:        P(py + ky, px + 4), R(py + ky, px)        kx 4 x frames 0..3, then kx 0..3 x frame 4

@@ -41,8 +41,8 @@ __device__ __forceinline__ i32x4 lds16(const char* p) { return *reinterpret_cast
 // ABL: timing ablations (0 in the library; tools/gemm_ablate.hip, AVSE_GEMM_ABL variant libraries): 1 = the tile's
 // last workgroup skips reading the other partials, 2 = S16: no global loads, 4 = S16: no MFMAs (outputs meaningless)
 // S16: AVSE_F32_SPLIT operands (DESIGN.md §3 split-f16).  A slab row is 16 k as [h(16) | l(16)] f16 (the same 64 B
-// as 32 bf16 k), activations in the split-pair layout and weights packed [Wh(16) | Wl(16)] per 16 k (capi.hip
-// build_layer, k_conv's packing); per slab two v_mfma_f32_16x16x32_f16, [Ah | Al] x [Wh | Wh] and [Ah | Al] x [Wl | Wl]
+// as 32 bf16 k), activations in the split-pair layout and weights packed [Wh(16) | Wl(16)] per 16 k (weight_pack.cpp
+// pack_layer, k_conv's packing); per slab two v_mfma_f32_16x16x32_f16, [Ah | Al] x [Wh | Wh] and [Ah | Al] x [Wl | Wl]
 // (every lane of a W fragment reads k-group kg & 1 of the h or the l half): all four products.  Sums are blocked as
 // k_conv's (kFp32Block slabs summed from zero, then added to the running sum in order) and split-K splits hold
 // whole blocks (GemmArgs::slabs_per_split), so a split plan fixed by K and N (dense) or one block per split (v_conv6)

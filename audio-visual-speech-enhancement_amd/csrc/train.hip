@@ -778,23 +778,18 @@ struct TLayer {
     LayerDef L;
     int cin_pad = 0;          // channel stride of this layer's input tensor
     int hq = 1, wq = 1;       // conv output grid (full resolution)
-    int ho = 1, wo = 1;       // after pool
     long long o_k = 0, o_b = 0, o_g = -1, o_be = -1, o_mm = -1, o_mv = -1;   // canonical blob offsets
-    // forward conv (k_conv), packed [phase][cout][kpad] gathered from the blob
-    int nphase = 1;
-    ConvPhase ph[MAX_PHASES];
-    std::vector<int2> taps;
-    long long fw_off = 0;     // offset in the forward packed buffer
+    // forward conv and input gradient (k_conv): geometry (layer_geom.h) and the offsets of their weights, packed
+    // [phase][rows][kpad] from the blob, in the trainer's wfwd / wdg
+    LayerGeom fw;
+    long long fw_off = 0;
     int2* d_taps = nullptr;
-    // dgrad
     bool dgrad = false;
-    int dg_nphase = 1, dg_hq = 1, dg_wq = 1, dg_sy = 1, dg_sx = 1, dg_oys = 1, dg_oxs = 1, dg_ci = 0;
-    ConvPhase dg_ph[MAX_PHASES];
-    std::vector<int2> dg_taps;
+    DgradGeom dg;
     long long dg_off = 0;
     int2* d_dg_taps = nullptr;
     // wgrad taps (dy, dx) per Keras tap ky * kw + kx
-    std::vector<int2> wg_taps;
+    std::vector<Tap> wg_taps;
     int2* d_wg_taps = nullptr;
     // tensors
     float* in = nullptr;      // this layer's input [N][hin][win][cin_pad] (or a concat view)
@@ -810,6 +805,9 @@ struct TLayer {
 }  // namespace avse
 
 using namespace avse;
+
+static_assert(sizeof(Tap) == sizeof(int2) && offsetof(Tap, dy) == offsetof(int2, x) && offsetof(Tap, dx) == offsetof(int2, y),
+              "Tap must be layout-compatible with int2 (the tap tables are uploaded as they are)");
 
 struct avse_trainer {
     int device = 0;
@@ -852,15 +850,6 @@ int talloc(avse_trainer* t, T** p, size_t count) {
     return 0;
 }
 
-long long kpad_of(int ntaps, int cp) { return ((long long)ntaps * cp + 31) / 32 * 32; }
-
-// Keras kernel element index for (ky, kx, in-channel c_in, out-channel c_out) of layer L
-long long kidx(const LayerDef& L, int ky, int kx, int ci, int co) {
-    if (L.kind == DENSE) return (long long)ci * L.cout + co;
-    if (L.kind == CONV) return (((long long)ky * L.kw + kx) * L.cin + ci) * L.cout + co;
-    return (((long long)ky * L.kw + kx) * L.cout + co) * L.cin + ci;   // transposed conv (kh, kw, cout, cin)
-}
-
 // k_pack tiles of one (layer, phase, tap) block: rows x cols, dst row stride dld, source element (r, c) at
 // src + r sr + c sc (Keras kernel strides from kidx)
 void add_pack_tiles(std::vector<PackTile>& v, int which, long long dst, int dld, long long src, long long sr, long long sc,
@@ -887,6 +876,21 @@ int check_pack_tiles(const std::vector<PackTile>& v, int which, const std::vecto
     return 0;
 }
 
+// appends one layer's gather map (blob indices; layer_geom.h gather_map) and the k_pack tiles of each (phase, tap):
+// rows x reduction channels, read at the Keras kernel's strides
+void append_packing(std::vector<int>& map, std::vector<PackTile>& tiles, int which, long long o_k, const LayerDef& L,
+                    const PhaseSet& g) {
+    const long long base = (long long)map.size();
+    for (int v : gather_map(L, g)) map.push_back(v < 0 ? -1 : (int)(o_k + v));
+    for (int p = 0; p < g.nphase; ++p)
+        for (size_t j = 0; j < g.kyx[p].size(); ++j) {
+            const int ky = g.kyx[p][j].first, kx = g.kyx[p][j].second;
+            const long long s0 = kidx(L, ky, kx, 0, 0), s_ci = kidx(L, ky, kx, 1, 0) - s0, s_co = kidx(L, ky, kx, 0, 1) - s0;
+            add_pack_tiles(tiles, which, base + g.ph[p].w_off + (long long)j * g.cp, g.ph[p].kpad, o_k + s0,
+                           g.dgrad ? s_ci : s_co, g.dgrad ? s_co : s_ci, g.rows, g.red);
+        }
+}
+
 int build_plan(avse_trainer* t, const float* host_blob) {
     t->layers.resize(kNumLayers);
     long long off = 0;
@@ -896,7 +900,6 @@ int build_plan(avse_trainer* t, const float* host_blob) {
         TLayer& T = t->layers[i];
         const LayerDef& L = t->plan.L[i];
         T.L = L;
-        T.cin_pad = (L.kind == DENSE) ? L.cin : ((L.cin + 7) / 8) * 8;
         T.o_k = off;
         off += (long long)L.kh * L.kw * L.cin * L.cout;
         T.o_b = off;
@@ -905,152 +908,24 @@ int build_plan(avse_trainer* t, const float* host_blob) {
             T.o_g = off; T.o_be = off + L.bn_channels; T.o_mm = off + 2 * L.bn_channels; T.o_mv = off + 3 * L.bn_channels;
             off += 4LL * L.bn_channels;
         }
-        const int pt = (L.kind == CONV) ? same_pad_before(L.hin, L.kh, L.sh) : std::max(L.kh - L.sh, 0) / 2;
-        const int pl = (L.kind == CONV) ? same_pad_before(L.win, L.kw, L.sw) : std::max(L.kw - L.sw, 0) / 2;
-        // ---- forward phases / taps (as capi.hip build_layer) ----
-        std::vector<std::vector<std::pair<int, int>>> ptaps;
-        if (L.kind == DENSE) {
-            T.nphase = 1;
-            ptaps.push_back({{0, 0}});
-            T.taps.push_back(make_int2(0, 0));
-            T.ph[0] = ConvPhase{0, 0, 1, 0, 0, 0};
-        } else if (L.kind == CONV) {
-            T.hq = same_out(L.hin, L.sh);
-            T.wq = same_out(L.win, L.sw);
-            T.nphase = 1;
-            std::vector<std::pair<int, int>> pl_;
-            for (int ky = 0; ky < L.kh; ++ky)
-                for (int kx = 0; kx < L.kw; ++kx) {
-                    pl_.push_back({ky, kx});
-                    T.taps.push_back(make_int2(ky - pt, kx - pl));
-                }
-            ptaps.push_back(pl_);
-            T.ph[0] = ConvPhase{0, 0, (int)pl_.size(), 0, 0, 0};
-        } else {
-            T.hq = L.hin * L.sh;
-            T.wq = L.win * L.sw;
-            T.nphase = L.sh * L.sw;
-            if (T.nphase > MAX_PHASES) return tfail(AVSE_ERR_UNSUPPORTED, "deconv stride too large");
-            for (int py = 0; py < L.sh; ++py)
-                for (int px = 0; px < L.sw; ++px) {
-                    std::vector<std::pair<int, int>> pl_;
-                    const int toff = (int)T.taps.size();
-                    for (int ky = 0; ky < L.kh; ++ky) {
-                        const int ry = py + pt - ky;
-                        if (((ry % L.sh) + L.sh) % L.sh) continue;
-                        for (int kx = 0; kx < L.kw; ++kx) {
-                            const int rx = px + pl - kx;
-                            if (((rx % L.sw) + L.sw) % L.sw) continue;
-                            pl_.push_back({ky, kx});
-                            T.taps.push_back(make_int2(ry / L.sh, rx / L.sw));
-                        }
-                    }
-                    T.ph[py * L.sw + px] = ConvPhase{py, px, (int)pl_.size(), 0, 0, toff};
-                    ptaps.push_back(pl_);
-                }
-        }
-        T.ho = L.pool ? T.hq / 2 : T.hq;
-        T.wo = L.pool ? T.wq / 2 : T.wq;
+        // ---- forward: geometry, the gather map and the k_pack tiles that must reproduce it ----
+        T.fw = layer_geom(L);
+        if (T.fw.status != GEOM_OK) return tfail(AVSE_ERR_UNSUPPORTED, geom_message(T.fw.status));
+        T.cin_pad = T.fw.cin_pad;
+        T.hq = T.fw.hz;
+        T.wq = T.fw.wz;
         T.fw_off = (long long)mf.size();
-        long long woff = 0;
-        for (int p = 0; p < T.nphase; ++p) {
-            const int cp = T.cin_pad;
-            const long long kp = kpad_of((int)ptaps[p].size(), cp);
-            T.ph[p].kpad = (int)kp;
-            T.ph[p].w_off = woff;
-            const size_t base = mf.size();
-            mf.resize(base + (size_t)(L.cout * kp), -1);
-            for (int n = 0; n < L.cout; ++n)
-                for (size_t j = 0; j < ptaps[p].size(); ++j)
-                    for (int c = 0; c < L.cin; ++c)
-                        mf[base + (size_t)n * kp + j * cp + c] =
-                            (int)(T.o_k + kidx(L, ptaps[p][j].first, ptaps[p][j].second, c, n));
-            for (size_t j = 0; j < ptaps[p].size(); ++j) {
-                const int ky = ptaps[p][j].first, kx = ptaps[p][j].second;
-                const long long s0 = kidx(L, ky, kx, 0, 0);
-                add_pack_tiles(tiles, 0, (long long)base + (long long)j * cp, (int)kp, T.o_k + s0,
-                               kidx(L, ky, kx, 0, 1) - s0, kidx(L, ky, kx, 1, 0) - s0, L.cout, L.cin);
-            }
-            woff += (long long)L.cout * kp;
-        }
+        append_packing(mf, tiles, 0, T.o_k, L, T.fw);
         // ---- weight-gradient taps: Keras tap order, offsets (ky - pt, kx - pl) on the strided grid ----
         for (int ky = 0; ky < L.kh; ++ky)
-            for (int kx = 0; kx < L.kw; ++kx) T.wg_taps.push_back(make_int2(ky - (L.kind == DENSE ? 0 : pt), kx - (L.kind == DENSE ? 0 : pl)));
+            for (int kx = 0; kx < L.kw; ++kx) T.wg_taps.push_back(Tap{ky - T.fw.pt, kx - T.fw.pl});
         // ---- dgrad: not for the first layer of a branch (its input is data) ----
         T.dgrad = !(i == 0 || std::strcmp(L.name, "v_conv1") == 0);
         if (T.dgrad) {
-            const int cpi = (L.cout % 8) ? ((L.cout + 7) / 8) * 8 : L.cout;   // dz channel stride (d_deconv6: 8)
-            T.dg_ci = (L.kind == DENSE) ? L.cout : cpi;
-            std::vector<std::vector<std::pair<int, int>>> dtaps;
-            if (L.kind == DENSE) {
-                T.dg_nphase = 1;
-                dtaps.push_back({{0, 0}});
-                T.dg_taps.push_back(make_int2(0, 0));
-                T.dg_ph[0] = ConvPhase{0, 0, 1, 0, 0, 0};
-            } else if (L.kind == CONV) {
-                // dx[iy], iy = q s + r: taps ky = r + pt (mod s), dz row q + (r + pt - ky) / s
-                if (L.hin % L.sh || L.win % L.sw) return tfail(AVSE_ERR_UNSUPPORTED, "conv dgrad needs input dims divisible by the stride");
-                T.dg_nphase = L.sh * L.sw;
-                T.dg_hq = L.hin / L.sh;
-                T.dg_wq = L.win / L.sw;
-                T.dg_oys = L.sh;
-                T.dg_oxs = L.sw;
-                for (int ry = 0; ry < L.sh; ++ry)
-                    for (int rx = 0; rx < L.sw; ++rx) {
-                        std::vector<std::pair<int, int>> pl_;
-                        const int toff = (int)T.dg_taps.size();
-                        for (int ky = 0; ky < L.kh; ++ky) {
-                            const int dy = ry + pt - ky;
-                            if (((dy % L.sh) + L.sh) % L.sh) continue;
-                            for (int kx = 0; kx < L.kw; ++kx) {
-                                const int dx = rx + pl - kx;
-                                if (((dx % L.sw) + L.sw) % L.sw) continue;
-                                pl_.push_back({ky, kx});
-                                T.dg_taps.push_back(make_int2(dy / L.sh, dx / L.sw));
-                            }
-                        }
-                        if (pl_.empty()) return tfail(AVSE_ERR_UNSUPPORTED, "conv dgrad phase without taps");
-                        T.dg_ph[ry * L.sw + rx] = ConvPhase{ry, rx, (int)pl_.size(), 0, 0, toff};
-                        dtaps.push_back(pl_);
-                    }
-            } else {
-                // transposed conv: din[iy] = sum_ky dout[iy s + ky - pt] W[ky] (a strided conv of dout)
-                T.dg_nphase = 1;
-                T.dg_hq = L.hin;
-                T.dg_wq = L.win;
-                T.dg_sy = L.sh;
-                T.dg_sx = L.sw;
-                std::vector<std::pair<int, int>> pl_;
-                for (int ky = 0; ky < L.kh; ++ky)
-                    for (int kx = 0; kx < L.kw; ++kx) {
-                        pl_.push_back({ky, kx});
-                        T.dg_taps.push_back(make_int2(ky - pt, kx - pl));
-                    }
-                dtaps.push_back(pl_);
-                T.dg_ph[0] = ConvPhase{0, 0, (int)pl_.size(), 0, 0, 0};
-            }
+            T.dg = dgrad_geom(L);
+            if (T.dg.status != GEOM_OK) return tfail(AVSE_ERR_UNSUPPORTED, geom_message(T.dg.status));
             T.dg_off = (long long)md.size();
-            long long doff = 0;
-            for (int p = 0; p < T.dg_nphase; ++p) {
-                const int cp = T.dg_ci;
-                const long long kp = kpad_of((int)dtaps[p].size(), cp);
-                T.dg_ph[p].kpad = (int)kp;
-                T.dg_ph[p].w_off = doff;
-                const size_t base = md.size();
-                md.resize(base + (size_t)(L.cin * kp), -1);
-                for (int n = 0; n < L.cin; ++n)          // output channel of dgrad = the layer's input channel
-                    for (size_t j = 0; j < dtaps[p].size(); ++j)
-                        for (int c = 0; c < L.cout; ++c)   // reduction channel = the layer's output channel
-                            md[base + (size_t)n * kp + j * cp + c] =
-                                (int)(T.o_k + kidx(L, dtaps[p][j].first, dtaps[p][j].second, n, c));
-                for (size_t j = 0; j < dtaps[p].size(); ++j) {
-                    const int ky = dtaps[p][j].first, kx = dtaps[p][j].second;
-                    const long long s0 = kidx(L, ky, kx, 0, 0);
-                    add_pack_tiles(tiles, 1, (long long)base + (long long)j * cp, (int)kp, T.o_k + s0,
-                                   kidx(L, ky, kx, 1, 0) - s0, kidx(L, ky, kx, 0, 1) - s0, L.cin, L.cout);
-                }
-                doff += (long long)L.cin * kp;
-            }
+            append_packing(md, tiles, 1, T.o_k, L, T.dg);
         }
     }
     if (off != blob_floats(t->plan)) return tfail(AVSE_ERR_INVALID, "trainer plan / blob size mismatch");
@@ -1065,13 +940,13 @@ int build_plan(avse_trainer* t, const float* host_blob) {
     if (int rc = talloc(t, &t->wdg, md.size())) return rc;
     AVSE_HIP_CHECK(hipMemcpy(t->pack_tiles, tiles.data(), tiles.size() * sizeof(PackTile), hipMemcpyHostToDevice));
     for (auto& T : t->layers) {
-        if (int rc = talloc(t, &T.d_taps, T.taps.size())) return rc;
-        AVSE_HIP_CHECK(hipMemcpy(T.d_taps, T.taps.data(), T.taps.size() * sizeof(int2), hipMemcpyHostToDevice));
+        if (int rc = talloc(t, &T.d_taps, T.fw.taps.size())) return rc;
+        AVSE_HIP_CHECK(hipMemcpy(T.d_taps, T.fw.taps.data(), T.fw.taps.size() * sizeof(int2), hipMemcpyHostToDevice));
         if (int rc = talloc(t, &T.d_wg_taps, T.wg_taps.size())) return rc;
         AVSE_HIP_CHECK(hipMemcpy(T.d_wg_taps, T.wg_taps.data(), T.wg_taps.size() * sizeof(int2), hipMemcpyHostToDevice));
         if (T.dgrad) {
-            if (int rc = talloc(t, &T.d_dg_taps, T.dg_taps.size())) return rc;
-            AVSE_HIP_CHECK(hipMemcpy(T.d_dg_taps, T.dg_taps.data(), T.dg_taps.size() * sizeof(int2), hipMemcpyHostToDevice));
+            if (int rc = talloc(t, &T.d_dg_taps, T.dg.taps.size())) return rc;
+            AVSE_HIP_CHECK(hipMemcpy(T.d_dg_taps, T.dg.taps.data(), T.dg.taps.size() * sizeof(int2), hipMemcpyHostToDevice));
         }
     }
     // parameters, gradients, Adam moments
@@ -1219,9 +1094,9 @@ ConvArgs fwd_args(avse_trainer* t, const TLayer& T, int64_t N) {
     a.out_c_off = 0;
     a.pool = 0;
     a.act = 0;
-    a.nphase = T.nphase;
+    a.nphase = T.fw.nphase;
     a.ksplit = 1;
-    for (int p = 0; p < T.nphase; ++p) a.ph[p] = T.ph[p];
+    for (int p = 0; p < T.fw.nphase; ++p) a.ph[p] = T.fw.ph[p];
     return a;
 }
 
@@ -1238,14 +1113,14 @@ ConvArgs dgrad_args(avse_trainer* t, const TLayer& T, const float* dz, int64_t N
     a.N = (int)N;
     a.Hi = T.hq;
     a.Wi = T.wq;
-    a.Ci = T.dg_ci;
+    a.Ci = T.dg.ci;
     a.in_clip_stride = (long long)T.hq * T.wq * T.zc;
-    a.Hq = (L.kind == DENSE) ? 1 : T.dg_hq;
-    a.Wq = (L.kind == DENSE) ? 1 : T.dg_wq;
-    a.sy = T.dg_sy;
-    a.sx = T.dg_sx;
-    a.oys = T.dg_oys;
-    a.oxs = T.dg_oxs;
+    a.Hq = (L.kind == DENSE) ? 1 : T.dg.hq;
+    a.Wq = (L.kind == DENSE) ? 1 : T.dg.wq;
+    a.sy = T.dg.sy;
+    a.sx = T.dg.sx;
+    a.oys = T.dg.oys;
+    a.oxs = T.dg.oxs;
     a.Ho = L.hin;
     a.Wo = L.win;
     a.Co = L.cin;
@@ -1254,9 +1129,9 @@ ConvArgs dgrad_args(avse_trainer* t, const TLayer& T, const float* dz, int64_t N
     a.out_c_off = 0;
     a.pool = 0;
     a.act = 0;
-    a.nphase = T.dg_nphase;
+    a.nphase = T.dg.nphase;
     a.ksplit = 1;
-    for (int p = 0; p < T.dg_nphase; ++p) a.ph[p] = T.dg_ph[p];
+    for (int p = 0; p < T.dg.nphase; ++p) a.ph[p] = T.dg.ph[p];
     return a;
 }
 

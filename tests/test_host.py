@@ -249,7 +249,7 @@ def test_range_set_aside_keeps_earlier_bits():
 
 def test_concat_exponent_mismatch_is_flagged_at_load():
     """a_conv5 / v_conv6 share the smaller activation exponent; a model whose halves want different ones is
-    flagged when float32_split weights are built (the rule restated from csrc/capi.hip act_exponents)."""
+    flagged when float32_split weights are built (the rule restated from csrc/weight_pack.cpp act_exponents)."""
     import warnings
     from avse_amd import ops
     from avse_amd.model import KerasModel
