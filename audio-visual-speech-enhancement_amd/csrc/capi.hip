@@ -151,6 +151,7 @@ const OptionName kOptionNames[] = {
     {"no_v1p", "AVSE_NO_V1P", &Options::no_v1p},
     {"no_a1valu", "AVSE_NO_A1VALU", &Options::no_a1valu},
     {"no_planar", "AVSE_NO_PLANAR", &Options::no_planar},
+    {"four_products", "AVSE_FOUR_PRODUCTS", &Options::four_products},
     {"side_prio", "AVSE_SIDE_PRIO", &Options::side_prio},
 };
 
@@ -554,8 +555,8 @@ int avse_ctx_create(int device, avse_ctx** out) {
         if (e && *e) c->opt.*(o.field) = std::atoi(e);
     }
     if (hipMalloc((void**)&c->mse_partial, sizeof(float) * 256) != hipSuccess ||
-        hipMalloc((void**)&c->gemm_counters, sizeof(int) * 8192) != hipSuccess ||
-        hipMemset(c->gemm_counters, 0, sizeof(int) * 8192) != hipSuccess ||
+        hipMalloc((void**)&c->gemm_counters, sizeof(int) * kGemmCounters) != hipSuccess ||
+        hipMemset(c->gemm_counters, 0, sizeof(int) * kGemmCounters) != hipSuccess ||
         hipMalloc((void**)&c->range, sizeof(unsigned) * 4) != hipSuccess ||
         hipMemset(c->range, 0, sizeof(unsigned) * 4) != hipSuccess ||
         hipHostMalloc((void**)&c->range_host, sizeof(unsigned) * 4, hipHostMallocDefault) != hipSuccess) {
@@ -936,6 +937,8 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
         }
         g.partial = reinterpret_cast<float*>(c->arena + part_off);
         g.counters = c->gemm_counters;
+        g.counters_cap = kGemmCounters;
+        g.four_products = opt.four_products;
         return launch_gemm(g, mode, s);
     };
     // dense layers / v_conv6: split-K when the grid is small, partials at the split-K offset of the arena layout the
@@ -1132,23 +1135,19 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
     }
     if (concurrent) AVSE_HIP_CHECK(hipStreamWaitEvent(s, c->join, 0));
     // fusion + decoder dense (network.py:53-58, :66-78)
-    if (use_gemm) {
-        if ((rc = gemm(L(11), buf(B_CAT), CAT, buf(B_E1), EMB, 0, 0, N, off[B_COUNT], 11)) || (rc = mark())) return rc;
-        if ((rc = gemm(L(12), buf(B_E1), EMB, buf(B_E2), EMB, 0, 0, N, off[B_COUNT], 12)) || (rc = mark())) return rc;
-        if ((rc = gemm(L(13), buf(B_E2), EMB, buf(B_E3), AEMB, 0, 0, N, off[B_COUNT], 13)) || (rc = mark())) return rc;
-    } else {
-        ConvArgs a = conv_args(L(11), buf(B_CAT), CAT, buf(B_E1), EMB, EMB, 0, N);
-        ksplit(a, off[B_COUNT]);
-        int dti = pairs(a, true, true, 11);
-        if ((rc = launch_conv(a, split ? dti : cdt, s)) || (rc = mark())) return rc;
-        a = conv_args(L(12), buf(B_E1), EMB, buf(B_E2), EMB, EMB, 0, N);
-        ksplit(a, off[B_COUNT]);
-        dti = pairs(a, true, true, 12);
-        if ((rc = launch_conv(a, split ? dti : cdt, s)) || (rc = mark())) return rc;
-        a = conv_args(L(13), buf(B_E2), EMB, buf(B_E3), AEMB, AEMB, 0, N);
-        ksplit(a, off[B_COUNT]);
-        dti = pairs(a, true, true, 13);
-        if ((rc = launch_conv(a, split ? dti : cdt, s)) || (rc = mark())) return rc;
+    const struct { int li, in, out; long long lda, ldo; } dense[3] = {
+        {11, B_CAT, B_E1, CAT, EMB}, {12, B_E1, B_E2, EMB, EMB}, {13, B_E2, B_E3, EMB, AEMB}};
+    for (const auto& d : dense) {
+        // k_gemm, or k_conv + split-K reduce: Options::no_gemm, or a split launch with more tiles than k_gemm has
+        // split-K tickets (launch_gemm returns -1)
+        rc = use_gemm ? gemm(L(d.li), buf(d.in), d.lda, buf(d.out), d.ldo, 0, 0, N, off[B_COUNT], d.li) : -1;
+        if (rc == -1) {
+            ConvArgs a = conv_args(L(d.li), buf(d.in), d.lda, buf(d.out), d.ldo, d.ldo, 0, N);
+            ksplit(a, off[B_COUNT]);
+            const int dti = pairs(a, true, true, d.li);
+            rc = launch_conv(a, split ? dti : cdt, s);
+        }
+        if (rc || (rc = mark())) return rc;
     }
     // audio decoder (network.py:112-135)
     const int d_in[6] = {B_E3, B_D1, B_D2, B_D3, B_D4, B_D5};
@@ -1193,6 +1192,7 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
             DecTailArgs da = dec_tail_args(L(17), L(18), W, buf(d_in[3]), out, N);
             da.range_flag = rflag;
             da.range_bit = 1u << 17;
+            da.four_products = opt.four_products;
             if (dec_tail_s16_supported(da)) {
                 if ((rc = launch_dec_tail_s16(da, s)) || (rc = mark()) || (rc = mark())) return rc;   // d4, d5 stages
                 break;

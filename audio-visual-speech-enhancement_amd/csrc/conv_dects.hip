@@ -27,6 +27,16 @@
 //   * d_deconv5 walks its four stride phases (4 / 6 / 6 / 9 taps x 4 chunks; every phase a whole number of ring groups)
 //     with immediate tap offsets; each phase's epilogue folds BN, LeakyReLU and d_deconv6's 64 -> 1 dot: 4 channels
 //     in-lane, the lane rows by two xor shuffles, the four channel blocks (waves) through LDS in a fixed order.
+//   * PR (planar slab pairs, the default; DecTailArgs::four_products selects the slab-by-slab form above): two
+//     consecutive slabs as one 32-deep operand per half, W'h = [Wh(t) | Wh(t+1)], W'l, A'h = [Ah(t) | Ah(t+1)], A'l
+//     (lanes of k-groups 0, 1 read slab t, 2, 3 slab t + 1; 16-B groups kg & 1 of the h half, 2 + (kg & 1) of the l
+//     half: every distinct operand byte once, no lane exchange), and three MFMAs per fragment and pair, W'h x A'l,
+//     W'h x A'h, W'l x A'h (Wl x Al <= 2^-22 |w a| is dropped, as in the stream convolutions).  d_deconv4 pairs taps
+//     t, t + 1 of one chunk (horizontally adjacent: the wave's upper half reads one pixel pitch lower in the window),
+//     d_deconv5 chunks c, c + 1 of one tap (+ 64 B in the image pixel); every phase and every 8-slab summation block is
+//     a whole number of pairs.  Per wave and pair 16 ds_read_b128 for 21 MFMAs (slab by slab: 18 for 28).  The lane
+//     groups' addresses are the slab-by-slab ones moved by a constant (one pixel pitch, 64 B, a ring slab), so the
+//     pitches stay bank-conflict free (tools/lds_swizzle_search.py --tail).
 #include <cstdlib>
 #include <utility>
 
@@ -37,9 +47,9 @@ namespace {
 
 // timing ablations (tools/_ab variant libraries only; 0 in the library): 1 = no MFMAs (fragment reads kept alive),
 // 2 = no fragment reads in the loops (MFMAs on the prologue's fragments), 4 = no barriers in the loops.  Measured
-// (profiles/r06c_split_tail_ablate.txt, B = 512): full 0.335 ms, 1: 0.188, 2: 0.306, 4: 0.326.  Also measured and
-// not kept: the stream kernels' three-product slab pairs (Wl Al dropped, A' by v_permlane32_swap): 0.343 vs 0.335 ms
-// (the tail is not MFMA-issue-bound: 14 MFMAs per slab per wave, ~54 % MFMA busy)
+// (profiles/r06c_split_tail_ablate.txt, B = 512, the slab-by-slab form): full 0.335 ms, 1: 0.188, 2: 0.306, 4: 0.326.
+// Also measured and not kept: three-product slab pairs with A' built by v_permlane32_swap: 0.343 vs 0.335 ms (the swaps
+// cost what the MFMAs saved; the planar pairs below, PR, need none)
 #ifndef AVSE_DECTS_ABL
 #define AVSE_DECTS_ABL 0
 #endif
@@ -74,6 +84,7 @@ constexpr int ph_woff(int p) { int s = 0; for (int q = 0; q < p; ++q) s += CO * 
 constexpr int ph_gstart(int p) { int s = 0; for (int q = 0; q < p; ++q) s += 4 * ph_nt(q); return s; }      // slabs
 constexpr int ph_of(int g) { int p = 0; while (p < 3 && g >= ph_gstart(p + 1)) ++p; return p; }
 static_assert(ph_gstart(4) % 4 == 0 && (4 * ph_nt(0)) % 4 == 0, "every phase is whole ring groups");
+static_assert(ph_gstart(1) % 2 == 0 && ph_gstart(2) % 2 == 0 && ph_gstart(3) % 2 == 0, "every phase is whole slab pairs");
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
     const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
@@ -100,6 +111,7 @@ __device__ __forceinline__ void unroll(std::integer_sequence<int, I...>, F&& f) 
     (f(std::integral_constant<int, I>{}), ...);
 }
 
+template <bool PR>
 __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
 
@@ -113,10 +125,11 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     // weight slabs through the LDS ring: lane tid moves 8 B (half kh of 16-B group kq) of row tid >> 3
     const int brow = tid >> 3, kq = (tid >> 1) & 3, kh = tid & 1;
     const int bst = BOFF + brow * 64 + ((kq ^ wsw(brow)) << 4) + kh * 8;           // + slot * 16384 + pos * 4096
-    // this wave's Wh / Wl fragments: row 16 cb + r16, 16-B group (kg & 1) / 2 + (kg & 1)
-    const int brd = 16 * cb + r16;
-    const int bfh = BOFF + brd * 64 + (((kg & 1) ^ wsw(brd)) << 4);
-    const int bfl = BOFF + brd * 64 + (((2 + (kg & 1)) ^ wsw(brd)) << 4);
+    // this wave's Wh / Wl fragments: row 16 cb + r16, 16-B group (kg & 1) / 2 + (kg & 1) (PR: k-groups 2, 3 from the
+    // pair's second slab)
+    const int brd = 16 * cb + r16, bps = PR ? (kg >> 1) * 4096 : 0;
+    const int bfh = BOFF + bps + brd * 64 + (((kg & 1) ^ wsw(brd)) << 4);
+    const int bfl = BOFF + bps + brd * 64 + (((2 + (kg & 1)) ^ wsw(brd)) << 4);
     auto st8 = [&](int addr, i32x2 v) { *reinterpret_cast<i32x2*>(lds + addr) = v; };
     auto read_w = [&](int off, i32x4 (&f)[2]) {
         f[0] = lds16(lds, bfh + off);
@@ -137,6 +150,39 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     };
     // D = W x A: a lane holds channels 16 cb + 4 kg .. + 3 of pixel r16 of each fragment
     auto mfma_all = [&](const i32x4 (&fa)[SL], const i32x4 (&fw)[2], bool slot6) {
+        if constexpr (DABL & 1) {
+#pragma unroll
+            for (int i = 0; i < SL; ++i) asm volatile("" ::"v"(fa[i]));
+            asm volatile("" ::"v"(fw[0]), "v"(fw[1]));
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < SL; ++i) {
+            if (i == SL - 1 && !slot6) continue;
+            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[0]), __builtin_bit_cast(f16x8, fa[i]),
+                                                             part[i], 0, 0, 0);
+            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[1]), __builtin_bit_cast(f16x8, fa[i]),
+                                                             part[i], 0, 0, 0);
+        }
+    };
+
+    // PR: fa = A'h, fl = A'l, fw = (W'h, W'l).  The seven W'h x A'l products first (independent accumulators), so that
+    // the one A'l buffer can take the next pair's l halves while the h products run (a second A'l buffer spilled);
+    // then each accumulator's W'h x A'h and W'l x A'h back to back (the matrix pipe chains them)
+    auto mfma_l = [&](const i32x4 (&fl)[SL], const i32x4 (&fw)[2], bool slot6) {
+        if constexpr (DABL & 1) {
+#pragma unroll
+            for (int i = 0; i < SL; ++i) asm volatile("" ::"v"(fl[i]));
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < SL; ++i) {
+            if (i == SL - 1 && !slot6) continue;
+            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[0]), __builtin_bit_cast(f16x8, fl[i]),
+                                                             part[i], 0, 0, 0);
+        }
+    };
+    auto mfma_h = [&](const i32x4 (&fa)[SL], const i32x4 (&fw)[2], bool slot6) {
         if constexpr (DABL & 1) {
 #pragma unroll
             for (int i = 0; i < SL; ++i) asm volatile("" ::"v"(fa[i]));
@@ -194,7 +240,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             const int q = 16 * (fr0 + i) + r16, r = q / W, x = q - r * W;
-            vb[i] = (r * P4 + x) * S4 + kg * 16;
+            // PR: 16-B group kg & 1 of the h half (the l half 32 B on), k-groups 2, 3 from tap t + 1: one pixel lower
+            vb[i] = (r * P4 + x) * S4 + (PR ? (kg & 1) * 16 - (kg >> 1) * S4 : kg * 16);
         }
         // prologue: window chunk 0 -> buffer 0; weight slabs 0..3 -> ring slot 0, 4..7 in registers
         {
@@ -219,10 +266,11 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
         zero_all();
         lds_barrier();
 
-        i32x4 fa[2][SL], fw[2][2];
+        i32x4 fa[2][SL], fl[SL], fw[2][2];
         // next chunk's window pieces: loaded at tap k < NPC, stored at tap k + 12, before the chunk's last barrier
         // (stored 3 taps after the load: 0.335 vs 0.333 ms, not their latency)
-        constexpr int PST = 12;
+        // (PR: 4 taps after the load; the pieces' 12 registers are then free for the second fragment set)
+        constexpr int PST = PR ? 4 : 12;
         i32x4 pr[NPC];
         int wb = 0;      // byte offset of the window buffer being read
         auto read_a = [&](auto tt, i32x4 (&f)[SL]) {
@@ -231,13 +279,61 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 #pragma unroll
             for (int i = 0; i < SL; ++i) f[i] = lds16(lds + imm + wb, vb[i]);
         };
-        read_a(std::integral_constant<int, 0>{}, fa[0]);
+        // PR: the pair of taps t, t + 1 (t even): hl = 0 the h halves, 1 the l halves
+        auto read_ap = [&](auto tt, auto hl, i32x4 (&f)[SL]) {
+            constexpr int t = decltype(tt)::value % 16;
+            constexpr int imm = ((3 - t / 4) * P4 + (3 - t % 4)) * S4 + 32 * decltype(hl)::value;
+#pragma unroll
+            for (int i = 0; i < SL; ++i) f[i] = lds16(lds + imm + wb, vb[i]);
+        };
+        constexpr std::integral_constant<int, 0> kH{};
+        constexpr std::integral_constant<int, 1> kL{};
+        read_a(std::integral_constant<int, 0>{}, fa[0]);   // PR: vb makes this the pair's h halves
+        if constexpr (PR) read_ap(std::integral_constant<int, 0>{}, kL, fl);
         read_w(0, fw[0]);
         // slab S = 16 c + t; group S / 4 in ring slot (S / 4) & 1; barrier every 4 slabs (t % 4 == 3)
         for (int c = 0; c < 8; ++c) {
             const int nb = (c & 1) ? 0 : WBUF;           // next chunk -> the other buffer
             const int cs = c * 64, cn = (c + 1) * 64;    // this / next chunk's byte offset in a pixel / weight tap
-            unroll(std::make_integer_sequence<int, 16>{}, [&](auto tt) {
+            if constexpr (PR) unroll(std::make_integer_sequence<int, 8>{}, [&](auto uu) {
+                constexpr int u = decltype(uu)::value, t = 2 * u;   // taps t, t + 1
+                __builtin_amdgcn_sched_barrier(0);
+                // both slabs' ring and window traffic (as below), the barrier after a ring group's second pair
+                unroll(std::make_integer_sequence<int, 2>{}, [&](auto dd) {
+                    constexpr int tq = t + decltype(dd)::value;
+                    st8(bst + (((tq / 4) + 1) & 1) * 16384 + (tq % 4) * 4096, pb[tq & 3]);
+                    if constexpr (tq + 8 < 16) pb[tq & 3] = bpiece(std::integral_constant<int, tq + 8>{}, cs);
+                    else pb[tq & 3] = bpiece(std::integral_constant<int, tq + 8 - 16>{}, cn);
+                    if constexpr (tq < NPC) pr[tq] = __builtin_amdgcn_raw_buffer_load_b128(rsIn, psrc[tq], cn, 0);
+                    if constexpr (tq >= PST && tq - PST < NPC) {
+                        if (pok[tq - PST] && c < 7) *reinterpret_cast<i32x4*>(lds + nb + pdst[tq - PST]) = pr[tq - PST];
+                    }
+                });
+                if constexpr (t % 4 == 2) loop_barrier();
+                if constexpr (t == 14) wb = nb;
+                // the next pair's fragments go out before this pair's MFMAs
+                // (the h halves and weights; the l halves into their one buffer once this pair's l products are out)
+                if constexpr (DABL & 2) {
+                } else if constexpr (t < 14) {
+                    read_ap(std::integral_constant<int, t + 2>{}, kH, fa[(u + 1) & 1]);
+                } else if (c < 7) {
+                    read_ap(std::integral_constant<int, 0>{}, kH, fa[0]);
+                }
+                if constexpr (!(DABL & 2)) read_w((((t + 2) / 4) & 1) * 16384 + ((t + 2) % 4) * 4096, fw[(u + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_l(fl, fw[u & 1], true);
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (DABL & 2) {
+                } else if constexpr (t < 14) {
+                    read_ap(std::integral_constant<int, t + 2>{}, kL, fl);
+                } else if (c < 7) {
+                    read_ap(std::integral_constant<int, 0>{}, kL, fl);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_h(fa[u & 1], fw[u & 1], true);
+                if constexpr (t % 8 == 6) flush();
+            });
+            else unroll(std::make_integer_sequence<int, 16>{}, [&](auto tt) {
                 constexpr int t = decltype(tt)::value;
                 __builtin_amdgcn_sched_barrier(0);
                 // weights of slab S + 4 (loaded 4 slabs ago) -> group slot (S / 4 + 1) & 1; slab S + 8 -> registers
@@ -278,13 +374,16 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
         }
         // epilogue: BN + LeakyReLU (the layer's activation exponent folded into sc4 / sh4) -> pairs at image pixel
         // (r + 1 - h, x + 1), channels 16 cb + 4 kg + e: 8 B of h pieces, 8 B of l pieces
+        // (pixel addresses from an opaque copy of the lane index: computed here, not kept across the loop above)
+        int lane4 = lane;
+        asm volatile("" : "+v"(lane4));
         const f32x4 sc = par4(PSC4), sh = par4(PSH4);
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
-            const int q = 16 * (fr0 + i) + r16;
+            const int q = 16 * (fr0 + i) + (lane4 & 15);
             if (q >= R4 * W) continue;
             const int r = q / W, x = q - r * W;
-            const int px = ((r + 1 - half) * P5 + x + 1) * S5 + cb * 64 + 8 * kg;
+            const int px = ((r + 1 - half) * P5 + x + 1) * S5 + cb * 64 + 8 * (lane4 >> 4);
             f16x4 hv, lv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -303,10 +402,15 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     // =============================== d_deconv5 + d_deconv6 ===============================
     float* const outc = a.out + (long long)clip * (4 * H * W);
     const __amdgpu_buffer_rsrc_t rsW5 = make_rsrc(a.w5, (long long)ph_woff(4) * 4);
+    // this section's lane-derived addresses from an opaque copy of the thread index: computed here, not hoisted above
+    // d_deconv4's loop (where they were spilled and reloaded)
+    int tid5 = tid;
+    asm volatile("" : "+v"(tid5));
+    const int r16_5 = tid5 & 15, kg_5 = (tid5 >> 4) & 3, brow5 = tid5 >> 3, kq5 = (tid5 >> 1) & 3, kh5 = tid5 & 1;
     int vrow5[3];   // this lane's ring piece in a weight row of kpad 4, 6, 9 taps x 64 (bytes per row 4 kpad)
-    vrow5[0] = brow * (4 * CO * 4) + kq * 16 + kh * 8;
-    vrow5[1] = brow * (6 * CO * 4) + kq * 16 + kh * 8;
-    vrow5[2] = brow * (9 * CO * 4) + kq * 16 + kh * 8;
+    vrow5[0] = brow5 * (4 * CO * 4) + kq5 * 16 + kh5 * 8;
+    vrow5[1] = brow5 * (6 * CO * 4) + kq5 * 16 + kh5 * 8;
+    vrow5[2] = brow5 * (9 * CO * 4) + kq5 * 16 + kh5 * 8;
     auto bpiece5 = [&](auto gg) {   // ring piece of global slab g (past the end: phase 3's slab 0, unused)
         constexpr int g = decltype(gg)::value < ph_gstart(4) ? decltype(gg)::value : ph_gstart(3);
         constexpr int p = ph_of(g), sl = g - ph_gstart(p);
@@ -316,8 +420,9 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     int vb5[SL];
 #pragma unroll
     for (int i = 0; i < SL; ++i) {
-        const int q = 16 * (fr0 + i) + r16, yl = q / W, x = q - yl * W;
-        vb5[i] = (yl * P5 + x) * S5 + kg * 16;   // tap (-1, -1)
+        const int q = 16 * (fr0 + i) + r16_5, yl = q / W, x = q - yl * W;
+        // tap (-1, -1); PR: group kg & 1 of the h half (the l half 32 B on), k-groups 2, 3 from the next chunk
+        vb5[i] = (yl * P5 + x) * S5 + (PR ? (kg_5 & 1) * 16 + (kg_5 >> 1) * 64 : kg_5 * 16);
     }
     auto read_a5 = [&](auto gg, i32x4 (&f)[SL]) {
         constexpr int g = decltype(gg)::value;
@@ -328,6 +433,19 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
         for (int i = 0; i < SL - 1; ++i) f[i] = lds16(lds + imm, vb5[i]);
         if (s6) f[SL - 1] = lds16(lds + imm, vb5[SL - 1]);
     };
+    // PR: slabs g, g + 1 (chunks c, c + 1 of one tap): hl = 0 the h halves, 1 the l halves
+    auto read_a5p = [&](auto gg, auto hl, i32x4 (&f)[SL]) {
+        constexpr int g = decltype(gg)::value;
+        constexpr int p = ph_of(g), sl = g - ph_gstart(p), tap = sl / 4, c = sl % 4;
+        static_assert(c % 2 == 0, "a pair lies inside one tap");
+        constexpr int dy = (p >> 1) - tap / ph_nx(p), dx = (p & 1) - tap % ph_nx(p);
+        constexpr int imm = ((dy + 1) * P5 + (dx + 1)) * S5 + c * 64 + 32 * decltype(hl)::value;
+#pragma unroll
+        for (int i = 0; i < SL - 1; ++i) f[i] = lds16(lds + imm, vb5[i]);
+        if (s6) f[SL - 1] = lds16(lds + imm, vb5[SL - 1]);
+    };
+    constexpr std::integral_constant<int, 0> kH{};
+    constexpr std::integral_constant<int, 1> kL{};
     float* const xp = reinterpret_cast<float*>(lds + XP);
     auto epilogue5 = [&](auto pp) {
         constexpr int p = decltype(pp)::value, py = p >> 1, px = p & 1;
@@ -367,12 +485,43 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     }
     zero_all();
     lds_barrier();
-    i32x4 fa[2][SL], fw[2][2];
-    read_a5(std::integral_constant<int, 0>{}, fa[0]);
+    i32x4 fa[2][SL], fl[SL], fw[2][2];
+    read_a5(std::integral_constant<int, 0>{}, fa[0]);   // PR: vb5 makes this the pair's h halves
+    if constexpr (PR) read_a5p(std::integral_constant<int, 0>{}, kL, fl);
     read_w(0, fw[0]);
     // global slab g: store g + 4 -> slot ((g / 4) + 1) & 1, load g + 8, barrier every 4 slabs; the fragments of g + 1
     // go out before g's MFMAs (a phase's last slab: after its epilogue, whose barrier also orders the xp buffer)
-    unroll(std::make_integer_sequence<int, ph_gstart(4)>{}, [&](auto gg) {
+    if constexpr (PR) unroll(std::make_integer_sequence<int, ph_gstart(4) / 2>{}, [&](auto uu) {
+        constexpr int u = decltype(uu)::value, g = 2 * u, p = ph_of(g);   // slabs g, g + 1
+        constexpr bool last = g + 2 == ph_gstart(p + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        unroll(std::make_integer_sequence<int, 2>{}, [&](auto dd) {
+            constexpr int gq = g + decltype(dd)::value;
+            st8(bst + (((gq / 4) + 1) & 1) * 16384 + (gq % 4) * 4096, pb[gq & 3]);
+            pb[gq & 3] = bpiece5(std::integral_constant<int, gq + 8>{});
+        });
+        if constexpr (g % 4 == 2) loop_barrier();
+        if constexpr (!last && !(DABL & 2)) {
+            read_a5p(std::integral_constant<int, g + 2>{}, kH, fa[(u + 1) & 1]);
+            read_w((((g + 2) / 4) & 1) * 16384 + ((g + 2) % 4) * 4096, fw[(u + 1) & 1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_l(fl, fw[u & 1], s6);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!last && !(DABL & 2)) read_a5p(std::integral_constant<int, g + 2>{}, kL, fl);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_h(fa[u & 1], fw[u & 1], s6);
+        if constexpr (!last && (g - ph_gstart(p)) % 8 == 6) flush();
+        if constexpr (last) {
+            epilogue5(std::integral_constant<int, p>{});
+            if constexpr (p < 3) {
+                read_a5p(std::integral_constant<int, g + 2>{}, kH, fa[(u + 1) & 1]);
+                read_a5p(std::integral_constant<int, g + 2>{}, kL, fl);
+                read_w((((g + 2) / 4) & 1) * 16384 + ((g + 2) % 4) * 4096, fw[(u + 1) & 1]);
+            }
+        }
+    });
+    else unroll(std::make_integer_sequence<int, ph_gstart(4)>{}, [&](auto gg) {
         constexpr int g = decltype(gg)::value, p = ph_of(g);
         constexpr bool last = g + 1 == ph_gstart(p + 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -411,8 +560,10 @@ bool dec_tail_s16_supported(const DecTailArgs& a) {
 }
 
 int launch_dec_tail_s16(const DecTailArgs& a, hipStream_t s) {
-    if (int rc = ensure_lds_attr((const void*)k_dec_tail_s16, LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(k_dec_tail_s16, dim3(2 * a.N), dim3(NT), LDS_BYTES, s, a);
+    // planar slab pairs with three products; Options::four_products: slab by slab with all four
+    auto* const kf = a.four_products ? k_dec_tail_s16<false> : k_dec_tail_s16<true>;
+    if (int rc = ensure_lds_attr((const void*)kf, LDS_BYTES)) return rc;
+    hipLaunchKernelGGL(kf, dim3(2 * a.N), dim3(NT), LDS_BYTES, s, a);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -47,7 +47,15 @@ __device__ __forceinline__ i32x4 lds16(const char* p) { return *reinterpret_cast
 // k_conv's (kFp32Block slabs summed from zero, then added to the running sum in order) and split-K splits hold
 // whole blocks (GemmArgs::slabs_per_split), so a split plan fixed by K and N (dense) or one block per split (v_conv6)
 // gives every batch size the same bits.  Outputs are stored as pairs (range guard: GemmArgs::range_flag).
-template <int MODE, int ABL = 0, bool S16 = false>
+// PR (planar slab pairs, the default for S16; GemmArgs::four_products selects the form above): two consecutive slabs
+// t, t + 1 (t even: a pair lies inside one ring group and one summation block) as one 32-deep operand per half,
+//   A'h = [Ah(t) | Ah(t+1)]  A'l = [Al(t) | Al(t+1)]  W'h = [Wh(t) | Wh(t+1)]  W'l = [Wl(t) | Wl(t+1)]
+// (lanes of k-groups 0, 1 read slab t, 2, 3 slab t + 1: 16-B groups kg & 1 of the h half, 2 + (kg & 1) of the l half,
+// so every distinct operand byte is read once and no lane exchange is needed), and three MFMAs per accumulator and
+// pair, A'h x W'h, A'l x W'h, A'h x W'l: Al x Wl (<= 2^-22 |a w|, below the pairs' own representation error) is
+// dropped as in the stream convolutions.  Per wave and pair 12 ds_read_b128 and 24 MFMAs (slab by slab: 16 and 32).
+// Slabs past the split's end are zeros in LDS (load), so an odd slab count pairs its last slab with zeros.
+template <int MODE, int ABL = 0, bool S16 = false, bool PR = S16>
 __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     __shared__ int last_flag;
@@ -109,7 +117,22 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
     // S16: the h half of W read by every lane (k-group kg & 1) and the l half (2 + (kg & 1))
     const int bfr = 8192 + (32 * wn + r16) * 64 + (((S16 ? kg & 1 : kg) ^ wsw(r16)) << 4);
     const int bfl = 8192 + (32 * wn + r16) * 64 + (((2 + (kg & 1)) ^ wsw(r16)) << 4);
-    i32x4 fa[2][4], fb[2][2], fl[2][2];
+    // PR: slab (s & ~1) + (kg >> 1) of the pair; h halves (16-B group kg & 1) and l halves (2 + (kg & 1)) of A and W
+    const int pso = (kg >> 1) * SLAB;
+    const int pah = pso + (64 * wm + r16) * 64 + (((kg & 1) ^ wsw(r16)) << 4);
+    const int pal = pso + (64 * wm + r16) * 64 + (((2 + (kg & 1)) ^ wsw(r16)) << 4);
+    i32x4 fa[2][4], fb[2][2], fl[2][2], fal[2][4];
+    auto read_pair = [&](int s, int buf) {   // s even: fa = A'h, fal = A'l, fb = W'h, fl = W'l
+        const char* const b = lds + ((s >> 2) & 1) * GRP + (s & 3) * SLAB;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[buf][i] = lds16(b + pah + 1024 * i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fal[buf][i] = lds16(b + pal + 1024 * i);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fb[buf][j] = lds16(b + pso + bfr + 1024 * j);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fl[buf][j] = lds16(b + pso + bfl + 1024 * j);
+    };
     auto read = [&](int s, int buf) {
         const char* const b = lds + ((s >> 2) & 1) * GRP + (s & 3) * SLAB;
 #pragma unroll
@@ -145,10 +168,54 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
         for (int s = 0; s < 4; ++s) store(s, a0[s], w0[s]);
     }
     __syncthreads();
-    read(0, 0);
+    if constexpr (S16 && PR) read_pair(0, 0);
+    else read(0, 0);
     // slab S: store S + 4 (loaded 4 slabs ago), load S + 8, a barrier every 4 slabs publishes the next group;
     // every step runs (the padding past nsl only moves data) so the outstanding-load count is static
-    if constexpr (S16) {
+    if constexpr (S16 && PR) {
+        // one fp32 summation block (four slab pairs) per iteration.  Pair at slabs s, s + 1: both slabs' ring traffic
+        // (the barrier after a group's second pair), the next pair's fragments, then the pair's 24 MFMAs product by
+        // product over the eight fragment blocks (no MFMA waits on the one just issued; per accumulator the order
+        // A'h W'h, A'l W'h, A'h W'l).
+        const int npad8 = (nsl + kFp32Block - 1) & ~(kFp32Block - 1);
+        for (int s0 = 0; s0 < npad8; s0 += kFp32Block) {
+#pragma unroll
+            for (int p = 0; p < kFp32Block / 2; ++p) {
+                const int s = s0 + 2 * p, q0 = (2 * p) & 3, q1 = (2 * p + 1) & 3;
+                __builtin_amdgcn_sched_barrier(0);
+                store(s + 4, ra[q0], rw[q0]);
+                load(s + 8, ra[q0], rw[q0]);
+                store(s + 5, ra[q1], rw[q1]);
+                load(s + 9, ra[q1], rw[q1]);
+                if (p & 1) __syncthreads();
+                read_pair(s + 2, (p + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr ((ABL & 4) != 0) {   // ablation: no MFMAs (fragments kept live)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        blk[i][0][0] += __builtin_bit_cast(float, fa[p & 1][i][0] ^ fal[p & 1][i][3] ^ fb[p & 1][i & 1][1] ^
+                                                                      fl[p & 1][i & 1][2]);
+                    continue;
+                }
+#pragma unroll
+                for (int h = 0; h < 3; ++h)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            blk[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                __builtin_bit_cast(f16x8, h == 1 ? fal[p & 1][i] : fa[p & 1][i]),
+                                __builtin_bit_cast(f16x8, h == 2 ? fl[p & 1][j] : fb[p & 1][j]), blk[i][j], 0, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[i][j] += blk[i][j];
+                    blk[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+        }
+    } else if constexpr (S16) {
         // one fp32 summation block per iteration: the block's MFMAs into blk (the h-weight products of all eight
         // fragment blocks, then the l-weight ones: no MFMA waits on the one just issued; per accumulator k_conv's
         // order), then into the running sum.  Padded slabs read zeros (load) and add exact zeros: no branch in the
@@ -325,8 +392,13 @@ int launch_gemm(const GemmArgs& g, int mode, hipStream_t s) {
 #ifndef AVSE_GEMM_ABL
 #define AVSE_GEMM_ABL 0
 #endif
-    const void* kf = mode == 0 ? (s16 ? (const void*)k_gemm<0, AVSE_GEMM_ABL, true> : (const void*)k_gemm<0>)
-                               : (s16 ? (const void*)k_gemm<1, AVSE_GEMM_ABL, true> : (const void*)k_gemm<1>);
+    const bool pr = s16 && !g.four_products;   // planar slab pairs, three products (Options::four_products: slab by slab)
+    const void* kf = mode == 0 ? (pr    ? (const void*)k_gemm<0, AVSE_GEMM_ABL, true, true>
+                                  : s16 ? (const void*)k_gemm<0, AVSE_GEMM_ABL, true, false>
+                                        : (const void*)k_gemm<0>)
+                               : (pr    ? (const void*)k_gemm<1, AVSE_GEMM_ABL, true, true>
+                                  : s16 ? (const void*)k_gemm<1, AVSE_GEMM_ABL, true, false>
+                                        : (const void*)k_gemm<1>);
     if (int rc = ensure_lds_attr(kf, LDS_BYTES)) return rc;
     const int kq = s16 ? 16 : 32;   // k per 64-B slab
     const int nslab = g.kpad / kq;
@@ -338,6 +410,8 @@ int launch_gemm(const GemmArgs& g, int mode, hipStream_t s) {
         set_error("gemm: bad arguments");
         return 3;
     }
+    // split-K tickets: one counter per output tile (the caller then takes the layer's k_conv path)
+    if (!gemm_tickets_fit(g.M, g.N, g.ksplit, g.counters_cap)) return -1;
     const dim3 grid((g.M + 127) / 128, (g.N + 127) / 128, g.ksplit);
     hipLaunchKernelGGL(reinterpret_cast<void (*)(GemmArgs)>(const_cast<void*>(kf)), grid, dim3(NT), LDS_BYTES, s, g);
     AVSE_HIP_CHECK(hipGetLastError());

@@ -192,4 +192,13 @@ inline std::vector<int> gather_map(const LayerDef& L, const PhaseSet& g) {
     return m;
 }
 
+// gemm.hip's split-K tickets: one int per 128 x 128 output tile of a launch, in a per-context array of kGemmCounters.
+// A split launch (ksplit > 1) with more tiles than counters does not fit: launch_gemm declines it and the forward runs
+// that layer on k_conv.  (The split dtype's dense layers always split: dec_dense2's 25 column tiles pass the array at
+// 327 row tiles, about 41.9K clips.)
+constexpr int kGemmCounters = 8192;
+inline bool gemm_tickets_fit(long long M, long long N, int ksplit, long long counters) {
+    return ksplit <= 1 || ((M + 127) / 128) * ((N + 127) / 128) <= counters;
+}
+
 }  // namespace avse

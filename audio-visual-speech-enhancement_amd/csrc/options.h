@@ -24,7 +24,8 @@ struct Options {
     int no_v1p = 0;           // AVSE_NO_V1P: split 5-frame v_conv1 on k_conv_v1s (K 160), not k_conv_v1p (K 128; read at load)
     int no_a1valu = 0;        // AVSE_NO_A1VALU: split a_conv1 on k_conv after audio_prep, not k_aconv1_split
     int no_planar = 0;        // AVSE_NO_PLANAR: split stream convs on the slice-by-slice [Ah | Al] grouping with lane swaps
-    int side_prio = 0;        // AVSE_SIDE_PRIO: audio side stream priority (0 default, 1 least, 2 greatest; read when created)
+    int four_products = 0;    // AVSE_FOUR_PRODUCTS: split k_gemm and decoder tail slab by slab with all four products, not three-product planar slab pairs
+    int side_prio = 0;       // AVSE_SIDE_PRIO: audio side stream priority (0 default, 1 least, 2 greatest; read when created)
 };
 
 // ---- tiled video convolutions: conv_v1r.hip (v_conv1), conv_stream.hip (v_conv2..v_conv5) ----

@@ -52,8 +52,9 @@ enum avse_status {
  *                   x = h + l (h = f16(x), l = f16(x - h); weights scaled per output channel by a power of two) and
  *                   forms the products with v_mfma_f32_16x16x32_f16, each MFMA rounding its 32 exact products once
  *                   into the fp32 accumulator (a K = 3200 dot product: more accurate than exact-fp32 MFMA,
- *                   tools/split_probe.hip): h h, l h, h l in the video convolutions v_conv1..v_conv5 (l l, 2^-22 of
- *                   |a b|, dropped), all four in the other layers.  Activations pass between layers as the pairs
+ *                   tools/split_probe.hip): h h, l h, h l in the video convolutions v_conv1..v_conv5, in k_gemm's
+ *                   layers (v_conv6, the dense layers) and in the fused decoder tail (l l, 2^-22 of |a b|, dropped;
+ *                   option four_products keeps it in the latter two), all four in the remaining layers.  Activations pass between layers as the pairs
  *                   (about 22 significant bits; the float32 network inputs are split on load, the decoder's last
  *                   output is float32): whole-network error measured 1.3x AVSE_F32's (6.8e-5 vs
  *                   5.1e-5 absolute RMS on dB-scale outputs, tests/test_gpu_split.py), inside the north star's 1e-4.
@@ -105,6 +106,9 @@ void avse_ctx_destroy(avse_ctx* ctx);
  *   no_a1valu (AVSE_NO_A1VALU)       AVSE_F32_SPLIT a_conv1 on audio_prep + k_conv instead of k_aconv1_split
  *   no_planar (AVSE_NO_PLANAR)       AVSE_F32_SPLIT stream convolutions on the slice-by-slice [Ah | Al] grouping with
  *                                    lane swaps instead of the planar slice-pair grouping
+ *   four_products (AVSE_FOUR_PRODUCTS) AVSE_F32_SPLIT k_gemm (v_conv6, the dense layers) and the fused decoder tail slab
+ *                                    by slab with all four products of (Ah + Al)(Wh + Wl) instead of three-product
+ *                                    planar slab pairs
  *   side_prio (AVSE_SIDE_PRIO)       audio side stream priority: 0 default, 1 least, 2 greatest (set before the
  *                                    context's first concurrent forward)
  * Unknown names return AVSE_ERR_INVALID. */

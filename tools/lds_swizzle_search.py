@@ -81,11 +81,96 @@ def v1r_read2_cycles(pitch, pb=12):
     return worst
 
 
+def gemm_fragment_reads(pairs):
+    """gemm.hip k_gemm<.., S16> fragment byte addresses per lane inside a ring group (4 slabs of 16 KB: A rows at
+    row * 64, W rows at 8192 + row * 64, 16-B slot xor wsw(row) = 2 ((row >> 2) & 1)), for every wave (wm, wn), fragment
+    and slab position: slab by slab (A slot kg; W slots kg & 1 and 2 + (kg & 1)) or the planar slab pairs (lanes of
+    k-groups 2, 3 one slab further; h slots kg & 1, l slots 2 + (kg & 1) of A and of W).  Yields (name, [64 addresses])."""
+    wsw = lambda row: 2 * ((row >> 2) & 1)
+    for pos in (range(0, 4, 2) if pairs else range(4)):
+        for wm in range(2):
+            for i in range(4):
+                rows = [64 * wm + 16 * i + (l & 15) for l in range(64)]
+                if pairs:
+                    for nm, s0 in (("A'h", 0), ("A'l", 2)):
+                        yield f"{nm} pos {pos} wm {wm} i {i}", [
+                            (pos + (l >> 5)) * 16384 + rows[l] * 64 + (((s0 + ((l >> 4) & 1)) ^ wsw(l & 15)) << 4) for l in range(64)]
+                else:
+                    yield f"A pos {pos} wm {wm} i {i}", [pos * 16384 + rows[l] * 64 + (((l >> 4) ^ wsw(l & 15)) << 4) for l in range(64)]
+        for wn in range(4):
+            for j in range(2):
+                rows = [32 * wn + 16 * j + (l & 15) for l in range(64)]
+                for nm, s0 in (("Wh", 0), ("Wl", 2)):
+                    yield f"{nm} pos {pos} wn {wn} j {j}", [
+                        (pos + ((l >> 5) if pairs else 0)) * 16384 + 8192 + rows[l] * 64 + (((s0 + ((l >> 4) & 1)) ^ wsw(l & 15)) << 4)
+                        for l in range(64)]
+
+
+def tail_fragment_reads(pairs):
+    """conv_dects.hip k_dec_tail_s16 A fragment byte addresses per lane: 16 consecutive pixels q = 16 f + r16 of the
+    10-wide grid at pixel pitch 18, d_deconv4 window pixels of 96 B (16 taps, 14 fragments), d_deconv5 image pixels of
+    288 B (the phases' taps x 4 chunks of 64 B, 13 fragments); slab by slab a lane reads 16-B group kg, the planar pairs
+    read group kg & 1 (h) or 2 + (kg & 1) (l) with k-groups 2, 3 on the next tap (one pixel lower: d_deconv4, every tap
+    pair) or the next chunk (+ 64 B: d_deconv5, every chunk pair).  Yields (name, [64 addresses])."""
+    def pix(f, l, pitch):
+        q = 16 * f + (l & 15)
+        return (q // 10) * 18 * pitch + (q % 10) * pitch
+    for f in range(14):
+        for t in (range(0, 16, 2) if pairs else range(16)):
+            imm = ((3 - t // 4) * 18 + (3 - t % 4)) * 96
+            if pairs:
+                for nm, s0 in (("A'h", 0), ("A'l", 32)):
+                    yield f"d4 {nm} f {f} taps {t},{t + 1}", [imm + s0 + pix(f, l, 96) + ((l >> 4) & 1) * 16 - (l >> 5) * 96 for l in range(64)]
+            else:
+                yield f"d4 A f {f} tap {t}", [imm + pix(f, l, 96) + (l >> 4) * 16 for l in range(64)]
+    for f in range(13):
+        for dy in range(3):
+            for dx in range(3):
+                for c in (range(0, 4, 2) if pairs else range(4)):
+                    imm = (dy * 18 + dx) * 288 + c * 64
+                    if pairs:
+                        for nm, s0 in (("A'h", 0), ("A'l", 32)):
+                            yield f"d5 {nm} f {f} tap ({dy},{dx}) chunks {c},{c + 1}", [
+                                imm + s0 + pix(f, l, 288) + ((l >> 4) & 1) * 16 + (l >> 5) * 64 for l in range(64)]
+                    else:
+                        yield f"d5 A f {f} tap ({dy},{dx}) chunk {c}", [imm + pix(f, l, 288) + (l >> 4) * 16 for l in range(64)]
+    # weight ring: 64 rows x 64 B per slab (4 KB), slot xor wsw(row); wave's rows 16 cb + r16
+    wsw = lambda row: 2 * ((row >> 2) & 1)
+    for cb in range(4):
+        for pos in (range(0, 4, 2) if pairs else range(4)):
+            for nm, s0 in (("Wh", 0), ("Wl", 2)):
+                yield f"{nm} cb {cb} pos {pos}", [(pos + ((l >> 5) if pairs else 0)) * 4096 + (16 * cb + (l & 15)) * 64 +
+                                                  (((s0 + ((l >> 4) & 1)) ^ wsw(16 * cb + (l & 15))) << 4) for l in range(64)]
+
+
+def read_conflicts(addrs):
+    """16-lane service groups of one ds_read_b128 that do not hit 16 distinct 16-B units of the 256-B bank line."""
+    return sum(len({(addrs[l] // 16) % 16 for l in grp}) < 16 for grp in GROUPS)
+
+
 if __name__ == "__main__":
     import sys
+    if "--gemm" in sys.argv:
+        for pairs in (False, True):
+            reads = list(gemm_fragment_reads(pairs))
+            assert all(0 <= a and a + 16 <= 65536 and a % 16 == 0 for _, ad in reads for a in ad), "inside the ring group"
+            bad = [name for name, ad in reads if read_conflicts(ad)]
+            assert not bad, bad[:8]
+            print(f"k_gemm split fragments, {'planar slab pairs' if pairs else 'slab by slab'}: {len(reads)} reads "
+                  f"(every wave, fragment and slab position), all conflict-free")
+        sys.exit(0)
     if "--v1r" in sys.argv:
         for pitch in range(20, 29):
             print(f"conv_v1r window pitch {pitch}: {v1r_read2_cycles(pitch)} LDS cycles per A fragment (8 = conflict-free)")
+        sys.exit(0)
+    if "--tail" in sys.argv:
+        for pairs in (False, True):
+            reads = list(tail_fragment_reads(pairs))
+            assert all(a >= 0 and a % 16 == 0 for _, ad in reads for a in ad)
+            bad = [name for name, ad in reads if read_conflicts(ad)]
+            assert not bad, bad[:8]
+            print(f"k_dec_tail_s16 fragments, {'planar slab pairs' if pairs else 'slab by slab'}: {len(reads)} reads (every "
+                  f"fragment, tap or tap pair, chunk or chunk pair, weight ring position), all conflict-free at pitch 18")
         sys.exit(0)
     assert all(max(g) < 32 or min(g) >= 32 for g in GROUPS), "a service group stays within one half of the wave"
     for name, kmap in KMAPS.items():

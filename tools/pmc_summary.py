@@ -26,7 +26,10 @@ LABELS = [("k_spec_seg", ["stft"]), ("k_spec640", ["stft"]), ("k_spec_dft", ["st
           ("k_splitk_reduce", ["splitk_reduce"]),
           ("k_conv_stream<5,", ["v_conv2"]), ("k_conv_stream<3, 16, 16", ["v_conv3", "v_conv4"]),
           ("k_conv_stream<3, 8, 8", ["v_conv5"]), ("k_gemm<1>", ["v_conv6"]),
-          ("k_gemm<0>", ["enc_dense", "dec_dense1", "dec_dense2"]), ("k_dec_head", ["dec_head"]),
+          ("k_gemm<0>", ["enc_dense", "dec_dense1", "dec_dense2"]),
+          # the split dtype's instantiations (k_gemm<MODE, ABL, true, PR>)
+          ("k_gemm<1,", ["v_conv6"]), ("k_gemm<0,", ["enc_dense", "dec_dense1", "dec_dense2"]),
+          ("k_dec_head", ["dec_head"]),
           ("k_dec_tail", ["dec_tail"]), ("k_conv<", ["k_conv"]), ("k_istft", ["istft"]), ("k_ola", ["istft_ola"])]
 ALGO_BYTES = {  # algorithmic HBM bytes per launch: bf16 2 B per value; split pairs 4 B
     ("bf16", "v_conv2", 512): 512 * (64 * 64 * 128 * 2 + 32 * 32 * 128 * 2) + 128 * 3200 * 2,

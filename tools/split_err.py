@@ -13,6 +13,17 @@ model (one v_mfma_f32_16x16x32_f16 sums its 32 products exactly and rounds once 
     pair:   [Ah Bh + Al Bh](t) | [Ah Bh + Al Bh](t+1) | Ah Bl (t) + Ah Bl (t+1)
     planar: Ah Bh (t) + Ah Bh (t+1) | Al Bh (t) + Al Bh (t+1) | Ah Bl (t) + Ah Bl (t+1)
 (v_conv1 keeps the fp16x3 scheme above in both.)
+
+    python tools/split_err.py [N] [seed] generic      # the generic layers' two forms, accumulation order included
+
+"generic" emulates the layers that run on gemm.hip k_gemm (v_conv6, enc_dense, dec_dense1, dec_dense2) and on the fused
+decoder tail conv_dects.hip (d_deconv4, d_deconv5) under the same MFMA accumulation model, with 16-k slabs in each
+kernel's K order, k_conv's blocked summation (8 slabs from zero, then into the running sum), the dense layers' split-K
+plan (gemm_s16_ksplit: groups of blocks per split, the splits added in order) and activations passed on as f16 pairs:
+    four:   slab by slab, [Ah Wh + Al Wh](t) | [Ah Wl + Al Wl](t)                            (two roundings per slab)
+    three:  slab pairs,   Ah Wh (t, t+1) | Al Wh (t, t+1) | Ah Wl (t, t+1)                   (three roundings per pair)
+(the tail takes Al Wh first).  The layers before v_conv6 and a_conv5's embedding come from the float64 oracle rounded
+to float32, d_deconv1..3 and d_deconv6 are float64 on float32-rounded inputs: the figures isolate the two kernels' forms.
 """
 import os
 import sys
@@ -131,6 +142,146 @@ def make_grouped_conv(grouping, fallback):
     return conv
 
 
+def pairs16(x):
+    """float64 holding float32 values -> the f16 pair (h, l) a split layer stores and the next one reads"""
+    return split(f32(x), 2, torch.float16)
+
+
+def emu_gemm(slabs, M, cout, form, lh_first=False, blocks_per_split=0):
+    """slabs: list of callables -> (ah, al [M, 16], wh, wl [16, cout]) in the kernel's K order; returns the fp32
+    accumulator [M, cout] under the MFMA model (each MFMA's products exact, one rounding into the accumulator)."""
+    nslab = len(slabs)
+    parts, acc = [], torch.zeros(M, cout, dtype=torch.float64)
+    for b0 in range(0, nslab, 8):
+        blk = torch.zeros(M, cout, dtype=torch.float64)
+        if form == "four":
+            for t in range(b0, min(b0 + 8, nslab)):
+                ah, al, wh, wl = slabs[t]()
+                blk = f32(blk + (ah @ wh + al @ wh))
+                blk = f32(blk + (ah @ wl + al @ wl))
+        else:
+            for t in range(b0, min(b0 + 8, nslab), 2):
+                ah0, al0, wh0, wl0 = slabs[t]()
+                if t + 1 < nslab:
+                    ah1, al1, wh1, wl1 = slabs[t + 1]()
+                else:   # an odd tail pairs with a zero slab
+                    ah1, al1, wh1, wl1 = (torch.zeros_like(v) for v in (ah0, al0, wh0, wl0))
+                hh, lh, hl = ah0 @ wh0 + ah1 @ wh1, al0 @ wh0 + al1 @ wh1, ah0 @ wl0 + ah1 @ wl1
+                for term in ((lh, hh, hl) if lh_first else (hh, lh, hl)):
+                    blk = f32(blk + term)
+        acc = f32(acc + blk)
+        if blocks_per_split and (b0 // 8 + 1) % blocks_per_split == 0:
+            parts.append(acc)
+            acc = torch.zeros(M, cout, dtype=torch.float64)
+    if not blocks_per_split:
+        return acc
+    if nslab and ((nslab + 7) // 8) % blocks_per_split:
+        parts.append(acc)
+    tot = torch.zeros(M, cout, dtype=torch.float64)
+    for q in parts:   # the tile's last workgroup adds the splits' partials in split order
+        tot = f32(tot + q)
+    return tot
+
+
+def wpairs(w):
+    """[K, cout] weights -> (wh, wl, scale): x 2^e per output channel with max |w| 2^e in [2^14, 2^15) (weight_pack.cpp)"""
+    wmax = w.abs().amax(dim=0).clamp_min(1e-30)
+    wsc = torch.pow(2.0, 14 - torch.floor(torch.log2(wmax)))
+    wh, wl = split(w * wsc, 2, torch.float16)
+    return wh, wl, wsc
+
+
+def emu_dense(x, kernel, bias, form):
+    K_, cout = kernel.shape
+    kp = (K_ + 15) // 16 * 16
+    w = torch.zeros(kp, cout, dtype=torch.float64)
+    w[:K_] = torch.as_tensor(np.asarray(kernel, np.float32), dtype=torch.float64)
+    wh, wl, wsc = wpairs(w)
+    xp = torch.zeros(x.shape[0], kp, dtype=torch.float64)
+    xp[:, :K_] = x
+    xh, xl = pairs16(xp)
+    slabs = [lambda t=t: (xh[:, 16 * t:16 * t + 16], xl[:, 16 * t:16 * t + 16], wh[16 * t:16 * t + 16], wl[16 * t:16 * t + 16])
+             for t in range(kp // 16)]
+    nblocks, tiles_n = (kp // 16 + 7) // 8, (cout + 127) // 128   # gemm.hip gemm_s16_ksplit
+    ks = max(1, min(nblocks, 256 // (4 * tiles_n)))
+    G = (nblocks + ks - 1) // ks
+    acc = emu_gemm(slabs, x.shape[0], cout, form, blocks_per_split=G if (nblocks + G - 1) // G > 1 else 0)
+    return f32(acc / wsc + torch.as_tensor(bias, dtype=torch.float64))
+
+
+def emu_gather(x, taps, wk, order, form, lh_first=False):
+    """One stride phase as a GEMM: x NHWC [n, H, W, cin] (float64 of float32), taps [(dy, dx)] with wk[i] the [cin, cout]
+    weights of tap i, output pixel (y, x) reads input (y + dy, x + dx) (zero outside); order: list of (tap, chunk)."""
+    n, H, W, cin = x.shape
+    cout = wk[0].shape[1]
+    wh, wl, wsc = wpairs(torch.cat(wk, 0))
+    xh, xl = pairs16(x)
+    pad = max(max(abs(dy), abs(dx)) for dy, dx in taps)
+    xh, xl = (F.pad(v, (0, 0, pad, pad, pad, pad)) for v in (xh, xl))
+
+    def slab(tap, c):
+        dy, dx = taps[tap]
+        cs = slice(16 * c, 16 * c + 16)
+        a = [v[:, pad + dy:pad + dy + H, pad + dx:pad + dx + W, cs].reshape(-1, 16) for v in (xh, xl)]
+        ws = slice(tap * cin + 16 * c, tap * cin + 16 * c + 16)
+        return a[0], a[1], wh[ws], wl[ws]
+    acc = emu_gemm([lambda t=t, c=c: slab(t, c) for t, c in order], n * H * W, cout, form, lh_first)
+    return (acc / wsc).reshape(n, H, W, cout)
+
+
+def main_generic(N, seed, wd, mel, video, ref, rms):
+    inter = {}
+    K.forward(wd, mel, video, intermediates=inter)
+    T64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+
+    def bn_act(y, name):   # y NHWC or [n, c]; BN + LeakyReLU in float64, stored as float32 (then as pairs by the reader)
+        return f32(K.lrelu(K.bn(y, wd[name + "_bn"], torch.float64, channel_dim=y.dim() - 1)))
+
+    out = {}
+    for form in ("four", "three"):
+        # v_conv6: 3x3 'same' on 4 x 4 x 512, k = tap * 512 + c (gemm.hip MODE 1), BN + LeakyReLU, 2x2 max pool
+        v5 = f32(T64(inter["v_conv5"]))
+        k6 = T64(np.asarray(wd["v_conv6"]["kernel"], np.float32))
+        taps = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
+        y = emu_gather(v5, taps, [k6[ky, kx] for ky in range(3) for kx in range(3)],
+                       [(t, c) for t in range(9) for c in range(32)], form)
+        y = bn_act(f32(y + T64(wd["v_conv6"]["bias"])), "v_conv6")
+        y = F.max_pool2d(y.permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1).reshape(N, -1)
+        aemb = inter["concat"].shape[1] - y.shape[1]
+        x = torch.cat([f32(T64(inter["concat"][:, :aemb])), y], 1)
+        x = bn_act(emu_dense(x, wd["enc_dense"]["kernel"], wd["enc_dense"]["bias"], form), "enc_dense")
+        x = bn_act(emu_dense(x, wd["dec_dense1"]["kernel"], wd["dec_dense1"]["bias"], form), "dec_dense1")
+        x = emu_dense(x, wd["dec_dense2"]["kernel"], wd["dec_dense2"]["bias"], form)
+        x = bn_act(x.reshape(N, 5, -1, 128), "dec_dense2").permute(0, 3, 1, 2)
+        for name, s_ in (("d_deconv1", (2, 1)), ("d_deconv2", (2, 1)), ("d_deconv3", (2, 2))):
+            x = K.deconv_same(f32(x), wd[name]["kernel"], wd[name]["bias"], s_, torch.float64)
+            x = f32(K.lrelu(K.bn(x, wd[name + "_bn"], torch.float64)))
+        x = x.permute(0, 2, 3, 1)   # NHWC [N, 40, 10, 128]
+        # d_deconv4: 4x4 stride 1, tap t = (ky, kx) reads (1 - ky, 1 - kx); K13 walks slab 16 c + t
+        k4 = T64(np.asarray(wd["d_deconv4"]["kernel"], np.float32))   # (kh, kw, cout, cin)
+        taps = [(1 - ky, 1 - kx) for ky in range(4) for kx in range(4)]
+        y = emu_gather(x, taps, [k4[ky, kx].T for ky in range(4) for kx in range(4)],
+                       [(t, c) for c in range(8) for t in range(16)], form, lh_first=True)
+        x = bn_act(f32(y + T64(wd["d_deconv4"]["bias"])), "d_deconv4")
+        # d_deconv5: 5x5 stride 2, phase (py, px): kernel rows ky with (py + 1 - ky) even read dy = (py + 1 - ky) / 2
+        k5 = T64(np.asarray(wd["d_deconv5"]["kernel"], np.float32))
+        n_, H, W, _ = x.shape
+        y5 = torch.zeros(n_, 2 * H, 2 * W, k5.shape[2], dtype=torch.float64)
+        for py in range(2):
+            for px in range(2):
+                kys = [ky for ky in range(5) if (py + 1 - ky) % 2 == 0]
+                kxs = [kx for kx in range(5) if (px + 1 - kx) % 2 == 0]
+                taps = [((py + 1 - ky) // 2, (px + 1 - kx) // 2) for ky in kys for kx in kxs]
+                wk = [k5[ky, kx].T for ky in kys for kx in kxs]
+                y5[:, py::2, px::2] = emu_gather(x, taps, wk, [(t, c) for t in range(len(taps)) for c in range(4)], form,
+                                                 lh_first=True)
+        x = bn_act(f32(y5 + T64(wd["d_deconv5"]["bias"])), "d_deconv5")
+        got = (x @ T64(np.asarray(wd["d_deconv6"]["kernel"], np.float32))[0, 0].T + T64(wd["d_deconv6"]["bias"]))[..., 0].numpy()
+        out[form] = float(np.sqrt(np.mean((got - ref) ** 2)))
+        print(f"{form:6s} v_conv6 + dense + tail abs rms {out[form]:.3e}  rel {out[form] / rms:.2e}", flush=True)
+    print(f"three - four {out['three'] - out['four']:+.3e}")
+
+
 def main_groupings(N, seed, wd, mel, video, ref, rms):
     orig = K.conv_same
     v1 = make_conv("fp16x3", {"v_conv1"})
@@ -170,6 +321,8 @@ def main():
     print(f"N={N} seed={seed} output rms {rms:.4g}")
     if len(sys.argv) > 3 and sys.argv[3] == "groupings":
         return main_groupings(N, seed, wd, mel, video, ref, rms)
+    if len(sys.argv) > 3 and sys.argv[3] == "generic":
+        return main_generic(N, seed, wd, mel, video, ref, rms)
     for sname in SCHEMES:
         for lname, ls in layers_sets.items():
             if sname == "fp32" and lname != "v1-v5":
