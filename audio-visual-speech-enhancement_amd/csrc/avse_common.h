@@ -381,4 +381,21 @@ int launch_video_stats(const float* video, int64_t S, int H, int W, int F, float
 int launch_video_stats_u8(const uint8_t* video, int64_t S, int H, int W, int F, float* mean, float* stdv, void* scratch,
                           hipStream_t s);
 
+// ---- evaluate stage (eval.hip) ------------------------------------------------------------
+// avse_eval_pairs: the device copies of the host tables (eval_tables.cpp) and the call's geometry, passed by value.
+struct EvalDev {
+    const double* taps;    // [2 H + 1] resampling filter for (up, down)
+    const double* W;       // [256] STOI's frame window
+    const double* twid;    // [256] (re, im): e^{-2 pi i k / 512}
+    const double* segw;    // [win] the segmental SNR's window
+    const int* bands;      // [15] (lo, hi) bin ranges
+    int up, down, H;
+    int win, skip;         // segmental-SNR frame and hop
+    int stoi;              // 0: max(up, down) > 24, slots 3 and 4 are NaN and 0
+    int64_t cap;           // upper bound on off[n_pairs] - off[0] the scratch was sized for
+};
+size_t eval_pairs_scratch_bytes(int64_t n_pairs, const EvalDev& t);
+int launch_eval_pairs(const float* ref, const float* deg, const int64_t* off, int64_t n_pairs, const EvalDev& t,
+                      double* metrics, void* scratch, hipStream_t s);
+
 }  // namespace avse

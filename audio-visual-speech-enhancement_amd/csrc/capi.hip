@@ -15,6 +15,7 @@
 
 #include "../../include/avse.h"
 #include "avse_common.h"
+#include "eval_tables.h"
 #include "netplan.h"
 #include "spec_tables.h"
 #include "weight_pack.h"
@@ -71,11 +72,24 @@ struct IstftTables {
     float* gram_inv = nullptr;  // [n_mels][n_mels] (M M^T)^{-1} in float (n_mels == 80 only)
 };
 
+// device copies of the evaluate stage's tables (eval_tables.cpp), per sample rate
+struct EvalTables {
+    int sr = -1;
+    double* taps = nullptr;     // [2 H + 1]
+    double* W = nullptr;        // [256]
+    double* twid = nullptr;     // [256] (re, im)
+    double* segw = nullptr;     // [win]
+    int* bands = nullptr;       // [15] (lo, hi)
+    int up = 1, down = 1, H = 0, win = 0;
+};
+
 struct avse_ctx {
     int device = 0;
     Options opt;                // kernel-path switches (read from AVSE_* once, at creation)
     SpecTables spec;
     IstftTables istft;
+    EvalTables eval[4];         // the last four sample rates of avse_eval_pairs, replaced in turn
+    int eval_next = 0;
     float* frames = nullptr;    // ISTFT frame scratch
     size_t frames_bytes = 0;
     unsigned* umax = nullptr;
@@ -371,6 +385,41 @@ int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin,
     return 0;
 }
 
+// the resampling filter for sr -> 10 kHz, STOI's window / bands / twiddles and the segmental SNR's window
+int ensure_eval_tables(avse_ctx* c, int sr, hipStream_t s, const EvalTables** out) {
+    for (const EvalTables& have : c->eval)
+        if (have.sr == sr) {
+            *out = &have;
+            return 0;
+        }
+    if (s) {   // building and uploading tables allocates and copies: like the scratch, never inside a capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        AVSE_HIP_CHECK(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(AVSE_ERR_INVALID, "the tables of this sample rate would be built while the stream is being "
+                                          "captured: run one call with this rate before the capture");
+    }
+    EvalTables& t = c->eval[c->eval_next];
+    c->eval_next = (c->eval_next + 1) % 4;
+    *out = &t;
+    (void)hipFree(t.taps); (void)hipFree(t.W); (void)hipFree(t.twid); (void)hipFree(t.segw); (void)hipFree(t.bands);
+    t = EvalTables();
+    int up, down;
+    eval_ratio(sr, &up, &down);
+    const int win = seg_snr_window(sr);
+    // a rate STOI is not computed for gets the copy filter: the resampler does not run
+    const bool stoi = std::max(up, down) <= kEvalMaxRatio;
+    const std::vector<double> taps = stoi ? resample_taps(up, down) : resample_taps(1, 1);
+    if (int rc = table_to_device(taps, &t.taps)) return rc;
+    if (int rc = table_to_device(hann_inner(kStoiFrame), &t.W)) return rc;
+    if (int rc = table_to_device(stoi_twiddle(), &t.twid)) return rc;
+    if (int rc = table_to_device(hann_inner(win), &t.segw)) return rc;
+    if (int rc = table_to_device(stoi_bands(), &t.bands)) return rc;
+    t.up = up; t.down = down; t.H = ((int)taps.size() - 1) / 2; t.win = win;
+    t.sr = sr;
+    return 0;
+}
+
 // Pack one layer on the host (weight_pack.cpp: geometry, folded scale / shift, every weight layout) and upload it.
 int build_layer(avse_weights* W, int li, const float* kernel, const float* bias, const float* bn,
                 const Options& opt, int e_in = 0, int e_out = 0) {
@@ -577,6 +626,9 @@ void avse_ctx_destroy(avse_ctx* c) {
     (void)hipFree(c->spec.mel.start); (void)hipFree(c->spec.mel.width); (void)hipFree(c->spec.mel.weight);
     (void)hipFree(c->istft.pinvT); (void)hipFree(c->istft.twiddle); (void)hipFree(c->istft.window);
     (void)hipFree(c->istft.bins); (void)hipFree(c->istft.gram_inv);
+    for (EvalTables& t : c->eval) {
+        (void)hipFree(t.taps); (void)hipFree(t.W); (void)hipFree(t.twid); (void)hipFree(t.segw); (void)hipFree(t.bands);
+    }
     (void)hipFree(c->frames);
     (void)hipFree(c->umax);
     (void)hipFree(c->mse_partial);
@@ -1430,6 +1482,49 @@ int avse_mix_pairs(avse_ctx* c, const int16_t* speech, const int64_t* speech_off
     if (int rc = ensure_prep(c, mix_pairs_scratch_bytes(n_pairs), (hipStream_t)stream)) return rc;
     return launch_mix_pairs(speech, speech_off, noise, noise_off, snr_lin, n_pairs, L, rows, mix64, factor, c->prep,
                             (hipStream_t)stream);
+}
+
+int avse_eval_pairs(avse_ctx* c, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs, int sr,
+                    double* metrics, void* stream) {
+    return avse_eval_pairs_sized(c, ref, deg, off, n_pairs, 0, sr, metrics, stream);
+}
+
+int avse_eval_pairs_sized(avse_ctx* c, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
+                          int64_t total_samples, int sr, double* metrics, void* stream) {
+    if (!c || !ref || !deg || !off || !metrics) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (n_pairs < 1) return fail(AVSE_ERR_INVALID, "bad eval_pairs shape (n_pairs >= 1)");
+    if (sr < 8000 || sr > 48000) return fail(AVSE_ERR_INVALID, "sample rate outside 8000 .. 48000");
+    if (n_pairs >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "n_pairs must be below 2^31");
+    if (total_samples < 0 || total_samples > n_pairs * (1LL << 24))
+        return fail(AVSE_ERR_INVALID, "total_samples outside 0 .. n_pairs * 2^24");
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    // The pair lengths live on the device and the call does not wait for them.  The scratch is sized for
+    // total_samples, the caller's off[n_pairs] - off[0]; without it (0), for the most samples the two buffers can hold
+    // behind ref / deg (the extent of their allocations).  The kernels treat offsets that pass the bound as empty pairs.
+    int64_t cap = total_samples > 0 ? total_samples : n_pairs * (1LL << 24);
+    for (const float* p : {ref, deg}) {
+        if (total_samples > 0) break;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AVSE_ERR_INVALID, "ref / deg must point into device allocations (hipMalloc)");
+        }
+        const int64_t room = (int64_t)(((const char*)base + size) - (const char*)p) / (int64_t)sizeof(float);
+        cap = std::min(cap, room);
+    }
+    if (cap < 1) return fail(AVSE_ERR_INVALID, "ref / deg hold no samples");
+    const EvalTables* tables = nullptr;
+    if (int rc = ensure_eval_tables(c, sr, (hipStream_t)stream, &tables)) return rc;
+    const EvalTables& t = *tables;
+    EvalDev d;
+    d.taps = t.taps; d.W = t.W; d.twid = t.twid; d.segw = t.segw; d.bands = t.bands;
+    d.up = t.up; d.down = t.down; d.H = t.H;
+    d.win = t.win; d.skip = t.win / 4;
+    d.stoi = std::max(t.up, t.down) <= kEvalMaxRatio;
+    d.cap = cap;
+    if (int rc = ensure_prep(c, eval_pairs_scratch_bytes(n_pairs, d), (hipStream_t)stream)) return rc;
+    return launch_eval_pairs(ref, deg, off, n_pairs, d, metrics, c->prep, (hipStream_t)stream);
 }
 
 int avse_video_stats(avse_ctx* c, const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv,

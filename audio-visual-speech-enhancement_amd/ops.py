@@ -471,6 +471,98 @@ def mix_pairs(speech, noise, L, snr_db=0, return_mix64=True, device=None):
     return rows, mix64, factor
 
 
+def _eval_signals(x, name):
+    """eval_pairs' signal argument -> a list of 1-D signals (numpy arrays or tensors, int16 or floating point):
+    a sequence of 1-D (or [n, 1]) signals, or one 2-D array / tensor whose rows are the signals."""
+    if isinstance(x, (np.ndarray, torch.Tensor)):
+        if x.ndim != 2:
+            raise TypeError(f"{name}: a single array must be 2-D [pairs, samples]; pass a list for ragged signals")
+        x = list(x)
+    sigs = []
+    for k, a in enumerate(x):
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+        floating = a.dtype.is_floating_point if isinstance(a, torch.Tensor) else np.issubdtype(a.dtype, np.floating)
+        if not floating and a.dtype not in (torch.int16, np.dtype(np.int16)):
+            raise TypeError(f"{name}[{k}] must hold int16 or floating-point samples, got {a.dtype}")
+        if a.ndim == 2 and a.shape[1] == 1:
+            a = a[:, 0]
+        if a.ndim != 1:
+            raise TypeError(f"{name}[{k}] must be mono (1-D), got shape {tuple(a.shape)}")
+        sigs.append(a)
+    return sigs
+
+
+def _pack_f32(sigs, dev):
+    """Signals (already cut) -> one 1-D float32 tensor on `dev`: one concatenation on the side the signals live on."""
+    if all(isinstance(a, np.ndarray) for a in sigs):
+        return torch.from_numpy(np.concatenate([a.astype(np.float32, copy=False) for a in sigs])).to(dev)
+    return torch.cat([(a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)))
+                      .to(device=dev, dtype=torch.float32) for a in sigs])
+
+
+EVAL_MAX_SAMPLES = 1 << 24
+
+
+def eval_pairs(ref, deg, sample_rate=16000, device=None):
+    """The evaluate stage (speech_enhancement_evaluator.py:34-64 with open measures in PESQ's place): SNR, SI-SDR,
+    segmental SNR and STOI of n (clean, degraded) pairs in one avse_eval_pairs call (include/avse.h has the definitions).
+
+    ref / deg: sequences of mono signals (numpy or tensors, int16 or floating point, ragged), or one 2-D array / tensor
+    [n, samples] each; pair u is cut to min(len ref[u], len deg[u]).  Device tensors are packed on the device (no host
+    copy).  Or the packed form: ref = (1-D float32 device tensor, int64 offsets [n + 1]) and deg = a 1-D float32 device
+    tensor laid out by the same offsets.
+    Returns a float64 device tensor [n, 5]: snr, si_sdr, seg_snr, stoi, stoi_kept (_lib.EVAL_METRIC_NAMES)."""
+    sr = int(sample_rate)
+    if not 8000 <= sr <= 48000:
+        raise ValueError(f"sample_rate {sample_rate} outside 8000 .. 48000")
+    if _is_packed(ref):
+        rp, off = ref
+        dp = deg[0] if _is_packed(deg) else deg
+        for t, name in ((rp, "ref"), (dp, "deg")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError(f"{name}: the packed samples must be a ROCm device tensor")
+            if t.dtype != torch.float32 or t.ndim != 1 or not t.is_contiguous():
+                raise TypeError(f"{name}: the packed samples must be a contiguous 1-D float32 tensor")
+        off = np.ascontiguousarray(np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off), dtype=np.int64)
+        if off.ndim != 1 or off.size < 2 or off[0] < 0 or np.any(np.diff(off) < 0) or \
+                off[-1] > min(rp.numel(), dp.numel()):
+            raise ValueError("offsets must be [n + 1] non-decreasing element offsets into both packed buffers")
+        dev = rp.device
+    else:
+        rs, ds = _eval_signals(ref, "ref"), _eval_signals(deg, "deg")
+        if len(rs) != len(ds):
+            raise ValueError(f"{len(rs)} reference signals but {len(ds)} degraded signals")
+        if not rs:
+            raise ValueError("eval_pairs needs at least one pair")
+        lens = [min(int(a.shape[0]), int(b.shape[0])) for a, b in zip(rs, ds)]
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        dev = None
+    n = off.size - 1
+    lens = np.diff(off)
+    if np.any(lens == 0):
+        raise _lib.AvseError(f"avse_eval_pairs refused (status 1, AVSE_ERR_INVALID): pair {int(np.argmin(lens))} is empty")
+    if np.any(lens > EVAL_MAX_SAMPLES):
+        raise _lib.AvseError(f"avse_eval_pairs refused (status 1, AVSE_ERR_INVALID): pair {int(np.argmax(lens))} has "
+                             f"more than 2^24 samples")
+    if dev is None:      # only now: every refusal above happens before anything touches a device
+        for t in rs + ds:
+            if isinstance(t, torch.Tensor) and t.is_cuda and device is None:
+                device = t.device
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        rp = _pack_f32([a[:k] for a, k in zip(rs, lens)], dev)
+        dp = _pack_f32([a[:k] for a, k in zip(ds, lens)], dev)
+    ctx = _lib.context(dev)
+    off_d = torch.from_numpy(off).to(dev)
+    out = torch.empty((n, _lib.AVSE_EVAL_NMETRICS), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        # the offsets were built here: the scratch is sized for their span, not for the buffers' allocations
+        _lib.check(_lib.load().avse_eval_pairs_sized(ctx.handle, _lib.ptr(rp), _lib.ptr(dp), _lib.ptr(off_d), n,
+                                                     int(off[-1] - off[0]), sr, _lib.ptr(out),
+                                                     _lib.stream_handle(dev)), "avse_eval_pairs")
+    return out
+
+
 def mse(pred, target):
     """Keras mean_squared_error over every element -> 0-dim device tensor."""
     _dev_f32(pred, "pred")

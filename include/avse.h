@@ -32,7 +32,8 @@ extern "C" {
  *    status AVSE_ERR_CHECK (checked build)
  * 3: AVSE_F32_SPLIT range guard (avse_forward_checked, avse_range_status, status AVSE_ERR_RANGE), per-layer activation
  *    exponents (avse_weights_act_exponents, option no_act_scale); later additions under the same version (new symbols
- *    only, nothing existing changed): avse_mix_pairs, avse_video_stats */
+ *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
+ *    avse_eval_pairs_sized */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -397,6 +398,73 @@ int avse_trainer_iterations(avse_trainer* t, int64_t* iterations);
  * ISTFT chunk frame ranges); avse_spectrogram / avse_istft / avse_forward then synchronise their stream and return
  * AVSE_ERR_CHECK with the first failing check (kernel, check, block, thread, value, expected) in avse_last_error. */
 int avse_build_flags(void);
+
+/* ---- evaluate ---------------------------------------------------------------------------- */
+
+enum avse_eval_metric { AVSE_EVAL_SNR = 0, AVSE_EVAL_SI_SDR = 1, AVSE_EVAL_SEG_SNR = 2,
+                        AVSE_EVAL_STOI = 3, AVSE_EVAL_STOI_KEPT = 4 };
+#define AVSE_EVAL_NMETRICS 5
+/* Replaces speech_enhancement_evaluator.py:34-64 (the per-sample measure; PESQ itself stays an external binary).
+ * Four open measures of a (clean, degraded) pair, for a ragged group of pairs in one call.
+ *   ref, deg   float32 samples of n_pairs utterances, concatenated; pair u is [off[u], off[u + 1]) in BOTH buffers
+ *              (the caller has cut each pair to a common length), at any element offset
+ *   off        [n_pairs + 1] int64 element offsets (device array), ascending
+ *   sr         sample rate of every pair, 8000 .. 48000
+ *   metrics    [n_pairs][AVSE_EVAL_NMETRICS] float64
+ * Returns AVSE_ERR_INVALID for a NULL argument, n_pairs < 1, sr outside 8000 .. 48000, or a pair of more than 2^24
+ * samples.  The offsets are read on the device only: the caller, who built them, checks the pair lengths on the host
+ * (the Python binding does), and this entry point trusts them as avse_mix_pairs does.  What the device does with
+ * offsets that break the contract is bounded all the same: a pair longer than 2^24 samples, a descending offset, or
+ * offsets that pass the end of the allocations holding ref / deg, is treated as a pair of 0 samples.
+ * A pair of 0 samples gives NaN in every slot.
+ *
+ * All arithmetic is float64 on s = ref, y = deg (n samples), eps = 2^-52.
+ *  SNR      10 log10(sum s^2 / sum (s - y)^2).
+ *  SI-SDR   alpha = sum s y / sum s^2;  10 log10(alpha^2 sum s^2 / sum (alpha s - y)^2).  No mean is removed.
+ *           Two passes (the sums, then the residual with alpha): deg == ref gives alpha == 1.0 and a residual of
+ *           exactly 0, so SNR and SI-SDR are both +inf; sum s^2 == 0 gives NaN in both.
+ *  Segmental SNR   win = round(0.03 sr) (halves up), skip = win / 4 as an integer, w[i] = 0.5 (1 - cos(2 pi (i + 1) /
+ *           (win + 1))); frames start at i = 0, skip, .. while i + win <= n; per frame
+ *           v = 10 log10(sum (w s)^2 / (sum (w (s - y))^2 + eps) + eps) clamped to [-10, 35]; the result is the mean
+ *           over the frames, NaN without frames.
+ *  STOI     (Taal et al. 2011; fs = 10 kHz, 256-sample frames, hop 128, 512-point FFT, 15 third-octave bands from
+ *           150 Hz, 30-frame segments, beta = -15 dB, 40 dB dynamic range)
+ *    1. Resample both signals by up / down = (10000 / g) / (sr / g), g = gcd(10000, sr), as
+ *       scipy.signal.resample_poly(x, up, down) does with its defaults: H = 10 max(up, down), fc = 1 / max(up, down),
+ *       h[i] = up fc sinc(fc (i - H)) I0(5 sqrt(1 - ((i - H) / H)^2)) / I0(5), i = 0 .. 2H, normalised so that
+ *       sum(h) / up == 1; n10 = ceil(n up / down) outputs, y10[k] = sum_j h[H + k down - j up] x[j] over the j that keep
+ *       the tap index in [0, 2H].  up == down is a copy.  (This is scipy's filter, not the MATLAB / pystoi one: values
+ *       may differ from those tools in the low decimals.)  STOI is computed when max(up, down) <= 24; otherwise slots
+ *       3 and 4 are NaN and 0 and the other metrics are still computed.
+ *    2. Silent-frame removal: W[i] = 0.5 (1 - cos(2 pi (i + 1) / 257)), i < 256; frames start at i = 0, 128, .. while
+ *       i < n10 - 256 (strict); e_i = 20 log10(||W x_i|| + eps) from the clean signal; a frame is kept when
+ *       e_i > max(e) - 40.  K, the number of kept frames, is slot AVSE_EVAL_STOI_KEPT.  The kept windowed frames of
+ *       both signals (the clean signal's mask) are overlap-added at hop 128 in order: (K - 1) 128 + 256 samples.
+ *    3. Band spectra: the overlap-added signals are framed again by the same rule (M = K - 1 frames), windowed by W,
+ *       zero-padded to 512; X[j][m], Y[j][m] = sqrt(sum of |rfft|^2 over the bins [lo_j, hi_j)), the bins nearest to
+ *       150 2^(j/3) 2^(-+1/6) Hz on the grid of 10000 / 512 Hz: (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34)
+ *       (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219).
+ *    4. For m = 30 .. M and each band j, over the 30 frames ending at m: a = sqrt(sum X^2 / (sum Y^2 + eps)),
+ *       Y' = min(a Y, X (1 + 10^(15/20))), d = sum (X - mean X)(Y' - mean Y') / (||X - mean X|| ||Y' - mean Y'|| + eps).
+ *       STOI = the mean of d over all j and m; NaN when M < 30 (no frames at all included).
+ * Determinism: no floating-point atomics; every sum has an order fixed by the pair's own length (16 partial sums per
+ * pair combined in part order; frame and segment values stored, then summed in index order by contiguous runs), so two
+ * calls agree bit for bit and a pair's five numbers are the same bits alone and inside any batch, at any offset.
+ * The call is asynchronous on `stream` and does not synchronise.  Scratch comes from the context and grows outside a
+ * stream capture only.  The pair lengths are not known on the host, so this entry point sizes the scratch (up to about
+ * 25 bytes per sample) for the most samples the allocations holding ref / deg have room for behind the two pointers
+ * (hipMemGetAddressRange; pointers outside such allocations are refused): under a caching allocator that can be far
+ * more than the data.  A caller who knows off[n_pairs] - off[0] uses avse_eval_pairs_sized, which sizes the scratch for
+ * exactly that and takes any device pointer.  The tables of a sample rate are built and uploaded at the first call with
+ * that rate, outside a capture; the context keeps the last four rates, and a call that builds tables (a new rate, or a
+ * fifth one replacing the oldest) allocates, copies and frees, which synchronises the device. */
+int avse_eval_pairs(avse_ctx* ctx, const float* ref, const float* deg, const int64_t* off,
+                    int64_t n_pairs, int sr, double* metrics, void* stream);
+/* avse_eval_pairs with total_samples = off[n_pairs] - off[0] as the caller, who built the offsets, knows it
+ * (1 .. n_pairs * 2^24; 0 = unknown, which is avse_eval_pairs).  The scratch is sized for that many samples; offsets
+ * that pass it make their pairs empty (NaN rows), nothing is written out of bounds. */
+int avse_eval_pairs_sized(avse_ctx* ctx, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
+                          int64_t total_samples, int sr, double* metrics, void* stream);
 
 /* Number of forward scratch buffers reported by avse_debug_scratch. */
 #define AVSE_DEBUG_NBUF 20
