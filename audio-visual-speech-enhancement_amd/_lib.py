@@ -62,6 +62,11 @@ SIGNATURES = {
                                 _int, _int, _c_void_p, _c_void_p, _c_void_p]),
     "avse_istft": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _int, _int, _int, _flt, _flt,
                           _c_void_p, _c_void_p]),
+    # the ragged forms: (sig, host sig_off, host n_samples, n_utt, ...) / (mel, stft, host n_frames, host stft_frames, ...)
+    "avse_spectrogram_ragged": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _flt,
+                                       _flt, _flt, _flt, _int, _int, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_istft_ragged": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _int, _int,
+                                 _int, _flt, _flt, _c_void_p, _c_void_p]),
     "avse_weights_blob_floats": (_i64, []),
     "avse_weights_load": (_int, [_c_void_p, _c_void_p, _i64, _int, ctypes.POINTER(_c_void_p)]),
     "avse_weights_blob_floats_shape": (_i64, [_int, _int]),

@@ -6,6 +6,7 @@
 
 #include "layer_geom.h"
 #include "options.h"
+#include "ragged_geom.h"
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -129,6 +130,19 @@ struct SpecArgs {
 
 int launch_spectrogram(const SpecArgs& a, hipStream_t s);
 
+// Ragged batches (ragged_geom.h): the device copies of a RaggedGeom's rows, in the context's preprocess scratch.
+struct RaggedDev {
+    const RaggedUtt* utt;      // [n_utt]
+    const RaggedItem* items;   // [n_items]
+    int n_utt, n_items;
+};
+// frames per block of the kernel a ragged STFT of this shape runs in (k_spec640 / k_spec533); 0: no ragged kernel,
+// the launcher walks the batch's equal-length runs through launch_spectrogram
+int spectrogram_ragged_chunk(int n_fft, int hop, int n_mels, int mel_max_width);
+// a.sig / a.mel_db / a.stft_ri are the packed buffers' bases, a.n_utt the batch; a.n_samples / n_frames / n_slices are
+// ignored (per utterance in g).  One run: launch_spectrogram itself.  d may be empty where no ragged kernel runs.
+int launch_spectrogram_ragged(const SpecArgs& a, const RaggedGeom& g, const RaggedDev& d, hipStream_t s);
+
 struct IstftArgs {
     const float* mel_db;      // spf > 0: [n_utt][n_slices][n_mels][spf], else [n_utt][n_mels][T]
     int spf, n_slices;
@@ -152,6 +166,12 @@ struct IstftArgs {
 };
 
 int launch_istft(const IstftArgs& a, hipStream_t s);
+
+// output hops per block of k_istft_fused where it serves the shape (inverse size 640 / hop 160 / 80 bands, the
+// tridiagonal tables present); 0: no ragged kernel, the launcher walks the runs through launch_istft
+int istft_ragged_chunk(int N, int hop, int n_mels, bool fused_tables);
+// the ragged twin (a.T / stft_frames / n_slices ignored): one run is launch_istft itself
+int launch_istft_ragged(const IstftArgs& a, const RaggedGeom& g, const RaggedDev& d, hipStream_t s);
 
 // ---- implicit-GEMM convolution ----------------------------------------------------------
 struct ConvArgs {

@@ -105,6 +105,11 @@ struct avse_ctx {
     size_t arena_bytes = 0;
     char* prep = nullptr;       // avse_mix_pairs / avse_video_stats scratch (power words, per-chunk moments)
     size_t prep_bytes = 0;
+    // ragged STFT / ISTFT: the pinned host copy of the per-utterance rows and the item table (uploaded into `prep`),
+    // and the event after which the last upload has read it
+    char* ragged_host = nullptr;
+    size_t ragged_host_bytes = 0;
+    hipEvent_t ragged_done = nullptr;
     NetPlan last_plan = kPlan25;    // the network shape of the last forward (avse_debug_scratch's arena layout)
     // side stream for the audio branch of the forward (runs concurrently with the video encoder)
     hipStream_t side = nullptr;
@@ -334,6 +339,38 @@ int ensure_prep(avse_ctx* c, size_t need, hipStream_t s) {
     c->prep_bytes = 0;
     if (hipMalloc((void**)&c->prep, need) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (preprocess scratch)");
     c->prep_bytes = need;
+    return 0;
+}
+
+// Uploads a ragged batch's rows and item table (ragged_geom.h) into the preprocess scratch on `s` and points *d at
+// them.  The scratch and the pinned staging copy grow outside a stream capture only, like the scratch itself.
+int upload_ragged(avse_ctx* c, const RaggedGeom& g, hipStream_t s, RaggedDev* d) {
+    const size_t ub = sizeof(RaggedUtt) * g.utt.size(), ib = sizeof(RaggedItem) * g.items.size();
+    const size_t need = ub + ib;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (s) AVSE_HIP_CHECK(hipStreamIsCapturing(s, &cs));
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (int rc = ensure_prep(c, need, s)) return rc;
+    if (!capturing && c->ragged_done) AVSE_HIP_CHECK(hipEventSynchronize(c->ragged_done));   // the last upload has read it
+    if (need > c->ragged_host_bytes) {
+        if (capturing)
+            return fail(AVSE_ERR_INVALID, "the ragged tables would grow while the stream is being captured: run one "
+                                          "call of this size before the capture");
+        (void)hipHostFree(c->ragged_host);
+        c->ragged_host = nullptr;
+        c->ragged_host_bytes = 0;
+        if (hipHostMalloc((void**)&c->ragged_host, need) != hipSuccess) return fail(AVSE_ERR_OOM, "hipHostMalloc failed (ragged tables)");
+        c->ragged_host_bytes = need;
+    }
+    if (!c->ragged_done) AVSE_HIP_CHECK(hipEventCreateWithFlags(&c->ragged_done, hipEventDisableTiming));
+    std::memcpy(c->ragged_host, g.utt.data(), ub);
+    std::memcpy(c->ragged_host + ub, g.items.data(), ib);
+    AVSE_HIP_CHECK(hipMemcpyAsync(c->prep, c->ragged_host, need, hipMemcpyHostToDevice, s));
+    if (!capturing) AVSE_HIP_CHECK(hipEventRecord(c->ragged_done, s));
+    d->utt = reinterpret_cast<const RaggedUtt*>(c->prep);
+    d->items = reinterpret_cast<const RaggedItem*>(c->prep + ub);
+    d->n_utt = (int)g.utt.size();
+    d->n_items = (int)g.items.size();
     return 0;
 }
 
@@ -638,6 +675,8 @@ void avse_ctx_destroy(avse_ctx* c) {
     (void)hipFree(c->zero_video);
     (void)hipFree(c->arena);
     (void)hipFree(c->prep);
+    (void)hipHostFree(c->ragged_host);
+    if (c->ragged_done) (void)hipEventDestroy(c->ragged_done);
     for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
     if (c->cap) (void)hipStreamDestroy(c->cap);
     if (c->side) (void)hipStreamDestroy(c->side);
@@ -798,6 +837,122 @@ int avse_istft(avse_ctx* c, const float* mel_db, const float* stft_ri, int64_t n
     a.bins = c->istft.bins;
     a.gram_inv = c->opt.dense_istft ? nullptr : c->istft.gram_inv;
     if (int lr = launch_istft(a, (hipStream_t)stream)) return lr;
+    return debug_poll(stream);
+}
+
+int avse_spectrogram_ragged(avse_ctx* c, const float* sig, const int64_t* sig_off, const int64_t* n_samples,
+                            int64_t n_utt, int sr, int n_fft, int hop, int n_mels, float fmin, float fmax, float amin,
+                            float top_db, int pad_mode, int frames_per_slice, float* mel_db, float* stft_ri,
+                            void* stream) {
+    if (!c || !sig || !sig_off || !n_samples || !mel_db) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (n_utt < 0 || sr <= 0 || hop <= 0 || n_fft < 2) return fail(AVSE_ERR_INVALID, "bad spectrogram geometry");
+    if (n_fft > 2048) return fail(AVSE_ERR_UNSUPPORTED, "n_fft > 2048 not supported");
+    if (n_mels < 1 || n_mels > 80) return fail(AVSE_ERR_UNSUPPORTED, "n_mels must be in [1, 80]");
+    if (pad_mode != AVSE_PAD_REFLECT && pad_mode != AVSE_PAD_CONSTANT) return fail(AVSE_ERR_INVALID, "bad pad_mode");
+    if (frames_per_slice < 0) return fail(AVSE_ERR_INVALID, "frames_per_slice < 0");
+    if (n_utt > INT32_MAX) return fail(AVSE_ERR_INVALID, ragged_message(RAGGED_TOO_LARGE));
+    // chunk: that of the kernel this n_fft runs in (the band table's width, known only with the tables, can still send
+    // n_fft 533 to the run dispatch: the item table is then not used)
+    const int chunk = spectrogram_ragged_chunk(n_fft, hop, n_mels, 0);
+    const RaggedGeom g = ragged_spec_geom(sig_off, n_samples, n_utt, n_fft, hop, frames_per_slice, n_mels,
+                                          pad_mode == AVSE_PAD_REFLECT, chunk > 0 ? chunk : 1 << 30);
+    if (g.status != RAGGED_OK)
+        return fail(AVSE_ERR_INVALID, std::string(ragged_message(g.status)) + " (utterance " + std::to_string(g.bad_utt) + ")");
+    if (n_utt == 0) return 0;
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = ensure_spec_tables(c, sr, n_fft, n_mels, fmin, fmax);
+    if (rc) return rc;
+    if (n_utt > c->umax_cap) {
+        (void)hipFree(c->umax);
+        c->umax = nullptr;
+        c->umax_cap = 0;
+        AVSE_HIP_CHECK(hipMalloc((void**)&c->umax, sizeof(unsigned) * n_utt));
+        c->umax_cap = n_utt;
+    }
+    SpecArgs a;
+    a.sig = sig;
+    a.n_utt = n_utt;
+    a.n_samples = 0;          // per utterance (g)
+    a.n_fft = n_fft;
+    a.hop = hop;
+    a.n_frames = 0;
+    a.n_mels = n_mels;
+    a.amin = amin;
+    a.db_floor = (float)(20.0 * std::log10((double)amin));   // exact value for clamped bins
+    a.top_db = top_db;
+    a.pad_mode = pad_mode;
+    a.spf = frames_per_slice;
+    a.n_slices = 0;
+    a.mel_db = mel_db;
+    a.stft_ri = stft_ri;
+    a.twiddle = c->spec.twiddle;
+    a.window = c->spec.window;
+    a.mel_start = c->spec.mel.start;
+    a.mel_width = c->spec.mel.width;
+    a.mel_weight = c->spec.mel.weight;
+    a.mel_max_width = c->spec.mel.max_width;
+    std::memcpy(a.mel_seg_nq, c->spec.mel.seg_nq, sizeof(a.mel_seg_nq));
+    std::memcpy(a.mel_seg_nq4, c->spec.mel.seg_nq4, sizeof(a.mel_seg_nq4));
+    a.umax = c->umax;
+    RaggedDev d = {nullptr, nullptr, 0, 0};
+    if (g.runs.size() > 1 && spectrogram_ragged_chunk(n_fft, hop, n_mels, a.mel_max_width) > 0)
+        if (int ur = upload_ragged(c, g, (hipStream_t)stream, &d)) return ur;
+    if (int lr = launch_spectrogram_ragged(a, g, d, (hipStream_t)stream)) return lr;
+    return debug_poll(stream);
+}
+
+int avse_istft_ragged(avse_ctx* c, const float* mel_db, const float* stft_ri, const int64_t* n_frames,
+                      const int64_t* stft_frames, int64_t n_utt, int frames_per_slice, int sr, int n_fft, int hop,
+                      int n_mels, float fmin, float fmax, float* sig, void* stream) {
+    if (!c || !mel_db || !stft_ri || !n_frames || !stft_frames || !sig) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (n_utt < 0 || hop <= 0 || sr <= 0 || n_fft < 2) return fail(AVSE_ERR_INVALID, "bad istft geometry");
+    if (n_fft > 2048) return fail(AVSE_ERR_UNSUPPORTED, "n_fft > 2048 not supported");
+    if (n_mels < 1 || n_mels > 80) return fail(AVSE_ERR_UNSUPPORTED, "n_mels must be in [1, 80]");
+    if (frames_per_slice < 0) return fail(AVSE_ERR_INVALID, "frames_per_slice < 0");
+    if (n_utt > INT32_MAX) return fail(AVSE_ERR_INVALID, ragged_message(RAGGED_TOO_LARGE));
+    const int nb = 1 + n_fft / 2, N = 2 * (nb - 1);
+    // chunk: the fused kernel's where the shape can run in it (without its tables the run dispatch serves, and the
+    // item table is not used)
+    const int chunk = istft_ragged_chunk(N, hop, n_mels, true);
+    const RaggedGeom g = ragged_istft_geom(n_frames, stft_frames, n_utt, frames_per_slice, nb, hop, n_mels,
+                                           chunk > 0 ? chunk : 1 << 30);
+    if (g.status != RAGGED_OK)
+        return fail(AVSE_ERR_INVALID, std::string(ragged_message(g.status)) + " (utterance " + std::to_string(g.bad_utt) + ")");
+    if (n_utt == 0) return 0;
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = ensure_istft_tables(c, sr, n_fft, n_mels, fmin, fmax);
+    if (rc) return rc;
+    IstftArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.nb = nb; a.hop = hop; a.n_mels = n_mels;
+    a.gram_inv = c->opt.dense_istft ? nullptr : c->istft.gram_inv;
+    a.bins = c->istft.bins;
+    const bool in_kernel = g.runs.size() > 1 && istft_ragged_chunk(N, hop, n_mels, a.gram_inv && a.bins) > 0;
+    if (!in_kernel) {   // the unfused kernels' frame scratch, for the largest run
+        size_t need = 0;
+        for (const RaggedRun& r : g.runs)
+            need = std::max(need, sizeof(float) * (size_t)r.count * (size_t)g.utt[r.first].T * N);
+        if (need > c->frames_bytes) {
+            (void)hipFree(c->frames);
+            c->frames = nullptr;
+            c->frames_bytes = 0;
+            if (hipMalloc((void**)&c->frames, need) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (istft scratch)");
+            c->frames_bytes = need;
+        }
+    }
+    a.mel_db = mel_db;
+    a.spf = frames_per_slice;
+    a.stft = reinterpret_cast<const float2*>(stft_ri);
+    a.n_utt = n_utt;
+    a.pinvT = c->istft.pinvT;
+    a.twiddle = c->istft.twiddle;
+    a.window = c->istft.window;
+    a.frames = c->frames;
+    a.sig = sig;
+    RaggedDev d = {nullptr, nullptr, 0, 0};
+    if (in_kernel && !g.items.empty())
+        if (int ur = upload_ragged(c, g, (hipStream_t)stream, &d)) return ur;
+    if (int lr = launch_istft_ragged(a, g, d, (hipStream_t)stream)) return lr;
     return debug_poll(stream);
 }
 

@@ -13,7 +13,9 @@
 // 29.97 / 30 fps) is a 28 x 19 prime-factor DFT; k_istft_dft handles other sizes with a direct inverse DFT.  k_ola sums the <= 4
 // overlapping frames of each output sample in increasing frame order (librosa's order), divides by
 // the window sum-square where it exceeds float32 tiny, and drops n_fft/2 samples at both ends.
+// avse_istft_ragged (mixed lengths in one launch, ragged_geom.h): k_istft_fused<true> and launch_istft_ragged below.
 #include <algorithm>
+#include <type_traits>
 
 #include "avse_common.h"
 #include "fft_common.h"
@@ -203,7 +205,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t ist_rsrc(const void* base, lon
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
 }
 
-__global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(IstftArgs a, int n_chunks, int n_items) {
+// RG: the ragged form (avse_istft_ragged).  An item is (u, chunk) of the item table; the utterance's frame counts
+// and the offsets of its mel block, its STFT and its output come from its RaggedUtt row, for the item being computed
+// and, in the prefetch, for the NEXT item: its loads go through buffer resources that cover that utterance's own mel
+// block and STFT, nothing else.  The equal-length instantiation keeps its chunk-count parameter and its code.
+template <bool RG = false>
+__global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(IstftArgs a, std::conditional_t<RG, RaggedDev, int> geo,
+                                                                             int n_items) {
     __shared__ float2 zbuf[FW * ZS];            // frame f's slot: zbuf + f * ZS (Z', then 640 time samples)
     // amplitudes, then y in place; odd row pitch (81 floats): the MFMA fragment reads (16 consecutive frames at one
     // band) are conflict-free and step 3's frame-pair lanes 2-way (a pitch of 80 put them on 2 banks)
@@ -215,8 +223,10 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
     __shared__ float ginv_l[NMEL * NMEL];       // (M M^T)^{-1} for the MFMA solve of step 2
     __shared__ float2 tw[640];                  // W640^k
     __shared__ float4 bins_l[321];              // per bin: the two pinv weights and the first mel band
-    const int T = a.T, n_mels = a.n_mels;
-    const long long Lout = (long long)a.hop * (T - 1);
+    const int Tb = a.T, n_mels = a.n_mels;
+    const long long Lout_b = (long long)a.hop * (Tb - 1);
+    int n_chunks = 0;
+    if constexpr (!RG) n_chunks = geo;
 
     // tables -> LDS once per (persistent) block: the DFT twiddles and bin weights were global-memory reads in
     // every item's dependency chain
@@ -257,12 +267,21 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
     auto issue_loads = [&](int item, int part) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        const int u = item / n_chunks, b = item - u * n_chunks;
+        RaggedItem ri = {};
+        RaggedUtt ru = {};
+        if constexpr (RG) {
+            ri = geo.items[item];
+            ru = geo.utt[ri.u];
+        }
+        const int T = RG ? ru.T : Tb;
+        const int u = RG ? ri.u : item / n_chunks, b = RG ? ri.chunk : item - u * n_chunks;
         const int t_lo = max(0, b * OF - 1);
         const int nfr = min(T - 1, b * OF + OF + 1) - t_lo + 1;
         if (part < 0) {
-            const long long mel_u = a.spf > 0 ? (long long)a.n_slices * n_mels * a.spf : (long long)n_mels * T;
-            const __amdgpu_buffer_rsrc_t rsM = ist_rsrc(a.mel_db + u * mel_u, mel_u * 4);
+            const long long mel_u = RG        ? (long long)n_mels * T
+                                    : a.spf > 0 ? (long long)a.n_slices * n_mels * a.spf
+                                                : (long long)n_mels * T;
+            const __amdgpu_buffer_rsrc_t rsM = ist_rsrc(a.mel_db + (RG ? ru.mel_off : u * mel_u), mel_u * 4);
 #pragma unroll
             for (int j = 0; j < IT1; ++j) {
                 const int it = min(tid + 64 * IWAVES * j, FW * n_mels - 1);
@@ -281,16 +300,16 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
             }
             return;
         }
-        const long long stft_u = (long long)a.nb * a.stft_frames;
-        const __amdgpu_buffer_rsrc_t rsD = ist_rsrc(a.stft + u * stft_u, stft_u * 8);
+        const long long stft_u = (long long)a.nb * (RG ? ru.L : a.stft_frames);
+        const __amdgpu_buffer_rsrc_t rsD = ist_rsrc(a.stft + (RG ? ru.in_off : u * stft_u), stft_u * 8);
 #pragma unroll
         for (int j = 0; j < IT3; ++j) {
             if (j != part) continue;
             const int it = tid + 64 * IWAVES * j;
             const int k = it / FP, f = 2 * (it - FP * k);
             if (k <= 160 && f < nfr) {   // the pair's second frame may lie past the chunk / utterance: not used
-                const int ok = (k * a.stft_frames + t_lo + f) * 8;
-                const int om = ((k == 0 ? 320 : 320 - k) * a.stft_frames + t_lo + f) * 8;
+                const int ok = (k * (RG ? ru.L : a.stft_frames) + t_lo + f) * 8;
+                const int om = ((k == 0 ? 320 : 320 - k) * (RG ? ru.L : a.stft_frames) + t_lo + f) * 8;
                 dk[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsD, ok, 0, 0));
                 dm[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsD, om, 0, 0));
             }
@@ -308,7 +327,15 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));           // keep index math inside the loop (see k_spec640)
         const int lane = tid & 63, wave = tid >> 6;
-        const int u = item / n_chunks, b = item - u * n_chunks;
+        RaggedItem ri = {};
+        RaggedUtt ru = {};
+        if constexpr (RG) {
+            ri = geo.items[item];
+            ru = geo.utt[ri.u];
+        }
+        const int T = RG ? ru.T : Tb;
+        const long long Lout = RG ? (long long)a.hop * (T - 1) : Lout_b;
+        const int u = RG ? ri.u : item / n_chunks, b = RG ? ri.chunk : item - u * n_chunks;
         const int t_lo = max(0, b * OF - 1);
         const int t_hi = min(T - 1, b * OF + OF + 1);
         const int nfr = t_hi - t_lo + 1;
@@ -465,7 +492,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
         {
             const long long i0 = (long long)b * OF * 160;
             const int n_out = (int)min((long long)OF * 160, Lout - i0);
-            float* __restrict__ out = a.sig + (long long)u * Lout + i0;
+            float* __restrict__ out = a.sig + (RG ? ru.out_off : (long long)u * Lout) + i0;
 #pragma unroll 1
             for (int j = tid; j < n_out; j += 64 * IWAVES) {
                 const int p = (int)(i0 + j) + 320;                 // position in the untrimmed signal
@@ -746,7 +773,7 @@ int launch_istft(const IstftArgs& a, hipStream_t s) {
         AVSE_HIP_CHECK(hipGetDevice(&dev));
         AVSE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         const int grid = (int)std::min<long long>(items, (long long)AVSE_ISTFT_BPC * cus);
-        hipLaunchKernelGGL(k_istft_fused, dim3(grid), dim3(64 * IWAVES), 0, s, a, n_chunks, (int)items);
+        hipLaunchKernelGGL(k_istft_fused<false>, dim3(grid), dim3(64 * IWAVES), 0, s, a, n_chunks, (int)items);
         AVSE_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -773,6 +800,42 @@ int launch_istft(const IstftArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k_ola, dim3((unsigned)(g < 1 ? 1 : g)), dim3(256), 0, s, a);
         AVSE_HIP_CHECK(hipGetLastError());
     }
+    return 0;
+}
+
+int istft_ragged_chunk(int N, int hop, int n_mels, bool fused_tables) {
+    return N == 640 && hop == 160 && n_mels == NMEL && fused_tables ? OF : 0;
+}
+
+int launch_istft_ragged(const IstftArgs& a0, const RaggedGeom& g, const RaggedDev& d, hipStream_t s) {
+    if (a0.n_utt <= 0) return 0;
+    if (g.runs.size() == 1 || istft_ragged_chunk(a0.N, a0.hop, a0.n_mels, a0.gram_inv && a0.bins) == 0) {
+        // the equal-length launch on each run of utterances: a run has the equal-length layout
+        for (const RaggedRun& r : g.runs) {
+            const RaggedUtt& ru = g.utt[r.first];
+            IstftArgs a = a0;
+            a.mel_db = a0.mel_db + ru.mel_off;
+            a.n_slices = ru.S;
+            a.stft = a0.stft + ru.in_off;
+            a.stft_frames = ru.L;
+            a.n_utt = r.count;
+            a.T = ru.T;
+            a.sig = a0.sig + ru.out_off;
+            if (int rc = launch_istft(a, s)) return rc;
+        }
+        return 0;
+    }
+    if (g.items.empty()) return 0;   // no utterance has two frames: nothing to write
+    if (!d.utt || !d.items || d.n_items != (int)g.items.size()) {
+        set_error("ragged istft: no item table");
+        return 1;   // AVSE_ERR_INVALID
+    }
+    int dev = 0, cus = 256;
+    AVSE_HIP_CHECK(hipGetDevice(&dev));
+    AVSE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int grid = (int)std::min<long long>(d.n_items, (long long)AVSE_ISTFT_BPC * cus);
+    hipLaunchKernelGGL(k_istft_fused<true>, dim3(grid), dim3(64 * IWAVES), 0, s, a0, d, d.n_items);
+    AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }
 

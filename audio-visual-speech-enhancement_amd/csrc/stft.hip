@@ -18,9 +18,14 @@
 // [80, T] array, including the frame the slicing later drops) happens in-kernel; otherwise each
 // chunk publishes its max with an ordered-uint atomicMax and a clamp kernel follows.
 //
+// avse_spectrogram_ragged (utterances of mixed lengths in one launch, ragged_geom.h): k_spec640 / k_spec533 have a
+// ragged instantiation (RG) whose blocks take (utterance, chunk) from an item table and the utterance's geometry from
+// its row; launch_spectrogram_ragged below.
+//
 // n_fft = 533 (29.97 / 30 fps) runs k_spec533 (a Good-Thomas 13 x 41 prime-factor DFT); other n_fft use k_spec_dft,
 // a direct DFT, one block per frame.
 #include <algorithm>
+#include <type_traits>
 
 #include "avse_common.h"
 #include "fft_common.h"
@@ -162,9 +167,16 @@ __device__ __forceinline__ void pk_untangle(const v2f* __restrict__ zf, int k, c
 }
 
 // lane (f1, n1) of step 1 loads z[n1 + 16 n2] = (x[s0 + 2(n1 + 16 n2)], x[s0 + 2(n1 + 16 n2) + 1]), n2 < 20
+// RG (ragged batches): an utterance may start at any element of the packed buffer, so a base that is not 8-byte
+// aligned loads the pair as two dwords (the same values)
+template <bool RG = false>
 __device__ __forceinline__ void load_frame(float2 (&x)[20], const float* __restrict__ s, int L, int s0, int n1,
                                            int pad_mode) {
-    if (s0 >= 0 && s0 + 640 <= L) {
+    if (RG && s0 >= 0 && s0 + 640 <= L && (reinterpret_cast<uintptr_t>(s) & 7)) {
+        const float* p = s + s0 + 2 * n1;
+#pragma unroll
+        for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(p[32 * n2], p[32 * n2 + 1]);
+    } else if (s0 >= 0 && s0 + 640 <= L) {
         const float2* p = reinterpret_cast<const float2*>(s + s0) + n1;
 #pragma unroll
         for (int n2 = 0; n2 < 20; ++n2) x[n2] = p[16 * n2];
@@ -199,8 +211,15 @@ __device__ unsigned long long g_spec_stamps[4096][8];   // per block slot (block
 #define SPEC_STAMP(i)
 #endif
 
-template <bool FAST_MEL, bool RI>
-__global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, int n_chunks) {
+// RG: the ragged form (avse_spectrogram_ragged).  The block takes (u, chunk) from the item table and the utterance's
+// length, frame / slice counts and bases from its RaggedUtt row; the mel / STFT indices are then relative to the
+// utterance's own blocks.  top_db always goes through the per-utterance atomicMax and k_spec_clamp_ragged.  The
+// equal-length instantiations keep their second parameter (the chunk count) and their code.
+template <bool RG>
+using SpecGeomArg = std::conditional_t<RG, RaggedDev, int>;
+
+template <bool FAST_MEL, bool RI, bool RG = false>
+__global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, SpecGeomArg<RG> geo) {
     SPEC_STAMP_INIT
     __shared__ float2 zbuf[WAVES * FPG * ZS];
     __shared__ float dbuf[80 * CHUNK];
@@ -212,8 +231,17 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, in
     __shared__ float wmax[1][WAVES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = a.n_frames;
-    const int L = (int)a.n_samples;
+    RaggedItem ri = {};
+    RaggedUtt ru = {};
+    int n_chunks = 0;   // RG: never the single-block case
+    if constexpr (RG) {
+        ri = geo.items[blockIdx.x];
+        ru = geo.utt[ri.u];
+    } else {
+        n_chunks = geo;
+    }
+    const int T = RG ? ru.T : a.n_frames;
+    const int L = RG ? ru.L : (int)a.n_samples;
     const int n_mels = a.n_mels, mw = a.mel_max_width;
     const int g = FPG * wave;                       // this wave's first frame in the chunk
 
@@ -232,12 +260,13 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, in
 
     const int f1 = lane >> 4, n1 = lane & 15;
     const int item = blockIdx.x;
-    const int u = item / n_chunks, chunk = item - u * n_chunks;
+    const int u = RG ? ri.u : item / n_chunks, chunk = RG ? ri.chunk : item - u * n_chunks;
     float2 x[20];
     {
         const int nf = min(CHUNK, T - chunk * CHUNK);
         if (f1 < min(FPG, nf - g))
-            load_frame(x, a.sig + (long long)u * L, L, (chunk * CHUNK + g + f1) * a.hop - 320, n1, a.pad_mode);
+            load_frame<RG>(x, RG ? a.sig + ru.in_off : a.sig + (long long)u * L, L,
+                           (chunk * CHUNK + g + f1) * a.hop - 320, n1, a.pad_mode);
     }
     __syncthreads();
     SPEC_STAMP(0)
@@ -308,7 +337,7 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, in
                 pk_untangle(zf, k, ut2, X, Y);
                 mk[j] = pk_abs(X);
                 mm[j] = pk_abs(Y);
-                float2* o = reinterpret_cast<float2*>(a.stft_ri) + (long long)u * 321 * T + t0 + f;
+                float2* o = reinterpret_cast<float2*>(a.stft_ri) + (RG ? ru.out_off : (long long)u * 321 * T) + t0 + f;
                 o[(long long)k * T] = make_float2(X.x, X.y);
                 if (k != 160) o[(long long)(320 - k) * T] = make_float2(Y.x, -Y.y);   // X[320 - k] = conj(Y)
             }
@@ -408,11 +437,11 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, in
         const float floor_db = (single && a.top_db >= 0.f) ? vmax - a.top_db : -INFINITY;
         for (int it = tid; it < n_mels * nf; it += 64 * WAVES) {
             const int m = it / nf, tl = it - nf * m;
-            const long long oi = out_index(a.spf, a.n_slices, n_mels, T, u, m, t0 + tl);
-            AVSE_CHECK_DEV(t0 + tl < T && oi < (a.spf > 0 ? (long long)a.n_utt * a.n_slices * n_mels * a.spf
-                                                          : (long long)a.n_utt * n_mels * T),
+            const long long oi = out_index(a.spf, RG ? ru.S : a.n_slices, n_mels, T, RG ? 0 : u, m, t0 + tl);
+            AVSE_CHECK_DEV(t0 + tl < T && oi < (a.spf > 0 ? (long long)(RG ? 1 : a.n_utt) * (RG ? ru.S : a.n_slices) * n_mels * a.spf
+                                                          : (long long)(RG ? 1 : a.n_utt) * n_mels * T),
                            DK_SPEC, 2, t0 + tl, T);
-            if (oi >= 0) a.mel_db[oi] = fmaxf(dbuf[m * CHUNK + tl], floor_db);
+            if (oi >= 0) (RG ? a.mel_db + ru.mel_off : a.mel_db)[oi] = fmaxf(dbuf[m * CHUNK + tl], floor_db);
         }
         if (!single && tid == 0) atomicMax(a.umax + u, f2ord(vmax));
         SPEC_STAMP(6)
@@ -710,7 +739,8 @@ __device__ constexpr float kSin13[13] = {0.000000000e+00f, 4.647231698e-01f, 8.2
                                          -6.631226540e-01f, -9.350162148e-01f, -9.927088618e-01f, -8.229838610e-01f,
                                          -4.647231698e-01f};
 
-__global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, int n_chunks) {
+template <bool RG = false>
+__global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, SpecGeomArg<RG> geo) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* const seg = sm;                                  // [P533_SPAN] padded samples of the chunk's frames
     float* const win = sm + P533_SPAN;                      // [533] window   (seg / win: stages 0-1)
@@ -721,11 +751,34 @@ __global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, int n_chun
     int* const mwd = mst + 80;                                                    // [n_mels] band widths
     float* const red = reinterpret_cast<float*>(mwd + 80);                        // [6] block max
     const int tid = threadIdx.x;
-    const long long u = blockIdx.x / n_chunks;
-    const int t0 = (int)(blockIdx.x - u * n_chunks) * P533_CH;
-    const int nt = min(P533_CH, a.n_frames - t0);
-    const long long L = a.n_samples;
-    const float* sig = a.sig + u * L;
+    // RG: (u, chunk) from the item table, the utterance's geometry and bases from its row (k_spec640's note); mu is
+    // then 0, the utterance index inside its own mel / STFT blocks
+    long long u, mu, L;
+    int t0, n_chunks, n_frames, n_slices;
+    const float* sig;
+    float* mel_u;
+    float2* stft_u;
+    if constexpr (RG) {
+        const RaggedItem ri = geo.items[blockIdx.x];
+        const RaggedUtt ru = geo.utt[ri.u];
+        u = ri.u; mu = 0; L = ru.L;
+        t0 = ri.chunk * P533_CH;
+        n_chunks = 0;   // never the whole-utterance case
+        n_frames = ru.T; n_slices = ru.S;
+        sig = a.sig + ru.in_off;
+        mel_u = a.mel_db + ru.mel_off;
+        stft_u = reinterpret_cast<float2*>(a.stft_ri) + ru.out_off;
+    } else {
+        n_chunks = geo;
+        u = blockIdx.x / n_chunks; mu = u;
+        t0 = (int)(blockIdx.x - u * n_chunks) * P533_CH;
+        n_frames = a.n_frames; n_slices = a.n_slices;
+        L = a.n_samples;
+        sig = a.sig + u * L;
+        mel_u = a.mel_db;
+        stft_u = reinterpret_cast<float2*>(a.stft_ri);
+    }
+    const int nt = min(P533_CH, n_frames - t0);
     const int hop = a.hop;
 
     // stage 0: the chunk's padded samples (reflect / zero centre padding), the window, the Slaney rows
@@ -824,7 +877,7 @@ __global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, int n_chun
                 v.y = -v.y;
             }
             mrow[k] = __builtin_amdgcn_sqrtf(v.x * v.x + v.y * v.y);
-            if (a.stft_ri) reinterpret_cast<float2*>(a.stft_ri)[(u * nb + k) * a.n_frames + t0 + t] = v;
+            if (a.stft_ri) stft_u[(mu * nb + k) * n_frames + t0 + t] = v;
         }
     }
     // the rows' tails past bin 266 (read by the padded band dots) are zero
@@ -853,8 +906,8 @@ __global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, int n_chun
         dbv[r] = db;
         vmax = fmaxf(vmax, db);
         if (!whole) {
-            const long long oi = out_index(a.spf, a.n_slices, a.n_mels, a.n_frames, u, m, t0 + t);
-            if (oi >= 0) a.mel_db[oi] = db;
+            const long long oi = out_index(a.spf, n_slices, a.n_mels, n_frames, mu, m, t0 + t);
+            if (oi >= 0) mel_u[oi] = db;
         }
     }
 #pragma unroll
@@ -874,8 +927,8 @@ __global__ __launch_bounds__(P533_THREADS) void k_spec533(SpecArgs a, int n_chun
         const int it = tid + r * P533_THREADS;
         if (it >= a.n_mels * nt) continue;
         const int m = it / nt, t = it - m * nt;
-        const long long oi = out_index(a.spf, a.n_slices, a.n_mels, a.n_frames, u, m, t0 + t);
-        if (oi >= 0) a.mel_db[oi] = fmaxf(dbv[r], floor_db);
+        const long long oi = out_index(a.spf, n_slices, a.n_mels, n_frames, mu, m, t0 + t);
+        if (oi >= 0) mel_u[oi] = fmaxf(dbv[r], floor_db);
     }
 }
 
@@ -928,6 +981,20 @@ __global__ void k_spec_clamp(SpecArgs a) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long u = i / per_u;
         const float fl = ord2f(a.umax[u]) - a.top_db;
+        a.mel_db[i] = fmaxf(a.mel_db[i], fl);
+    }
+}
+
+// The ragged clamp pass: element i of the packed mel buffer belongs to the last utterance whose block starts at or
+// before i (ragged_geom.h ragged_mel_utt: the same search); the same fmaxf(x, max - top_db) as k_spec_clamp
+__global__ void k_spec_clamp_ragged(SpecArgs a, RaggedDev geo, long long total) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        int lo = 0, hi = geo.n_utt - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (geo.utt[mid].mel_off <= i) lo = mid; else hi = mid - 1;
+        }
+        const float fl = ord2f(a.umax[lo]) - a.top_db;
         a.mel_db[i] = fmaxf(a.mel_db[i], fl);
     }
 }
@@ -989,9 +1056,9 @@ int launch_spectrogram(const SpecArgs& a, hipStream_t s) {
             set_error("spectrogram batch too large (n_utt * chunks must fit in int32)");
             return 3;   // AVSE_ERR_UNSUPPORTED
         }
-        if (int rc = ensure_lds_attr((const void*)k_spec533, P533_LDS)) return rc;
+        if (int rc = ensure_lds_attr((const void*)k_spec533<false>, P533_LDS)) return rc;
         if (n_chunks > 1) AVSE_HIP_CHECK(hipMemsetAsync(a.umax, 0, sizeof(unsigned) * a.n_utt, s));
-        hipLaunchKernelGGL(k_spec533, dim3((unsigned)items), dim3(P533_THREADS), P533_LDS, s, a, n_chunks);
+        hipLaunchKernelGGL(k_spec533<false>, dim3((unsigned)items), dim3(P533_THREADS), P533_LDS, s, a, n_chunks);
         AVSE_HIP_CHECK(hipGetLastError());
         if (n_chunks > 1 && need_clamp_pass) {
             hipLaunchKernelGGL(k_spec_clamp, dim3(1024), dim3(256), 0, s, a);
@@ -1005,6 +1072,59 @@ int launch_spectrogram(const SpecArgs& a, hipStream_t s) {
     AVSE_HIP_CHECK(hipGetLastError());
     if (need_clamp_pass) {
         hipLaunchKernelGGL(k_spec_clamp, dim3(1024), dim3(256), 0, s, a);
+        AVSE_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+int spectrogram_ragged_chunk(int n_fft, int hop, int n_mels, int mel_max_width) {
+    if (n_fft == 640) return CHUNK;
+    if (n_fft == 533 && hop <= P533_HOPMAX && n_mels <= 80 && mel_max_width <= P533_MW) return P533_CH;
+    return 0;
+}
+
+int launch_spectrogram_ragged(const SpecArgs& a0, const RaggedGeom& g, const RaggedDev& d, hipStream_t s) {
+    if (a0.n_utt <= 0) return 0;
+    // the equal-length launch on utterances [first, first + count): a run has the equal-length layout
+    auto run = [&](const RaggedRun& r) {
+        const RaggedUtt& ru = g.utt[r.first];
+        SpecArgs a = a0;
+        a.sig = a0.sig + ru.in_off;
+        a.n_utt = r.count;
+        a.n_samples = ru.L;
+        a.n_frames = ru.T;
+        a.n_slices = ru.S;
+        a.mel_db = a0.mel_db + ru.mel_off;
+        a.stft_ri = a0.stft_ri ? a0.stft_ri + 2 * ru.out_off : nullptr;
+        a.umax = a0.umax + r.first;
+        return launch_spectrogram(a, s);
+    };
+    const int chunk = spectrogram_ragged_chunk(a0.n_fft, a0.hop, a0.n_mels, a0.mel_max_width);
+    if (g.runs.size() == 1 || chunk == 0) {
+        for (const RaggedRun& r : g.runs)
+            if (int rc = run(r)) return rc;
+        return 0;
+    }
+    if (g.items.empty() || !d.utt || !d.items || d.n_items != (int)g.items.size()) {
+        set_error("ragged spectrogram: no item table");
+        return 1;   // AVSE_ERR_INVALID
+    }
+    AVSE_HIP_CHECK(hipMemsetAsync(a0.umax, 0, sizeof(unsigned) * a0.n_utt, s));
+    const dim3 grid((unsigned)d.n_items);
+    if (a0.n_fft == 640) {
+        const bool fast = a0.n_mels <= 80 && a0.mel_max_width == MW, ri = a0.stft_ri != nullptr;
+        const dim3 block(64 * WAVES);
+        if (fast && ri) hipLaunchKernelGGL((k_spec640<true, true, true>), grid, block, 0, s, a0, d);
+        else if (fast) hipLaunchKernelGGL((k_spec640<true, false, true>), grid, block, 0, s, a0, d);
+        else if (ri) hipLaunchKernelGGL((k_spec640<false, true, true>), grid, block, 0, s, a0, d);
+        else hipLaunchKernelGGL((k_spec640<false, false, true>), grid, block, 0, s, a0, d);
+    } else {
+        if (int rc = ensure_lds_attr((const void*)k_spec533<true>, P533_LDS)) return rc;
+        hipLaunchKernelGGL(k_spec533<true>, grid, dim3(P533_THREADS), P533_LDS, s, a0, d);
+    }
+    AVSE_HIP_CHECK(hipGetLastError());
+    if (a0.top_db >= 0.f && g.mel_total > 0) {
+        hipLaunchKernelGGL(k_spec_clamp_ragged, dim3(1024), dim3(256), 0, s, a0, d, (long long)g.mel_total);
         AVSE_HIP_CHECK(hipGetLastError());
     }
     return 0;

@@ -105,7 +105,7 @@ def pair_groups(speech_signals, slice_duration_ms, n_video_slices, video_frame_r
 
 
 def preprocess_audio_pairs(speech_signals, noise_signals, slice_duration_ms, n_video_slices, video_frame_rate,
-                           snr_db=0):
+                           snr_db=0, ragged=False):
     """The batched preprocess_audio_pair (data_processor.py:119-139): per pair_groups group ONE ops.mix_pairs (noise
     looped to the speech, SNR gain, mixture, pad / truncate, all on the device) and ONE ops.spectrogram over the
     group's 3 U rows, instead of float64 numpy mixing and three one-utterance STFT launches per pair.
@@ -113,7 +113,13 @@ def preprocess_audio_pairs(speech_signals, noise_signals, slice_duration_ms, n_v
     speech_signals / noise_signals: AudioSignals holding mono int16 samples (TypeError otherwise, so that a caller can
     fall back to the per-sample path); n_video_slices, video_frame_rate, snr_db: one value, or one per pair.
     Returns per pair (mixed, speech, noise slice stacks [n_slices, 80, spf] float32, mixed AudioSignal of float64
-    [signal_length, 1] samples): the shapes, dtypes and values of the per-sample path."""
+    [signal_length, 1] samples): the shapes, dtypes and values of the per-sample path.
+
+    ragged=True: the pairs need not share a signal_length.  All pairs of one (n_fft, sample_rate) go through ONE
+    ops.mix_pairs at the largest signal_length and ONE ops.spectrogram_ragged over the 3 U rows, row k read with its own
+    signal_length_k: the mix's values do not depend on L and a row is zero past its speech, so the first
+    signal_length_k samples of row k are that pair's padded / truncated signal.  The results are those of
+    ragged=False."""
     n = len(speech_signals)
     if len(noise_signals) != n:
         raise ValueError(f"{n} speech signals but {len(noise_signals)} noise signals")
@@ -121,6 +127,30 @@ def preprocess_audio_pairs(speech_signals, noise_signals, slice_duration_ms, n_v
     noise = [_mono_int16(s, "noise %d" % i) for i, s in enumerate(noise_signals)]
     n_slices, fps, snr = _per_pair(n_video_slices, n), _per_pair(video_frame_rate, n), _per_pair(snr_db, n)
     out = [None] * n
+    if ragged:
+        rate_groups = {}
+        for i, sig in enumerate(speech_signals):
+            g = frame_geometry(sig.get_sample_rate(), slice_duration_ms, n_slices[i], fps[i])
+            rate_groups.setdefault((g["n_fft"], sig.get_sample_rate()), []).append((i, g))
+        for (n_fft, sr), members in rate_groups.items():
+            idx = [i for i, _ in members]
+            g0 = members[0][1]
+            U = len(idx)
+            lens = np.array([g["signal_length"] for _, g in members], dtype=np.int64)
+            Lmax = int(lens.max())
+            rows, mix64, _ = ops.mix_pairs([speech[i] for i in idx], [noise[i] for i in idx], Lmax,
+                                           snr_db=[snr[i] for i in idx])
+            offsets = np.arange(3 * U, dtype=np.int64) * Lmax
+            _, _, views = ops.spectrogram_ragged((rows.view(-1), offsets, np.tile(lens, 3)), sample_rate=sr, n_fft=n_fft,
+                                                 hop_length=g0["hop_length"], n_mels=N_MELS, fmin=MEL_FMIN,
+                                                 fmax=MEL_FMAX,
+                                                 frames_per_slice=g0["spectrogram_samples_per_slice"])
+            stacks = [v.cpu().numpy() for v in views]
+            mix64 = mix64.cpu().numpy()
+            for k, i in enumerate(idx):
+                out[i] = (stacks[k], stacks[U + k], stacks[2 * U + k],
+                          AudioSignal(np.ascontiguousarray(mix64[k, :lens[k]]), sr))
+        return out
     for (L, n_fft, sr), idx in pair_groups(speech_signals, slice_duration_ms, n_slices, fps):
         g = frame_geometry(sr, slice_duration_ms, n_slices[idx[0]], fps[idx[0]])
         U = len(idx)

@@ -139,6 +139,151 @@ def istft(mel_db, stft, sample_rate=16000, n_fft=640, hop_length=160, n_mels=80,
     return out
 
 
+def _ragged_signals(sigs):
+    """spectrogram_ragged's signal argument -> (1-D float32 device buffer, int64 offsets [U], int64 lengths [U]):
+    a list of 1-D float32 device tensors (packed here, tightly), or a (buffer, offsets, lengths) triple whose offsets
+    and lengths are integer sequences (any offsets: packed utterances, or the rows of a [U, stride] buffer)."""
+    if isinstance(sigs, tuple) and len(sigs) == 3 and isinstance(sigs[0], torch.Tensor) and \
+            not (isinstance(sigs[1], torch.Tensor) and sigs[1].is_floating_point()):
+        buf, off, lens = sigs
+        _dev_f32(buf, "sigs[0]")
+        off, lens = (np.ascontiguousarray(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x), dtype=np.int64)
+                     for x in (off, lens))
+        if off.ndim != 1 or off.shape != lens.shape:
+            raise ValueError("offsets and lengths must be 1-D and of one size")
+        if off.size and (off.min() < 0 or lens.min() < 0 or (off + lens).max() > buf.numel()):
+            raise ValueError("an utterance lies outside the buffer")
+        return buf.view(-1), off, lens
+    sigs = list(sigs)
+    for k, t in enumerate(sigs):
+        _dev_f32(t, f"sigs[{k}]")
+        if t.dim() != 1:
+            raise ValueError(f"sigs[{k}] must be 1-D, got shape {tuple(t.shape)}")
+    lens = np.array([t.numel() for t in sigs], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if len(sigs) else np.zeros(0, np.int64)
+    if not sigs:
+        raise ValueError("spectrogram_ragged needs at least one utterance")
+    return torch.cat(sigs), off, lens
+
+
+class RaggedViews:
+    """The per-utterance views of a packed buffer as a read-only sequence: view u is built when it is asked for (a
+    Tensor.view per utterance up front costs more host time than the launch it follows at small sizes).
+    `shapes[u]` is view u's shape without building it."""
+
+    def __init__(self, packed, sizes, shapes):
+        self.packed, self.shapes = packed, shapes
+        self._ends = np.cumsum(sizes)
+        self._sizes = sizes
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def __getitem__(self, u):
+        if isinstance(u, slice):
+            return [self[k] for k in range(*u.indices(len(self)))]
+        u = range(len(self))[u]
+        e = int(self._ends[u])
+        return self.packed[e - int(self._sizes[u]):e].view(self.shapes[u])
+
+    def __iter__(self):
+        return (self[u] for u in range(len(self)))
+
+
+def spectrogram_ragged(sigs, sample_rate=16000, n_fft=640, hop_length=160, n_mels=80, fmin=0.0, fmax=8000.0,
+                       amin=1e-5, top_db=80.0, pad_mode="reflect", frames_per_slice=0, return_stft=False):
+    """K1 for utterances of mixed lengths in one avse_spectrogram_ragged call: each utterance's result is the bits
+    spectrogram() gives for it alone (its own padding, trailing frames and top_db floor).
+
+    sigs: a list of 1-D float32 device tensors, or (buffer, offsets, lengths).  Returns (mel, counts, views):
+    (views: a RaggedViews sequence, each view built on access)
+    frames_per_slice == 0: mel is the 1-D packed buffer, counts the frames T_u, views[u] its [n_mels, T_u] block;
+    frames_per_slice  > 0: mel is [sum S_u, n_mels, frames_per_slice] (forward()'s input as it stands), counts the
+    slices S_u = T_u // frames_per_slice (0 is legal: an empty view), views[u] = mel[its slices].
+    With return_stft also (stft, stft_views): the packed 1-D complex64 STFT and the [1 + n_fft // 2, T_u] blocks."""
+    buf, off, lens = _ragged_signals(sigs)
+    U = int(lens.size)
+    dev = buf.device
+    spf = int(frames_per_slice)
+    if spf < 0:
+        raise ValueError("frames_per_slice < 0")
+    nb = 1 + n_fft // 2
+    T = n_frames(lens, hop_length, n_fft)             # (numpy, per utterance)
+    counts = T // spf if spf else T
+    sizes = counts * (n_mels * spf) if spf else T * n_mels
+    total, stotal = int(sizes.sum()), int(T.sum()) * nb
+    packed = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    mel = packed[:total]
+    stft = torch.empty((max(stotal, 1), 2), dtype=torch.float32, device=dev) if return_stft else None
+    pm = {"reflect": _lib.AVSE_PAD_REFLECT, "constant": _lib.AVSE_PAD_CONSTANT}[pad_mode]
+    if U:
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_spectrogram_ragged(
+                ctx.handle, _lib.ptr(buf), off.ctypes.data, lens.ctypes.data, U, int(sample_rate), int(n_fft),
+                int(hop_length), int(n_mels), float(fmin), float(fmax), float(amin),
+                float(-1.0 if top_db is None else top_db), pm, spf, _lib.ptr(packed), _lib.ptr(stft),
+                _lib.stream_handle(dev)), "avse_spectrogram_ragged")
+    Tl = T.tolist()
+    if spf:
+        views = RaggedViews(mel, sizes, [(c, n_mels, spf) for c in counts.tolist()])
+        mel = mel.view(-1, n_mels, spf)
+    else:
+        views = RaggedViews(mel, sizes, [(n_mels, t) for t in Tl])
+    if not return_stft:
+        return mel, counts, views
+    cstft = torch.view_as_complex(stft)[:stotal]
+    return mel, counts, views, cstft, RaggedViews(cstft, T * nb, [(nb, t) for t in Tl])
+
+
+def istft_ragged(mel_packed, counts, stft_packed, stft_frames, sample_rate=16000, n_fft=640, hop_length=160, n_mels=80,
+                 fmin=0.0, fmax=8000.0):
+    """K6 for utterances of mixed lengths in one avse_istft_ragged call: utterance u's signal is the bits istft() gives
+    for it alone.
+
+    mel_packed: [sum S_u, n_mels, spf] (forward()'s output for the concatenated slices; counts = the slices S_u, so
+    n_frames_u = S_u * spf) or the 1-D packed [n_mels, T_u] blocks (counts = the frames T_u).  stft_packed: the packed
+    complex64 STFT of spectrogram_ragged (or its float32 [..., 2] view), stft_frames its frames per utterance; every
+    n_frames_u <= stft_frames[u].  Returns a list of views of one packed output, hop * (n_frames_u - 1) samples each
+    (none for n_frames_u < 2)."""
+    _dev_f32(mel_packed, "mel_packed")
+    if stft_packed.dtype == torch.complex64:
+        stft_packed = torch.view_as_real(stft_packed)
+    _dev_f32(stft_packed, "stft_packed")
+    counts = np.ascontiguousarray(np.asarray(counts), dtype=np.int64)
+    sf = np.ascontiguousarray(np.asarray(stft_frames), dtype=np.int64)
+    if counts.ndim != 1 or counts.shape != sf.shape:
+        raise ValueError("counts and stft_frames must be 1-D and of one size")
+    if mel_packed.dim() == 3:
+        if mel_packed.shape[1] != n_mels:
+            raise ValueError("mel_packed / n_mels do not match")
+        spf = int(mel_packed.shape[2])
+        nf = counts * spf
+    elif mel_packed.dim() == 1:
+        spf = 0
+        nf = counts.copy()
+    else:
+        raise ValueError("mel_packed must be [slices, n_mels, spf] or the 1-D packed [n_mels, T] blocks")
+    nb = 1 + n_fft // 2
+    U = int(counts.size)
+    if U and (counts.min() < 0 or sf.min() < 0):
+        raise ValueError("negative counts")
+    if int(nf.sum()) * n_mels != mel_packed.numel() or int(sf.sum()) * nb * 2 != stft_packed.numel():
+        raise ValueError("counts / stft_frames do not add up to the packed buffers")
+    sizes = np.where(nf >= 2, hop_length * (nf - 1), 0)
+    dev = mel_packed.device
+    total = int(sizes.sum())
+    packed = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    if U and mel_packed.numel() and stft_packed.numel():
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_istft_ragged(
+                ctx.handle, _lib.ptr(mel_packed), _lib.ptr(stft_packed), nf.ctypes.data, sf.ctypes.data, U, spf,
+                int(sample_rate), int(n_fft), int(hop_length), int(n_mels), float(fmin), float(fmax),
+                _lib.ptr(packed), _lib.stream_handle(dev)), "avse_istft_ragged")
+    return list(packed[:total].split(sizes.tolist()))
+
+
 def act_exponent(model, layer):
     """The AVSE_F32_SPLIT activation exponent rule of csrc/capi.hip act_exponents for one layer: with M =
     max_c (|beta_c| + |gamma_c|) of its BatchNormalization, 0 for M in [2^-2, 2^8], else 3 - ceil-exponent(M) (M 2^e in

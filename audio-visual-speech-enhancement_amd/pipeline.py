@@ -12,6 +12,9 @@ equal-length utterances runs through the same three steps on device tensors:
                         (the normaliser fused into v_conv1)
   K6  avse_istft        predicted slices + mixture phase -> [U, hop * (S*spf - 1)]
 
+Utterances of mixed lengths run through the ragged forms of K1 / K6 (Enhancer.enhance_ragged: one
+avse_spectrogram_ragged, the forward over the concatenated clips, one avse_istft_ragged).
+
 Every utterance is independent (top_db is per utterance), so a multi-GPU run shards utterances
 (parallel.sharded_enhance) with no collective before the final gather.
 """
@@ -96,4 +99,61 @@ class Enhancer:
             ev[3].synchronize()
             timings.update(stft_ms=ev[0].elapsed_time(ev[1]), forward_ms=ev[1].elapsed_time(ev[2]),
                            istft_ms=ev[2].elapsed_time(ev[3]))
+        return out
+
+    def enhance_ragged(self, signals, videos, vmean=None, vstd=None):
+        """__call__ for utterances of mixed lengths: signals[u] is [L_u] float32, videos[u] [S_u, 128, 128, frames]
+        (float32 or uint8, one dtype for all).  One ragged STFT, the forward over the concatenated clips of all
+        utterances (in chunks of <= `chunk`, which may span utterances), one ragged ISTFT.  Each signal is padded /
+        truncated to its own S_u slices first, as __call__ does for the batch.  Returns a list of [hop * (S_u * spf - 1)]
+        tensors (views of one buffer), each the bits __call__ gives for that utterance alone."""
+        signals, videos = list(signals), list(videos)
+        if len(signals) != len(videos) or not signals:
+            raise ValueError("signals and videos must be non-empty lists of one length")
+        geo = [self.geometry(int(v.shape[0])) for v in videos]
+        g0 = geo[0]
+        spf = g0["spectrogram_samples_per_slice"]
+        fixed = []
+        for u, (s, v, g) in enumerate(zip(signals, videos, geo)):
+            if s.dim() != 1 or v.dim() != 4:
+                raise ValueError(f"signals[{u}] must be [L] and videos[{u}] [S, H, W, frames]")
+            if g["n_slices"] != v.shape[0]:
+                raise ValueError(f"{v.shape[0]} video slices but the audio geometry gives {g['n_slices']} spectrogram slices")
+            if spf != self.weights.T or v.shape[-1] != self.weights.F:
+                raise ValueError(f"{self.fps} fps gives [80, {spf}] slices with {v.shape[-1]} video frames; the weights "
+                                 f"are for [80, {self.weights.T}] x {self.weights.F} frames (build the network for this rate)")
+            L = g["signal_length"]
+            if s.shape[0] != L:
+                s = torch.nn.functional.pad(s, (0, max(0, L - s.shape[0])))[:L]
+            fixed.append(s.contiguous())
+        kw = dict(sample_rate=self.sr, n_fft=g0["n_fft"], hop_length=g0["hop_length"], n_mels=data_processor.N_MELS,
+                  fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX)
+        clips, counts, _, stft, sviews = ops.spectrogram_ragged(fixed, frames_per_slice=spf, return_stft=True, **kw)
+        if [int(c) for c in counts] != [int(v.shape[0]) for v in videos]:
+            raise ValueError("the spectrogram's slice counts differ from the videos'")
+        n = clips.shape[0]
+        frames = torch.cat(videos) if len(videos) > 1 else videos[0]
+        pred = torch.empty_like(clips)
+        split = self.weights.dtype == _lib.AVSE_F32_SPLIT
+        pipe = ops.RangePipeline(self.weights.ctx) if split else None
+        if split:
+            self.weights.ctx.set_aside_range()
+
+        def chunk(a, b, checked):
+            ops.forward(self.weights, clips[a:b], frames[a:b], vmean, vstd, out=pred[a:b], checked=checked)
+
+        for a in range(0, n, self.chunk):
+            b = min(n, a + self.chunk)
+            chunk(a, b, False)
+            if split:
+                pipe.submit(lambda a=a, b=b: chunk(a, b, True))
+
+        def istft():
+            return ops.istft_ragged(pred, counts, stft, [sh[1] for sh in sviews.shapes], **kw)
+        out = istft()
+        self.range_bits = 0
+        if split:
+            self.range_bits = pipe.drain()
+            if pipe.recomputed:      # a chunk was redone after the ISTFT had been queued: redo the ISTFT after it
+                out = istft()
         return out

@@ -26,9 +26,10 @@ Differences (host plumbing outside the hot path):
   * predict runs ONE forward per sample: the printed loss (speech_enhancer.py:76-77, an MSE over the
     sample like Model.evaluate) is computed from the same prediction that is reconstructed (the reference
     runs evaluate and predict, two forwards of the same input);
-  * predict batches: samples of one shape (slice count, frame rate, mixture length) run as one forward and one
-    batched STFT / ISTFT (BatchPredictor) — every result equals the per-sample path's bit for bit (the fp32 forward
-    is batch-invariant, csrc/capi.hip choose_ksplit); `-g N` (parsed and ignored by the reference,
+  * predict batches: samples of one slice shape, frame rate and sample rate run as one forward and one ragged
+    STFT / ISTFT whatever their lengths (RaggedBatchPredictor; BatchPredictor is the equal-length form) — every
+    result equals the per-sample path's bit for bit (the fp32 forward is batch-invariant, csrc/capi.hip
+    choose_ksplit); `-g N` (parsed and ignored by the reference,
     speech_enhancer.py:289) runs N ranks, one per GPU, each on a contiguous block of the samples.
 All spectrogram / network / reconstruction arithmetic goes through libavse (K1, forward, K6).
 """
@@ -124,11 +125,17 @@ def _u8_kw(video_u8):
     return {"video_u8": True} if video_u8 else {}
 
 
-def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200, video_u8=False):
+def _ragged_kw(ragged):
+    """The ragged keyword, passed on only when set (as _u8_kw)."""
+    return {"ragged": True} if ragged else {}
+
+
+def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200, video_u8=False, ragged=False):
     """preprocess_sample for a group of entries with the audio of all pairs in one
     data_processor.preprocess_audio_pairs call (device-side mixing, one STFT launch per geometry).  Catch-and-skip as
     preprocess_data: an entry whose files do not load is skipped; when the batched call fails (a multi-channel or
-    float wav: TypeError) the group is redone pair by pair on preprocess_sample, so only the failing pair is lost."""
+    float wav: TypeError) the group is redone pair by pair on preprocess_sample, so only the failing pair is lost.
+    ragged: pairs of different lengths share the device calls too (preprocess_audio_pairs(ragged=True))."""
     loaded = []
     for entry, noise in zip(speech_entries, noise_file_paths):
         try:
@@ -141,7 +148,8 @@ def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200, vi
         return []
     try:
         audio = data_processor.preprocess_audio_pairs([x[4] for x in loaded], [x[5] for x in loaded], slice_duration_ms,
-                                                      [x[2].shape[0] for x in loaded], [x[3] for x in loaded])
+                                                      [x[2].shape[0] for x in loaded], [x[3] for x in loaded],
+                                                      **_ragged_kw(ragged))
     except Exception:  # noqa: BLE001 — isolate the failing pair below
         audio = None
     samples = []
@@ -159,15 +167,16 @@ def preprocess_batch(speech_entries, noise_file_paths, slice_duration_ms=200, vi
     return samples
 
 
-def preprocess_data(speech_entries, noise_file_paths, batch=0, video_u8=False):
+def preprocess_data(speech_entries, noise_file_paths, batch=0, video_u8=False, ragged=False):
     """data_processor.py:180-198 (catch-and-skip per sample; the GPU does the spectrograms, so no Pool).
     batch > 0: groups of up to `batch` consecutive pairs through preprocess_batch (same samples, same order).
-    video_u8: the samples' video stays uint8 (--video-u8)."""
+    video_u8: the samples' video stays uint8 (--video-u8).  ragged: a batch's pairs of different lengths run in the
+    same device calls (what `preprocess --batch N` asks for)."""
     samples = []
     if batch > 0:
         for a in range(0, len(speech_entries), batch):
             samples.extend(preprocess_batch(speech_entries[a:a + batch], noise_file_paths[a:a + batch],
-                                            **_u8_kw(video_u8)))
+                                            **_u8_kw(video_u8), **_ragged_kw(ragged)))
         return samples
     for entry, noise in zip(speech_entries, noise_file_paths):
         try:
@@ -235,7 +244,8 @@ def preprocess(args):
     layout = Layout(args.base_dir)
     speech_entries, noise_file_paths = pair_speech_with_noise(args.dataset_dir, selected_speakers(args),
                                                               args.noise_dirs, limit=1000, shuffle=True)
-    samples = preprocess_data(speech_entries, noise_file_paths, batch=args.batch, **_u8_kw(args.video_u8))
+    samples = preprocess_data(speech_entries, noise_file_paths, batch=args.batch, **_u8_kw(args.video_u8),
+                              **_ragged_kw(args.batch > 0))
     save_preprocessed_blob(layout.preprocessed(args.data_name), samples)
     print("preprocessed %d samples" % len(samples))
 
@@ -332,9 +342,77 @@ class BatchPredictor:
         return [(float(losses[u].item()), AudioSignal(y[u], sr)) for u in range(U)]
 
 
+class RaggedBatchPredictor:
+    """BatchPredictor without the split by length: samples that share frame rate, sample rate and slice shape run as
+    one batch whatever their slice counts and mixture lengths — one forward over all their slices, one MSE per sample,
+    one ragged STFT of the mixtures for the phase and one ragged ISTFT.  Each result equals predict_one's bit for bit."""
+
+    def __init__(self, network, video_normalizer=None, chunk=1024):
+        self.network = network
+        self.video_normalizer = video_normalizer
+        self.chunk = int(chunk)
+
+    @staticmethod
+    def groups(samples):
+        """Indices of the samples that run as one batch, in first-seen order (sample_groups without the lengths)."""
+        groups = {}
+        for i, smp in enumerate(samples):
+            key = (tuple(smp.mixed_spectrograms.shape[1:]), tuple(smp.video_samples.shape[1:]),
+                   str(smp.video_samples.dtype == np.uint8), float(smp.video_frame_rate),
+                   smp.mixed_signal.get_sample_rate())
+            groups.setdefault(key, []).append(i)
+        return list(groups.values())
+
+    def __call__(self, group):
+        import torch
+        from . import _lib, ops
+        dw = self.network.device_weights()
+        dev = torch.device("cuda", dw.ctx.device_index)
+        U = len(group)
+        S = [int(g.mixed_spectrograms.shape[0]) for g in group]
+        if any(g.video_samples.shape[0] != s or g.speech_spectrograms.shape[0] != s for g, s in zip(group, S)):
+            raise ValueError("a sample's video, mixture and speech slice counts differ")
+        clips = torch.from_numpy(np.ascontiguousarray(np.concatenate([g.mixed_spectrograms for g in group]),
+                                                      dtype=np.float32)).to(dev)
+        # uint8 crops (--video-u8) go up as they are; C order (the samples' crops are transposed views, whose layout
+        # np.concatenate would keep)
+        video = np.ascontiguousarray(np.concatenate([g.video_samples for g in group]))
+        frames = torch.from_numpy(video if video.dtype == np.uint8 else video.astype(np.float32)).to(dev)
+        speech = torch.from_numpy(np.ascontiguousarray(np.concatenate([g.speech_spectrograms for g in group]),
+                                                       dtype=np.float32)).to(dev)
+        m = s = None
+        if self.video_normalizer is not None:
+            m, s = self.video_normalizer.device_stats(dev)
+        n = clips.shape[0]
+        pred = torch.empty_like(clips)
+        for a in range(0, n, self.chunk):
+            b = min(n, a + self.chunk)
+            ops.forward(dw, clips[a:b], frames[a:b], m, s, out=pred[a:b], checked=dw.dtype == _lib.AVSE_F32_SPLIT)
+        ends = np.cumsum(S)
+        losses = [ops.mse(pred[int(e - k):int(e)], speech[int(e - k):int(e)]) for e, k in zip(ends, S)]
+        sr, fps = group[0].mixed_signal.get_sample_rate(), group[0].video_frame_rate
+        n_fft = int(float(sr) / fps)
+        hop = int(n_fft / 4)
+        kw = dict(sample_rate=sr, n_fft=n_fft, hop_length=hop, n_mels=data_processor.N_MELS,
+                  fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX)
+        sigs = [torch.from_numpy(np.asarray(g.mixed_signal.get_data(channel_index=0)).astype(np.float32)).to(dev)
+                for g in group]
+        _, T, _, D, _ = ops.spectrogram_ragged(sigs, return_stft=True, **kw)
+        # reconstruct_speech_signal: the first min(T_pred, T_stft) frames (data_processor.py:68-70)
+        spf = int(pred.shape[2])
+        if all(k * spf <= t for k, t in zip(S, T)):
+            ys = ops.istft_ragged(pred, S, D, T, **kw)
+        else:   # a prediction longer than its mixture: the [80][T] layout of the concatenated, trimmed slices
+            nf = [min(k * spf, int(t)) for k, t in zip(S, T)]
+            flat = torch.cat([pred[int(e - k):int(e)].permute(1, 0, 2).reshape(pred.shape[1], k * spf)[:, :f].reshape(-1)
+                              for e, k, f in zip(ends, S, nf)])
+            ys = ops.istft_ragged(flat, nf, D, T, **kw)
+        return [(float(losses[u].item()), AudioSignal(ys[u].cpu().numpy(), sr)) for u in range(U)]
+
+
 def predict_samples(samples, predictor, run_dir, world=1, rank=0, write=write_prediction, fallback=None):
     """The predict loop over this rank's contiguous block of `samples` (parallel.shard_bounds), a batch per
-    sample_groups group; outputs are written by the rank that owns the sample (one node: a shared file system).  A
+    group of the predictor's own grouping (its `groups`, else sample_groups); outputs are written by the rank that owns the sample (one node: a shared file system).  A
     group that fails is retried sample by sample (`fallback`, or the predictor on one sample) so that, as in the
     reference (speech_enhancer.py:87-88), only the failing sample is skipped.  Returns {sample index: loss or None}
     for every sample on rank 0 (gathered from all ranks), this rank's own otherwise."""
@@ -342,7 +420,7 @@ def predict_samples(samples, predictor, run_dir, world=1, rank=0, write=write_pr
     lo, hi = shard_bounds(len(samples), world, rank)
     mine = samples[lo:hi]
     losses = {}
-    for idxs in sample_groups(mine):
+    for idxs in getattr(predictor, "groups", sample_groups)(mine):
         try:
             outs = predictor([mine[i] for i in idxs])
         except Exception:  # noqa: BLE001 — isolate the failing sample below
@@ -419,7 +497,7 @@ def predict(args):
     if args.per_sample:
         predictor = lambda group: [predict_one(network, video_normalizer, smp) for smp in group]  # noqa: E731
     else:
-        predictor = BatchPredictor(network, video_normalizer)
+        predictor = RaggedBatchPredictor(network, video_normalizer)
     losses = predict_samples(samples, predictor, run_dir, world, rank,
                              fallback=lambda smp: predict_one(network, video_normalizer, smp))
     if rank == 0:

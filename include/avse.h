@@ -163,6 +163,64 @@ int avse_istft(avse_ctx* ctx, const float* mel_db, const float* stft_ri, int64_t
                int stft_frames, int frames_per_slice, int sr, int n_fft, int hop, int n_mels,
                float fmin, float fmax, float* sig, void* stream);
 
+/* avse_spectrogram for a RAGGED batch: n_utt utterances of n_utt lengths in one call.  Replaces the same
+ * signal_to_spectrogram / preprocess_audio_signal code (data_processor.py:49-57, 77-96) as it runs once per
+ * utterance: every utterance has its own reflect / zero padding, its own trailing frames and its own top_db
+ * floor (the maximum over its own WHOLE [n_mels, T_u] array), exactly as if it were passed to avse_spectrogram
+ * alone — the results are the same bits.
+ *
+ *   sig_off    HOST [n_utt] int64   element offset of utterance u's first sample from `sig`; any offset, odd ones
+ *                                   included: tightly packed utterances and the rows of a [n_utt][stride] buffer
+ *                                   (avse_mix_pairs' rows) are both expressible
+ *   n_samples  HOST [n_utt] int64   its length; T_u = the centred frame count of avse_spectrogram for that length
+ *                                   (1 + n_samples[u] / hop for an even n_fft)
+ *   mel_db     frames_per_slice == 0: per utterance [n_mels][T_u], concatenated in utterance order
+ *              frames_per_slice  > 0: [sum_u S_u][n_mels][frames_per_slice], S_u = T_u / frames_per_slice; an
+ *                                   utterance's slices are consecutive, so the buffer is avse_forward's audio input
+ *                                   as it stands.  S_u == 0 is legal: that utterance writes no mel (its complex STFT
+ *                                   is still written) and takes part in no other utterance's top_db
+ *   stft_ri    nullable; per utterance [n_fft/2+1][T_u][2], concatenated
+ *
+ * A batch whose lengths are all equal has exactly avse_spectrogram's layout; where its utterances also start
+ * n_samples apart, the call IS avse_spectrogram's launch.  Otherwise n_fft 640 and 533 run ragged instantiations of
+ * their kernels (one block per (utterance, chunk of frames) from an item table built on the host), followed by the
+ * per-utterance clamp pass; other n_fft walk the maximal runs of consecutive equal-length, evenly spaced utterances
+ * through the equal-length kernels.  The item table is uploaded into context scratch, which grows outside a stream
+ * capture only (like avse_mix_pairs' scratch); a captured call reads the table from context-owned host memory when
+ * the graph runs, so replay it before the next ragged call on this context.
+ *
+ * Refused with AVSE_ERR_INVALID before any GPU work: a NULL ctx / sig / sig_off / n_samples / mel_db, n_utt < 0, an
+ * n_samples[u] < 1, reflect padding on an utterance of at most n_fft/2 samples, a negative frames_per_slice, and a
+ * batch too large (an utterance of 2^31 samples or more, or more than 2^31 - 1 (utterance, chunk) items). */
+int avse_spectrogram_ragged(avse_ctx* ctx, const float* sig, const int64_t* sig_off, const int64_t* n_samples,
+                            int64_t n_utt, int sr, int n_fft, int hop, int n_mels, float fmin, float fmax,
+                            float amin, float top_db, int pad_mode, int frames_per_slice, float* mel_db,
+                            float* stft_ri /* nullable */, void* stream);
+
+/* avse_istft for a RAGGED batch: replaces reconstruct_signal_from_spectrogram / reconstruct_speech_signal
+ * (data_processor.py:60-74, 99-116) as they run once per utterance.  Every utterance has its own last frame, and so
+ * its own window-sum edges; utterance u's samples are the bits avse_istft gives for it alone.
+ *
+ *   n_frames     HOST [n_utt] int64  frames reconstructed for utterance u (the first n_frames[u] of its STFT)
+ *   stft_frames  HOST [n_utt] int64  frames its mixture STFT holds
+ *   mel_db   frames_per_slice > 0: [sum_u n_frames[u] / frames_per_slice][n_mels][frames_per_slice] (avse_forward's
+ *            output for the concatenated slices, as it stands); == 0: per utterance [n_mels][n_frames[u]], concatenated
+ *   stft_ri  per utterance [n_fft/2+1][stft_frames[u]][2], concatenated (avse_spectrogram_ragged's stft_ri)
+ *   sig      per utterance hop * (n_frames[u] - 1) samples, concatenated; nothing for n_frames[u] < 2
+ *
+ * Equal lengths: avse_istft's layout and its launch.  Otherwise n_fft 640 / hop 160 / 80 bands run the ragged
+ * instantiation of the fused kernel (its prefetch reads the next item's utterance through buffer resources bounded
+ * by that utterance's own blocks); every other shape walks the runs of equal (n_frames, stft_frames) through the
+ * equal-length kernels.  Scratch and stream capture: as avse_spectrogram_ragged.
+ *
+ * Refused with AVSE_ERR_INVALID before any GPU work: a NULL ctx / mel_db / stft_ri / n_frames / stft_frames / sig,
+ * n_utt < 0, a negative n_frames[u] or stft_frames[u], an n_frames[u] that is no multiple of a positive
+ * frames_per_slice, n_frames[u] > stft_frames[u], a negative frames_per_slice, and a batch too large (an utterance
+ * whose STFT or mel block passes 2 GiB, or more than 2^31 - 1 items). */
+int avse_istft_ragged(avse_ctx* ctx, const float* mel_db, const float* stft_ri, const int64_t* n_frames,
+                      const int64_t* stft_frames, int64_t n_utt, int frames_per_slice, int sr, int n_fft, int hop,
+                      int n_mels, float fmin, float fmax, float* sig, void* stream);
+
 /* ---- network --------------------------------------------------------------------------- */
 
 /* Number of float32 values in a canonical weight blob (see avse_weights_load): the 25-fps network
