@@ -4,8 +4,7 @@
 #include <stdint.h>
 #include <string>
 
-#include "layer_geom.h"
-#include "options.h"
+#include "forward_plan.h"
 #include "ragged_geom.h"
 
 typedef __bf16 bf16_t;
@@ -94,17 +93,6 @@ int debug_read_stft(DebugHit* out);
 int debug_read_istft(DebugHit* out);
 
 // ---- STFT / mel front end ---------------------------------------------------------------
-struct MelTable {
-    int n_mels = 0;
-    int n_bins = 0;
-    int max_width = 0;         // max non-zero bins per band
-    int* start = nullptr;      // device [n_mels]
-    int* width = nullptr;      // device [n_mels]
-    float* weight = nullptr;   // device [n_mels][max_width]
-    int seg_nq[4] = {6, 6, 6, 6};   // k_spec640: 4-bin weight quads its mel pass j (bands 64 j / 3 ..) needs
-    int seg_nq4[4] = {7, 7, 7, 7};  // k_spec_seg: the same from the band start rounded down to a multiple of 4 bins
-};
-
 struct SpecArgs {
     const float* sig;
     int64_t n_utt;
@@ -222,10 +210,6 @@ __device__ __forceinline__ void range_report(unsigned* flag, unsigned bit, bool 
 constexpr unsigned kRangeAudioIn = 1u << 24, kRangeVideoIn = 1u << 25;
 int launch_flag_or(unsigned* flag, unsigned bits, hipStream_t s);
 
-// k_conv's fp32 blocked summation: K-slabs (16 products each) summed FP32_BLOCK at a time into a zeroed partial that
-// is added to the running sum in slab order.  A split-K whose every split is exactly one such block, reduced in split
-// order, therefore reproduces the unsplit sums bit for bit (train.hip train_split).
-constexpr int kFp32Block = 8;
 // launch_conv dtype: 0 fp32 (exact-fp32 MFMA), 1 bf16, kConvSplit fp32 input with split-f16 products (the generic
 // layers of AVSE_F32_SPLIT: weights packed [Cout][kpad] with each 16-k slab row [Bh(16) | Bl(16)] f16),
 // kConvSplitPairs the same on an input already in the split pair layout (Ci, strides, kpad, w_off in halves)
@@ -328,9 +312,7 @@ struct GemmArgs {
     int four_products;       // split: 1 = slab by slab with all four products (Options::four_products), 0 = planar slab
                              // pairs with three
 };
-int gemm_ksplit(int M, int N, int kpad, int cap);   // cap > 0 limits the split (Options::gemm_ksplit_cap)
-int gemm_s16_ksplit(int N, int kpad, int* slabs_per_split);   // split dense layers: plan from K and N only
-size_t gemm_ws_bytes(int M, int N, int kpad, int cap);
+// (the split-K plans, gemm_ksplit and gemm_s16_ksplit among them: forward_plan.h)
 int launch_gemm(const GemmArgs& g, int mode, hipStream_t s);   // 0 launched, -1 declined (counters_cap), else an error
 int launch_aud_enc(const AudEncArgs& a, hipStream_t s);
 int launch_dec_tail(const DecTailArgs& a, hipStream_t s);

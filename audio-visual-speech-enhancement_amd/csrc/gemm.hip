@@ -359,34 +359,6 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
 
 }  // namespace
 
-// split-K factor: as many workgroups as fit one round on the 256 CUs (one 128-KB workgroup per CU: 264
-// workgroups took two rounds), at least 8 slabs each
-int gemm_ksplit(int M, int N, int kpad, int cap) {
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128), nslab = kpad / 32;
-    int ks = 256 / tiles;
-    ks = ks > nslab / 8 ? nslab / 8 : ks;
-    if (cap > 0 && cap < ks) ks = cap;   // A/B: cap the split (timing experiments, ksplit == 1 parity test)
-    return ks < 1 ? 1 : ks;
-}
-
-size_t gemm_ws_bytes(int M, int N, int kpad, int cap) {
-    const int ks = gemm_ksplit(M, N, kpad, cap);
-    const size_t tiles = (size_t)((M + 127) / 128) * ((N + 127) / 128);
-    return ks > 1 ? tiles * ks * 128 * 128 * 4 : 0;
-}
-
-// AVSE_F32_SPLIT dense layers: splits of whole kFp32Block-slab blocks, the plan from K and N only (never M, so every
-// batch takes the same splits and the same ordered reduction): as many splits as fill the 256 CUs at the bench
-// batch's 4 row tiles
-int gemm_s16_ksplit(int N, int kpad, int* slabs_per_split) {
-    const int nblocks = (kpad / 16 + kFp32Block - 1) / kFp32Block, tiles_n = (N + 127) / 128;
-    int ks = std::max(1, std::min(nblocks, 256 / (4 * tiles_n)));
-    const int G = (nblocks + ks - 1) / ks;
-    ks = (nblocks + G - 1) / G;
-    if (slabs_per_split) *slabs_per_split = G * kFp32Block;
-    return ks;
-}
-
 int launch_gemm(const GemmArgs& g, int mode, hipStream_t s) {
     const bool s16 = g.split != 0;
 #ifndef AVSE_GEMM_ABL

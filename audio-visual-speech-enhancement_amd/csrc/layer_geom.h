@@ -1,5 +1,5 @@
 // Host-only layer geometry (no HIP header): the phase / tap tables every layer of the plan (netplan.h) runs with on
-// k_conv, for the inference forward (capi.hip), the training forward and its input gradient (train.hip), and the
+// k_conv, for the inference forward (forward.hip), the training forward and its input gradient (train.hip), and the
 // index maps from the Keras kernel to the packed [phase][rows][kpad] weights (weight_pack.cpp, train.hip).
 #pragma once
 #include <utility>
@@ -191,6 +191,11 @@ inline std::vector<int> gather_map(const LayerDef& L, const PhaseSet& g) {
         }
     return m;
 }
+
+// k_conv's fp32 blocked summation: K-slabs (16 products each) summed FP32_BLOCK at a time into a zeroed partial that
+// is added to the running sum in slab order.  A split-K whose every split is exactly one such block, reduced in split
+// order, therefore reproduces the unsplit sums bit for bit (train.hip train_split).
+constexpr int kFp32Block = 8;
 
 // gemm.hip's split-K tickets: one int per 128 x 128 output tile of a launch, in a per-context array of kGemmCounters.
 // A split launch (ksplit > 1) with more tiles than counters does not fit: launch_gemm declines it and the forward runs

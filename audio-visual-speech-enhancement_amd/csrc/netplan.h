@@ -1,4 +1,4 @@
-// The layer plan of /root/reference/network.py:17-175 (shared by the inference path, capi.hip, and the
+// The layer plan of /root/reference/network.py:17-175 (shared by the inference path, forward.hip, and the
 // training step, train.hip): kinds, channel counts, kernel sizes, strides, input grids, BN / pool flags, TF
 // 'SAME' geometry, and the canonical weight-blob size (include/avse.h, avse_weights_load).
 //

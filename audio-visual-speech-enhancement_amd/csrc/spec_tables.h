@@ -18,7 +18,7 @@ struct DftTables {
 };
 DftTables dft_tables(int n);
 
-// The filterbank as one run of non-zero bins per band (MelTable, avse_common.h).
+// The filterbank as one run of non-zero bins per band (MelTable, ctx.h).
 struct MelBands {
     int n_bins = 0, max_width = 0;
     std::vector<int> start, width;   // [n_mels]

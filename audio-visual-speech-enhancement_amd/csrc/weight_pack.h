@@ -1,5 +1,5 @@
 // Host-only weight folding and packing (no HIP header): from one layer's Keras kernel / bias / BatchNormalization
-// parameters to every buffer the inference kernels read.  capi.hip uploads the result (build_layer).
+// parameters to every buffer the inference kernels read.  weights.hip uploads the result (build_layer).
 #pragma once
 #include <stdint.h>
 

@@ -285,7 +285,7 @@ def istft_ragged(mel_packed, counts, stft_packed, stft_frames, sample_rate=16000
 
 
 def act_exponent(model, layer):
-    """The AVSE_F32_SPLIT activation exponent rule of csrc/capi.hip act_exponents for one layer: with M =
+    """The AVSE_F32_SPLIT activation exponent rule of csrc/weight_pack.cpp act_exponents for one layer: with M =
     max_c (|beta_c| + |gamma_c|) of its BatchNormalization, 0 for M in [2^-2, 2^8], else 3 - ceil-exponent(M) (M 2^e in
     (4, 8]), clamped to [-24, 24]."""
     g = np.abs(np.asarray(model.tensors[layer + "_bn/gamma"], np.float64))
@@ -298,7 +298,7 @@ def act_exponent(model, layer):
 
 def _warn_concat_exponents(model):
     """a_conv5 and v_conv6 write the two halves of one concat row that enc_dense reads as one K, so they share one
-    exponent, the smaller (capi.hip act_exponents).  When the halves' own rules disagree, the half that wanted the larger
+    exponent, the smaller (weight_pack.cpp act_exponents).  When the halves' own rules disagree, the half that wanted the larger
     exponent is stored with fewer than the pairs' ~22 bits (its lo pieces run into the f16 subnormals): flag it at load
     time — the range guard reports overflow and NaN, not this precision loss."""
     ea, ev = act_exponent(model, "a_conv5"), act_exponent(model, "v_conv6")

@@ -28,7 +28,7 @@ Differences (host plumbing outside the hot path):
     runs evaluate and predict, two forwards of the same input);
   * predict batches: samples of one slice shape, frame rate and sample rate run as one forward and one ragged
     STFT / ISTFT whatever their lengths (RaggedBatchPredictor; BatchPredictor is the equal-length form) — every
-    result equals the per-sample path's bit for bit (the fp32 forward is batch-invariant, csrc/capi.hip
+    result equals the per-sample path's bit for bit (the fp32 forward is batch-invariant, csrc/forward_plan.h
     choose_ksplit); `-g N` (parsed and ignored by the reference,
     speech_enhancer.py:289) runs N ranks, one per GPU, each on a contiguous block of the samples.
 All spectrogram / network / reconstruction arithmetic goes through libavse (K1, forward, K6).

@@ -4,9 +4,9 @@ dtype stores it, products exact.  So the schemes differ only in how activations 
 
     fp32        activations and weights rounded to float32 (the exact-fp32 path's storage)
     pair        activations as the f16 pair h + l (h = f16(x), l = f16(x - h)), weights as per-output-channel
-                power-of-two scaled pairs (csrc/capi.hip build_layer)
+                power-of-two scaled pairs (csrc/weight_pack.cpp pack_layer)
     pair+sigma  the same with a per-layer power-of-two activation scale 2^sigma_L (include/avse.h: the stored pair is
-                of x 2^sigma_L; sigma from the BN statistics, capi.hip act_exponents)
+                of x 2^sigma_L; sigma from the BN statistics, weight_pack.cpp act_exponents)
 
 Also prints each layer's activation magnitude (RMS, max) and the fraction of values whose lo piece is an f16
 subnormal (|x| 2^sigma < 2^-3).
@@ -60,7 +60,7 @@ def q_w_pair(w, axis_out):
 
 
 def act_exponents(wd, target=6.0):
-    """sigma_L per layer from the BN statistics (the data-free rule of capi.hip): the layer's largest per-channel
+    """sigma_L per layer from the BN statistics (the data-free rule of weight_pack.cpp): the layer's largest per-channel
     |beta| + |gamma| / sqrt(var + eps) * sqrt(var) ~ |beta| + |gamma|, scaled to ~2^target"""
     out = {}
     for name, p in wd.items():

@@ -108,7 +108,7 @@ def make_grouped_conv(grouping, fallback):
         if not (x.shape[2] == x.shape[3] and x.shape[2] in (64, 32, 16, 8) and cin % 16 == 0):
             return fallback(x, kernel, bias, strides, dtype)
         w = torch.as_tensor(np.asarray(kernel, np.float32), dtype=torch.float64)
-        # weights x 2^e_n per output channel, max |w| 2^e_n in [2^14, 2^15) (capi.hip packing)
+        # weights x 2^e_n per output channel, max |w| 2^e_n in [2^14, 2^15) (weight_pack.cpp packing)
         wmax = w.abs().amax(dim=(0, 1, 2)).clamp_min(1e-30)
         wsc = torch.pow(2.0, 14 - torch.floor(torch.log2(wmax)))
         wh, wl = split(w * wsc, 2, torch.float16)
@@ -202,7 +202,7 @@ def emu_dense(x, kernel, bias, form):
     xh, xl = pairs16(xp)
     slabs = [lambda t=t: (xh[:, 16 * t:16 * t + 16], xl[:, 16 * t:16 * t + 16], wh[16 * t:16 * t + 16], wl[16 * t:16 * t + 16])
              for t in range(kp // 16)]
-    nblocks, tiles_n = (kp // 16 + 7) // 8, (cout + 127) // 128   # gemm.hip gemm_s16_ksplit
+    nblocks, tiles_n = (kp // 16 + 7) // 8, (cout + 127) // 128   # forward_plan.h gemm_s16_ksplit
     ks = max(1, min(nblocks, 256 // (4 * tiles_n)))
     G = (nblocks + ks - 1) // ks
     acc = emu_gemm(slabs, x.shape[0], cout, form, blocks_per_split=G if (nblocks + G - 1) // G > 1 else 0)
