@@ -26,6 +26,9 @@ AVSE_VIDEO_F32, AVSE_VIDEO_U8 = 0, 1       # avse_video_dtype: element type of a
 AVSE_ERR_RANGE = 6
 AVSE_EVAL_NMETRICS = 5
 EVAL_METRIC_NAMES = ("snr", "si_sdr", "seg_snr", "stoi", "stoi_kept")   # avse_eval_metric, in slot order
+AVSE_EVAL_NMETRICS_EXT = 6                                               # avse_eval_pairs_ext: ESTOI behind them
+EVAL_METRIC_NAMES_EXT = EVAL_METRIC_NAMES + ("estoi",)
+AVSE_EVAL_ANY_RATE = 1                                                   # avse_eval_flags
 AVSE_RANGE_RECOMPUTE, AVSE_RANGE_ERROR = 0, 1
 # range-guard bits (include/avse.h avse_forward_checked): bit i = plan layer i, 24 / 25 the split audio / video inputs
 LAYER_NAMES = ("a_conv1", "a_conv2", "a_conv3", "a_conv4", "a_conv5", "v_conv1", "v_conv2", "v_conv3", "v_conv4",
@@ -83,7 +86,9 @@ SIGNATURES = {
     "avse_eval_pairs": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _c_void_p, _c_void_p]),
     "avse_eval_pairs_sized": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _int, _c_void_p,
                                      _c_void_p]),
-    "avse_forward_checked": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+    "avse_eval_pairs_ext": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _int, _int, _c_void_p,
+                                   _c_void_p]),
+    "avse_forward_checked":(_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
                                     _c_void_p, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "avse_range_status": (_int, [_c_void_p, _c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "avse_range_snapshot": (_int, [_c_void_p, _c_void_p, _c_void_p]),

@@ -384,7 +384,7 @@ int launch_video_stats_u8(const uint8_t* video, int64_t S, int H, int W, int F, 
                           hipStream_t s);
 
 // ---- evaluate stage (eval.hip) ------------------------------------------------------------
-// avse_eval_pairs: the device copies of the host tables (eval_tables.cpp) and the call's geometry, passed by value.
+// avse_eval_pairs / avse_eval_pairs_ext: the device copies of the host tables (eval_tables.cpp) and the call's geometry, passed by value.
 struct EvalDev {
     const double* taps;    // [2 H + 1] resampling filter for (up, down)
     const double* W;       // [256] STOI's frame window
@@ -393,8 +393,12 @@ struct EvalDev {
     const int* bands;      // [15] (lo, hi) bin ranges
     int up, down, H;
     int win, skip;         // segmental-SNR frame and hop
-    int stoi;              // 0: max(up, down) > 24, slots 3 and 4 are NaN and 0
+    int stoi;              // 0: max(up, down) > 24 without AVSE_EVAL_ANY_RATE, slots 3 and 4 are NaN and 0 (5: NaN)
     int64_t cap;           // upper bound on off[n_pairs] - off[0] the scratch was sized for
+    // avse_eval_pairs_ext
+    const double* ptaps;   // [up][2 H / up + 1] the filter by phase (eval_tables.h resample_taps_by_phase); NULL when
+                           // max(up, down) <= 24: k_eval_resample runs, from `taps`
+    int ms;                // slots per metrics row: 5, or 6 with ESTOI in slot 5
 };
 size_t eval_pairs_scratch_bytes(int64_t n_pairs, const EvalDev& t);
 int launch_eval_pairs(const float* ref, const float* deg, const int64_t* off, int64_t n_pairs, const EvalDev& t,

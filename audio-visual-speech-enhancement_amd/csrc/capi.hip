@@ -146,9 +146,14 @@ int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin,
 }
 
 // the resampling filter for sr -> 10 kHz, STOI's window / bands / twiddles and the segmental SNR's window
-int ensure_eval_tables(avse_ctx* c, int sr, hipStream_t s, const EvalTables** out) {
+// any_rate (AVSE_EVAL_ANY_RATE): a rate with max(up, down) > 24 gets its real filter, by phase; such an entry and the
+// default call's entry of the same rate (the copy filter) are different entries of the cache
+int ensure_eval_tables(avse_ctx* c, int sr, bool any_rate, hipStream_t s, const EvalTables** out) {
+    int up, down;
+    eval_ratio(sr, &up, &down);
+    const bool big = any_rate && std::max(up, down) > kEvalMaxRatio;
     for (const EvalTables& have : c->eval)
-        if (have.sr == sr) {
+        if (have.sr == sr && have.big == big) {
             *out = &have;
             return 0;
         }
@@ -160,19 +165,22 @@ int ensure_eval_tables(avse_ctx* c, int sr, hipStream_t s, const EvalTables** ou
     c->eval_next = (c->eval_next + 1) % 4;
     *out = &t;
     t = EvalTables();
-    int up, down;
-    eval_ratio(sr, &up, &down);
     const int win = seg_snr_window(sr);
     // a rate STOI is not computed for gets the copy filter: the resampler does not run
-    const bool stoi = std::max(up, down) <= kEvalMaxRatio;
+    const bool stoi = big || std::max(up, down) <= kEvalMaxRatio;
     const std::vector<double> taps = stoi ? resample_taps(up, down) : resample_taps(1, 1);
-    if (int rc = table_to_device(taps, t.taps)) return rc;
+    if (big) {
+        if (int rc = table_to_device(resample_taps_by_phase(taps, up), t.ptaps)) return rc;
+    } else {
+        if (int rc = table_to_device(taps, t.taps)) return rc;
+    }
     if (int rc = table_to_device(hann_inner(kStoiFrame), t.W)) return rc;
     if (int rc = table_to_device(stoi_twiddle(), t.twid)) return rc;
     if (int rc = table_to_device(hann_inner(win), t.segw)) return rc;
     if (int rc = table_to_device(stoi_bands(), t.bands)) return rc;
     t.up = up; t.down = down; t.H = ((int)taps.size() - 1) / 2; t.win = win;
     t.sr = sr;
+    t.big = big;
     return 0;
 }
 
@@ -247,6 +255,51 @@ int istft_args(avse_ctx* c, const float* mel_db, const float* stft_ri, int64_t n
     a.gram_inv = c->opt.dense_istft ? nullptr : c->istft.gram_inv.p.get();
     *out = a;
     return 0;
+}
+
+// avse_eval_pairs_sized (flags 0, 5 slots per row) and avse_eval_pairs_ext (6 slots): one set of checks, one launch
+int eval_pairs_call(avse_ctx* c, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
+                    int64_t total_samples, int sr, int flags, int slots, double* metrics, void* stream) {
+    if (!c || !ref || !deg || !off || !metrics) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (flags & ~AVSE_EVAL_ANY_RATE) return fail(AVSE_ERR_INVALID, "unknown avse_eval_flags bit");
+    if (n_pairs < 1) return fail(AVSE_ERR_INVALID, "bad eval_pairs shape (n_pairs >= 1)");
+    if (sr < 8000 || sr > 48000) return fail(AVSE_ERR_INVALID, "sample rate outside 8000 .. 48000");
+    if (n_pairs >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "n_pairs must be below 2^31");
+    if (total_samples < 0 || total_samples > n_pairs * (1LL << 24))
+        return fail(AVSE_ERR_INVALID, "total_samples outside 0 .. n_pairs * 2^24");
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    // The pair lengths live on the device and the call does not wait for them.  The scratch is sized for
+    // total_samples, the caller's off[n_pairs] - off[0]; without it (0), for the most samples the two buffers can hold
+    // behind ref / deg (the extent of their allocations).  The kernels treat offsets that pass the bound as empty pairs.
+    int64_t cap = total_samples > 0 ? total_samples : n_pairs * (1LL << 24);
+    for (const float* p : {ref, deg}) {
+        if (total_samples > 0) break;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AVSE_ERR_INVALID, "ref / deg must point into device allocations (hipMalloc)");
+        }
+        const int64_t room = (int64_t)(((const char*)base + size) - (const char*)p) / (int64_t)sizeof(float);
+        cap = std::min(cap, room);
+    }
+    if (cap < 1) return fail(AVSE_ERR_INVALID, "ref / deg hold no samples");
+    const EvalTables* tables = nullptr;
+    if (int rc = ensure_eval_tables(c, sr, (flags & AVSE_EVAL_ANY_RATE) != 0, (hipStream_t)stream, &tables)) return rc;
+    const EvalTables& t = *tables;
+    // the large ratios scale sample offsets by up to 10000 (eval.hip pair_geom, eval_layout): a cap whose product
+    // would leave int64 could not be allocated anyway (25 bytes of scratch per sample)
+    if (t.big && cap > (1LL << 40)) return fail(AVSE_ERR_OOM, "eval_pairs scratch for more than 2^40 samples");
+    EvalDev d;
+    d.taps = t.taps; d.W = t.W; d.twid = t.twid; d.segw = t.segw; d.bands = t.bands;
+    d.ptaps = t.big ? t.ptaps.p.get() : nullptr;
+    d.up = t.up; d.down = t.down; d.H = t.H;
+    d.win = t.win; d.skip = t.win / 4;
+    d.stoi = t.big || std::max(t.up, t.down) <= kEvalMaxRatio;
+    d.cap = cap;
+    d.ms = slots;
+    if (int rc = grow(c->prep, eval_pairs_scratch_bytes(n_pairs, d), (hipStream_t)stream, "preprocess scratch")) return rc;
+    return launch_eval_pairs(ref, deg, off, n_pairs, d, metrics, c->prep, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -469,40 +522,12 @@ int avse_eval_pairs(avse_ctx* c, const float* ref, const float* deg, const int64
 
 int avse_eval_pairs_sized(avse_ctx* c, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
                           int64_t total_samples, int sr, double* metrics, void* stream) {
-    if (!c || !ref || !deg || !off || !metrics) return fail(AVSE_ERR_INVALID, "NULL argument");
-    if (n_pairs < 1) return fail(AVSE_ERR_INVALID, "bad eval_pairs shape (n_pairs >= 1)");
-    if (sr < 8000 || sr > 48000) return fail(AVSE_ERR_INVALID, "sample rate outside 8000 .. 48000");
-    if (n_pairs >= (1LL << 31)) return fail(AVSE_ERR_UNSUPPORTED, "n_pairs must be below 2^31");
-    if (total_samples < 0 || total_samples > n_pairs * (1LL << 24))
-        return fail(AVSE_ERR_INVALID, "total_samples outside 0 .. n_pairs * 2^24");
-    AVSE_HIP_CHECK(hipSetDevice(c->device));
-    // The pair lengths live on the device and the call does not wait for them.  The scratch is sized for
-    // total_samples, the caller's off[n_pairs] - off[0]; without it (0), for the most samples the two buffers can hold
-    // behind ref / deg (the extent of their allocations).  The kernels treat offsets that pass the bound as empty pairs.
-    int64_t cap = total_samples > 0 ? total_samples : n_pairs * (1LL << 24);
-    for (const float* p : {ref, deg}) {
-        if (total_samples > 0) break;
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(AVSE_ERR_INVALID, "ref / deg must point into device allocations (hipMalloc)");
-        }
-        const int64_t room = (int64_t)(((const char*)base + size) - (const char*)p) / (int64_t)sizeof(float);
-        cap = std::min(cap, room);
-    }
-    if (cap < 1) return fail(AVSE_ERR_INVALID, "ref / deg hold no samples");
-    const EvalTables* tables = nullptr;
-    if (int rc = ensure_eval_tables(c, sr, (hipStream_t)stream, &tables)) return rc;
-    const EvalTables& t = *tables;
-    EvalDev d;
-    d.taps = t.taps; d.W = t.W; d.twid = t.twid; d.segw = t.segw; d.bands = t.bands;
-    d.up = t.up; d.down = t.down; d.H = t.H;
-    d.win = t.win; d.skip = t.win / 4;
-    d.stoi = std::max(t.up, t.down) <= kEvalMaxRatio;
-    d.cap = cap;
-    if (int rc = grow(c->prep, eval_pairs_scratch_bytes(n_pairs, d), (hipStream_t)stream, "preprocess scratch")) return rc;
-    return launch_eval_pairs(ref, deg, off, n_pairs, d, metrics, c->prep, (hipStream_t)stream);
+    return eval_pairs_call(c, ref, deg, off, n_pairs, total_samples, sr, 0, AVSE_EVAL_NMETRICS, metrics, stream);
+}
+
+int avse_eval_pairs_ext(avse_ctx* c, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
+                        int64_t total_samples, int sr, int flags, double* metrics, void* stream) {
+    return eval_pairs_call(c, ref, deg, off, n_pairs, total_samples, sr, flags, AVSE_EVAL_NMETRICS_EXT, metrics, stream);
 }
 
 int avse_video_stats(avse_ctx* c, const float* video, int64_t S, int H, int W, int F, float* mean, float* stdv,

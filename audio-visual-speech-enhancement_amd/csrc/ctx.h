@@ -83,10 +83,12 @@ struct IstftTables {
     Owned<float> gram_inv;   // [n_mels][n_mels] (M M^T)^{-1} in float (n_mels == 80 only)
 };
 
-// device copies of the evaluate stage's tables (eval_tables.cpp), per sample rate
+// device copies of the evaluate stage's tables (eval_tables.cpp), per sample rate and resampling path
 struct EvalTables {
     int sr = -1;
-    Owned<double> taps;      // [2 H + 1]
+    bool big = false;        // max(up, down) > 24 and built for AVSE_EVAL_ANY_RATE: ptaps in place of taps
+    Owned<double> taps;      // [2 H + 1] (big: not allocated)
+    Owned<double> ptaps;     // big only: [up][2 H / up + 1], the taps by phase
     Owned<double> W;         // [256]
     Owned<double> twid;      // [256] (re, im)
     Owned<double> segw;      // [win]
@@ -119,7 +121,7 @@ struct avse_ctx {
     avse::Options opt;          // kernel-path switches (read from AVSE_* once, at creation)
     avse::SpecTables spec;
     avse::IstftTables istft;
-    avse::EvalTables eval[4];   // the last four sample rates of avse_eval_pairs, replaced in turn
+    avse::EvalTables eval[4];   // the last four (sample rate, resampling path) of avse_eval_pairs*, replaced in turn
     int eval_next = 0;
     avse::Owned<float> frames;      // ISTFT frame scratch
     avse::Owned<unsigned> umax;     // spectrogram: one word per utterance

@@ -1,7 +1,8 @@
-// The evaluate stage (include/avse.h avse_eval_pairs): SNR, scale-invariant SDR, segmental SNR and STOI for a ragged
-// group of (clean, degraded) float32 pairs.  Everything is float64 arithmetic; every reduction has an order that
-// depends on the pair's own length only (never on its place in the batch or on its address), so a pair's numbers are
-// the same bits alone and inside any batch.  No floating-point atomics; every store is a vector store.
+// The evaluate stage (include/avse.h avse_eval_pairs, avse_eval_pairs_ext): SNR, scale-invariant SDR, segmental SNR,
+// STOI and (the _ext entry point's sixth slot) ESTOI for a ragged group of (clean, degraded) float32 pairs.  Everything
+// is float64 arithmetic; every reduction has an order that depends on the pair's own length only (never on its place in
+// the batch or on its address), so a pair's numbers are the same bits alone and inside any batch.  No floating-point
+// atomics; every store is a vector store.
 #include <algorithm>
 
 #include "avse_common.h"
@@ -148,9 +149,9 @@ __global__ __launch_bounds__(kThreads) void k_eval_sums_finish(const int64_t* __
         return;
     }
     const Pair p = pair_geom(off, U, u, t);
-    double* m = metrics + u * 5;
+    double* m = metrics + u * t.ms;
     if (p.n == 0) {
-        for (int k = 0; k < 5; ++k) m[k] = quiet_nan();
+        for (int k = 0; k < t.ms; ++k) m[k] = quiet_nan();
         return;
     }
     const double s2 = sums[4 * u + 0], sy = sums[4 * u + 1], d2 = sums[4 * u + 2];
@@ -160,6 +161,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_sums_finish(const int64_t* __
     if (!t.stoi) {
         m[3] = quiet_nan();
         m[4] = 0.0;
+        if (t.ms > 5) m[5] = quiet_nan();
     }
 }
 
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_seg(const float* __restrict__
 
 // The mean of cnt values in a fixed order: thread t sums the contiguous run [t c, (t + 1) c), c = ceil(cnt / 256), in
 // index order, and thread 0 adds the 256 run sums in run order.  NaN for cnt == 0.  One workgroup per pair.
-// MODE 0: the segmental-SNR frame values -> slot 2.  MODE 1: STOI's d(j, m) -> slot 3.
+// MODE 0: the segmental-SNR frame values -> slot 2.  MODE 1: STOI's d(j, m) -> slot 3.  MODE 2: ESTOI's d_m -> slot 5.
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void k_eval_mean(const int64_t* __restrict__ off, int64_t U, EvalDev t,
                                                         const double* __restrict__ vals, const int* __restrict__ kept,
@@ -209,8 +211,8 @@ __global__ __launch_bounds__(kThreads) void k_eval_mean(const int64_t* __restric
         cnt = p.Fs;
     } else {
         const int64_t M = (int64_t)kept[u] - 1;
-        base = 15 * p.fs;
-        cnt = M >= 30 ? 15 * (M - 29) : 0;
+        base = MODE == 1 ? 15 * p.fs : p.fs;
+        cnt = M >= 30 ? (MODE == 1 ? 15 : 1) * (M - 29) : 0;
     }
     const int64_t c = (cnt + kThreads - 1) / kThreads;
     double a = 0.0;
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_mean(const int64_t* __restric
     if (threadIdx.x == 0) {
         double tot = 0.0;
         for (int i = 0; i < kThreads; ++i) tot += run[i];
-        metrics[u * 5 + (MODE == 0 ? 2 : 3)] = (cnt > 0 && p.n > 0) ? tot / (double)cnt : quiet_nan();
+        metrics[u * t.ms + (MODE == 0 ? 2 : MODE == 1 ? 3 : 5)] = (cnt > 0 && p.n > 0) ? tot / (double)cnt : quiet_nan();
     }
 }
 
@@ -270,6 +272,55 @@ __global__ __launch_bounds__(kThreads) void k_eval_resample(const float* __restr
                 const double w = hp[-q * t.up];
                 ax += w * (double)xs[i0 + q];
                 ay += w * (double)ys[i0 + q];
+            }
+            x10[p.s10 + k] = ax;
+            y10[p.s10 + k] = ay;
+        }
+    }
+}
+
+// The same sum for max(up, down) > 24 (avse_eval_pairs_ext with AVSE_EVAL_ANY_RATE), where the 2H + 1 taps do not fit
+// in LDS: the same tiles and the same staged span (clean and degraded interleaved), the taps read from global memory.
+// With H + k down = B up + phase (0 <= phase < up) the tap of sample j is h[phase + (B - j) up], so output k walks row
+// `phase` of t.ptaps, which holds that row's T = 2H / up + 1 taps in ascending j from j = B - (T - 1): a contiguous run
+// per thread, the same terms in the same ascending-j order as above.  A row whose first tap would lie past 2H starts
+// with a zero (eval_tables.h resample_taps_by_phase), so the loop has a fixed trip count and no bounds; the table
+// (up T doubles: 71 KB at 100 / 441, up to 7.7 MB for a rate coprime to 10000) stays in L2.
+// Ranges: k down <= 2^24 up = 1.7e11 and H + k down fit int64; phase T + q < up T <= 970,000 fits int.
+// Dynamic LDS: resample_span float2.
+__global__ __launch_bounds__(kThreads) void k_eval_resample_big(const float* __restrict__ ref,
+                                                                const float* __restrict__ deg,
+                                                                const int64_t* __restrict__ off, int64_t U, EvalDev t,
+                                                                double* __restrict__ x10, double* __restrict__ y10) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int T = 2 * t.H / t.up + 1, span = resample_span(t.up, t.down, t.H);
+    float2* xy = reinterpret_cast<float2*>(lds);
+    const int64_t u = blockIdx.x;
+    const Pair p = pair_geom(off, U, u, t);
+    const float* s = ref + off[u];
+    const float* y = deg + off[u];
+    for (int64_t k0 = (int64_t)blockIdx.y * kThreads; k0 < p.n10; k0 += (int64_t)gridDim.y * kThreads) {
+        const int64_t jlo = (t.H + k0 * t.down) / t.up - (T - 1);   // the tile's first input sample (may be negative)
+        __syncthreads();                                             // the previous tile's reads
+        for (int i = threadIdx.x; i < span; i += kThreads) {
+            const int64_t j = jlo + i;
+            const bool in = j >= 0 && j < p.n;
+            xy[i] = make_float2(in ? s[j] : 0.f, in ? y[j] : 0.f);
+        }
+        __syncthreads();
+        const int64_t k = k0 + threadIdx.x;
+        if (k < p.n10) {
+            const int64_t c = t.H + k * t.down;
+            const int64_t B = c / t.up;
+            const int phase = (int)(c - B * t.up);
+            const int i0 = (int)(B - (T - 1) - jlo);                 // 0 <= i0, i0 + T <= 255 down / up + 1 + T < span
+            const double* hp = t.ptaps + phase * T;
+            double ax = 0.0, ay = 0.0;
+            for (int q = 0; q < T; ++q) {
+                const double w = hp[q];
+                const float2 v = xy[i0 + q];
+                ax += w * (double)v.x;
+                ay += w * (double)v.y;
             }
             x10[p.s10 + k] = ax;
             y10[p.s10 + k] = ay;
@@ -332,7 +383,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_mask(const int64_t* __restric
     }
     if (threadIdx.x == 0) {
         kept[u] = K;
-        metrics[u * 5 + 4] = p.n > 0 ? (double)K : quiet_nan();
+        metrics[u * t.ms + 4] = p.n > 0 ? (double)K : quiet_nan();
     }
 }
 
@@ -543,11 +594,96 @@ __global__ __launch_bounds__(kThreads) void k_eval_corr(const int64_t* __restric
     }
 }
 
+// ---- ESTOI: segment correlations ----------------------------------------------------------------
+constexpr int kSegPitch = 31;   // LDS row pitch of a 15 x 30 tile, in doubles: odd, so rows and columns both spread over the banks
+
+// grid (pairs, G): one wave per segment (the 30 frames ending at m = 30 + segment), four segments per workgroup step.
+// The 15 x 30 tiles of X and Y go to LDS.  1: lanes 0 .. 29 take one (signal, band) row each: the mean over its 30
+// frames in frame order, the row minus the mean, the norm of that from the squares in frame order, the row over
+// (norm + eps), back to LDS.  2: lanes 0 .. 29 take one frame each, the column of X and of Y in registers: the same
+// over the 15 bands in band order, then the column's sum of x y in band order.  Lane 0 adds the 30 column sums in
+// frame order and stores the sum over 30.  The barriers are workgroup-wide and every wave runs every step.
+__global__ __launch_bounds__(kThreads) void k_eval_ecorr(const int64_t* __restrict__ off, int64_t U, EvalDev t,
+                                                         const double* __restrict__ XB, const double* __restrict__ YB,
+                                                         const int* __restrict__ kept, double* __restrict__ de) {
+    __shared__ double tile[kWaves][2][15 * kSegPitch];
+    __shared__ double colsum[kWaves][32];
+    const int64_t u = blockIdx.x;
+    const Pair p = pair_geom(off, U, u, t);
+    const int64_t M = (int64_t)kept[u] - 1;
+    if (M < 30) return;   // block-uniform: ESTOI is NaN
+    const int64_t nseg = M - 29;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double* X = XB + 15 * p.fs;
+    const double* Y = YB + 15 * p.fs;
+    for (int64_t s0 = (int64_t)blockIdx.y * kWaves; s0 < nseg; s0 += (int64_t)gridDim.y * kWaves) {
+        const int64_t seg = s0 + wave;
+        const bool live = seg < nseg;
+        __syncthreads();   // the previous step's reads
+        for (int i = lane; i < 2 * 15 * 30; i += 64) {
+            const int sig = i / 450, r = i - 450 * sig, j = r / 30, k = r - 30 * j;
+            tile[wave][sig][j * kSegPitch + k] = live ? (sig ? Y : X)[(int64_t)j * M + seg + k] : 0.0;
+        }
+        __syncthreads();
+        if (lane < 30) {
+            double* row = tile[wave][lane / 15] + (lane % 15) * kSegPitch;
+            double v[30];
+            double mean = 0.0, sq = 0.0;
+#pragma unroll
+            for (int k = 0; k < 30; ++k) {
+                v[k] = row[k];
+                mean += v[k];
+            }
+            mean /= 30.0;
+#pragma unroll
+            for (int k = 0; k < 30; ++k) {
+                v[k] -= mean;
+                sq += v[k] * v[k];
+            }
+            const double den = sqrt(sq) + kEps;
+#pragma unroll
+            for (int k = 0; k < 30; ++k) row[k] = v[k] / den;
+        }
+        __syncthreads();
+        if (lane < 30) {
+            double xc[15], yc[15];
+            double mx = 0.0, my = 0.0, qx = 0.0, qy = 0.0, dot = 0.0;
+#pragma unroll
+            for (int j = 0; j < 15; ++j) {
+                xc[j] = tile[wave][0][j * kSegPitch + lane];
+                yc[j] = tile[wave][1][j * kSegPitch + lane];
+                mx += xc[j];
+                my += yc[j];
+            }
+            mx /= 15.0;
+            my /= 15.0;
+#pragma unroll
+            for (int j = 0; j < 15; ++j) {
+                xc[j] -= mx;
+                yc[j] -= my;
+                qx += xc[j] * xc[j];
+                qy += yc[j] * yc[j];
+            }
+            const double dx = sqrt(qx) + kEps, dy = sqrt(qy) + kEps;
+#pragma unroll
+            for (int j = 0; j < 15; ++j) dot += (xc[j] / dx) * (yc[j] / dy);
+            colsum[wave][lane] = dot;
+        }
+        __syncthreads();
+        if (lane == 0 && live) {
+            double tot = 0.0;
+            for (int k = 0; k < 30; ++k) tot += colsum[wave][k];
+            de[p.fs + seg] = tot / 30.0;
+        }
+    }
+}
+
 struct Layout {
-    size_t partial, sums, kept, segv, x10, y10, en, idx, xb, yb, d, total;
+    size_t partial, sums, kept, segv, x10, y10, en, idx, xb, yb, d, de, total;
 };
 
-Layout eval_layout(int64_t U, int64_t cap, int up, int down, int skip, bool stoi) {
+// estoi: the ESTOI values behind everything else, so the other offsets (and the total without it) do not move
+Layout eval_layout(int64_t U, int64_t cap, int up, int down, int skip, bool stoi, bool estoi) {
     Layout L;
     size_t o = 0;
     auto take = [&o](size_t bytes) {
@@ -568,6 +704,7 @@ Layout eval_layout(int64_t U, int64_t cap, int up, int down, int skip, bool stoi
     L.xb = take(sizeof(double) * 15 * capf);
     L.yb = take(sizeof(double) * 15 * capf);
     L.d = take(sizeof(double) * 15 * capf);
+    L.de = take(sizeof(double) * (estoi ? capf : 0));
     L.total = o;
     return L;
 }
@@ -575,12 +712,12 @@ Layout eval_layout(int64_t U, int64_t cap, int up, int down, int skip, bool stoi
 }  // namespace
 
 size_t eval_pairs_scratch_bytes(int64_t n_pairs, const EvalDev& t) {
-    return eval_layout(n_pairs, t.cap, t.up, t.down, t.skip, t.stoi != 0).total;
+    return eval_layout(n_pairs, t.cap, t.up, t.down, t.skip, t.stoi != 0, t.stoi != 0 && t.ms > 5).total;
 }
 
 int launch_eval_pairs(const float* ref, const float* deg, const int64_t* off, int64_t U, const EvalDev& t,
                       double* metrics, void* scratch, hipStream_t s) {
-    const Layout L = eval_layout(U, t.cap, t.up, t.down, t.skip, t.stoi != 0);
+    const Layout L = eval_layout(U, t.cap, t.up, t.down, t.skip, t.stoi != 0, t.stoi != 0 && t.ms > 5);
     char* base = reinterpret_cast<char*>(scratch);
     double* partial = reinterpret_cast<double*>(base + L.partial);
     double* sums = reinterpret_cast<double*>(base + L.sums);
@@ -610,8 +747,13 @@ int launch_eval_pairs(const float* ref, const float* deg, const int64_t* off, in
     hipLaunchKernelGGL(k_eval_mean<0>, per_pair, blk, 0, s, off, U, t, (const double*)segv, (const int*)kept, metrics);
     AVSE_HIP_CHECK(hipGetLastError());
     if (!t.stoi) return 0;
-    const size_t res_lds = sizeof(double) * (size_t)(t.up + 2 * t.H + 1) + 2 * sizeof(float) * (size_t)resample_span(t.up, t.down, t.H);
-    hipLaunchKernelGGL(k_eval_resample, wide, blk, res_lds, s, ref, deg, off, U, t, x10, y10);
+    const int span = resample_span(t.up, t.down, t.H);
+    if (t.ptaps) {
+        hipLaunchKernelGGL(k_eval_resample_big, wide, blk, sizeof(float2) * (size_t)span, s, ref, deg, off, U, t, x10, y10);
+    } else {
+        const size_t res_lds = sizeof(double) * (size_t)(t.up + 2 * t.H + 1) + 2 * sizeof(float) * (size_t)span;
+        hipLaunchKernelGGL(k_eval_resample, wide, blk, res_lds, s, ref, deg, off, U, t, x10, y10);
+    }
     AVSE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_eval_energy, wide, blk, 0, s, off, U, t, (const double*)x10, en);
     AVSE_HIP_CHECK(hipGetLastError());
@@ -624,6 +766,13 @@ int launch_eval_pairs(const float* ref, const float* deg, const int64_t* off, in
                        (const int*)kept, d);
     AVSE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_eval_mean<1>, per_pair, blk, 0, s, off, U, t, (const double*)d, (const int*)kept, metrics);
+    AVSE_HIP_CHECK(hipGetLastError());
+    if (t.ms <= 5) return 0;
+    double* de = reinterpret_cast<double*>(base + L.de);
+    hipLaunchKernelGGL(k_eval_ecorr, wide, blk, 0, s, off, U, t, (const double*)xb, (const double*)yb,
+                       (const int*)kept, de);
+    AVSE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_eval_mean<2>, per_pair, blk, 0, s, off, U, t, (const double*)de, (const int*)kept, metrics);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }

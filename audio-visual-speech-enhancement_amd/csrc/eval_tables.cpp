@@ -45,6 +45,18 @@ std::vector<double> resample_taps(int up, int down) {
     return h;
 }
 
+std::vector<double> resample_taps_by_phase(const std::vector<double>& h, int up) {
+    const size_t last = h.size() - 1;            // 2H
+    const size_t T = last / (size_t)up + 1;
+    std::vector<double> rows((size_t)up * T);
+    for (size_t phase = 0; phase < (size_t)up; ++phase)
+        for (size_t q = 0; q < T; ++q) {
+            const size_t i = phase + (size_t)up * (T - 1 - q);
+            rows[phase * T + q] = i <= last ? h[i] : 0.0;
+        }
+    return rows;
+}
+
 std::vector<double> hann_inner(int n) {
     std::vector<double> w(n > 0 ? n : 0);
     for (int i = 0; i < n; ++i) w[i] = 0.5 * (1.0 - std::cos(2.0 * M_PI * (double)(i + 1) / (double)(n + 1)));

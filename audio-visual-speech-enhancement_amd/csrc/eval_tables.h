@@ -10,7 +10,7 @@ constexpr int kStoiFrame = 256;      // frame length, hop kStoiFrame / 2
 constexpr int kStoiFft = 512;
 constexpr int kStoiBands = 15;       // third-octave bands from 150 Hz
 constexpr int kStoiSegment = 30;     // frames per intermediate-intelligibility segment
-constexpr int kEvalMaxRatio = 24;    // STOI is computed when max(up, down) <= 24
+constexpr int kEvalMaxRatio = 24;    // max(up, down) up to which the taps fit in LDS; above it STOI needs AVSE_EVAL_ANY_RATE
 
 // up / down = (10000 / g) / (sr / g), g = gcd(10000, sr)
 void eval_ratio(int sr, int* up, int* down);
@@ -22,6 +22,12 @@ double bessel_i0(double x);
 // i = 0 .. 2H, H = 10 max(up, down), fc = 1 / max(up, down), normalised so that sum(h) / up == 1.
 // up == down: the single tap {1.0} (a copy).
 std::vector<double> resample_taps(int up, int down);
+
+// The taps h[0 .. 2H] (resample_taps, up != down) by phase: [up][T], T = 2H / up + 1.  Row `phase` holds the taps
+// h[phase + i up] in DESCENDING i: entry q is h[phase + (T - 1 - q) up], or 0 where that index passes 2H (entry 0 of
+// the rows with phase > 2H mod up).  An output whose tap indices are congruent to `phase` reads its row front to back
+// while its input samples ascend (eval.hip k_eval_resample_big).
+std::vector<double> resample_taps_by_phase(const std::vector<double>& h, int up);
 
 // W[i] = 0.5 (1 - cos(2 pi (i + 1) / (n + 1))), i < n: STOI's frame window (n = 256) and the segmental SNR's
 std::vector<double> hann_inner(int n);

@@ -649,15 +649,9 @@ def _pack_f32(sigs, dev):
 EVAL_MAX_SAMPLES = 1 << 24
 
 
-def eval_pairs(ref, deg, sample_rate=16000, device=None):
-    """The evaluate stage (speech_enhancement_evaluator.py:34-64 with open measures in PESQ's place): SNR, SI-SDR,
-    segmental SNR and STOI of n (clean, degraded) pairs in one avse_eval_pairs call (include/avse.h has the definitions).
-
-    ref / deg: sequences of mono signals (numpy or tensors, int16 or floating point, ragged), or one 2-D array / tensor
-    [n, samples] each; pair u is cut to min(len ref[u], len deg[u]).  Device tensors are packed on the device (no host
-    copy).  Or the packed form: ref = (1-D float32 device tensor, int64 offsets [n + 1]) and deg = a 1-D float32 device
-    tensor laid out by the same offsets.
-    Returns a float64 device tensor [n, 5]: snr, si_sdr, seg_snr, stoi, stoi_kept (_lib.EVAL_METRIC_NAMES)."""
+def _eval_packed(ref, deg, sample_rate, device):
+    """eval_pairs' / eval_pairs_ext's arguments, checked -> (packed ref, packed deg, host offsets [n + 1], device,
+    sample rate): every refusal happens before anything touches a device."""
     sr = int(sample_rate)
     if not 8000 <= sr <= 48000:
         raise ValueError(f"sample_rate {sample_rate} outside 8000 .. 48000")
@@ -683,7 +677,6 @@ def eval_pairs(ref, deg, sample_rate=16000, device=None):
         lens = [min(int(a.shape[0]), int(b.shape[0])) for a, b in zip(rs, ds)]
         off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         dev = None
-    n = off.size - 1
     lens = np.diff(off)
     if np.any(lens == 0):
         raise _lib.AvseError(f"avse_eval_pairs refused (status 1, AVSE_ERR_INVALID): pair {int(np.argmin(lens))} is empty")
@@ -697,6 +690,20 @@ def eval_pairs(ref, deg, sample_rate=16000, device=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         rp = _pack_f32([a[:k] for a, k in zip(rs, lens)], dev)
         dp = _pack_f32([a[:k] for a, k in zip(ds, lens)], dev)
+    return rp, dp, off, dev, sr
+
+
+def eval_pairs(ref, deg, sample_rate=16000, device=None):
+    """The evaluate stage (speech_enhancement_evaluator.py:34-64 with open measures in PESQ's place): SNR, SI-SDR,
+    segmental SNR and STOI of n (clean, degraded) pairs in one avse_eval_pairs call (include/avse.h has the definitions).
+
+    ref / deg: sequences of mono signals (numpy or tensors, int16 or floating point, ragged), or one 2-D array / tensor
+    [n, samples] each; pair u is cut to min(len ref[u], len deg[u]).  Device tensors are packed on the device (no host
+    copy).  Or the packed form: ref = (1-D float32 device tensor, int64 offsets [n + 1]) and deg = a 1-D float32 device
+    tensor laid out by the same offsets.
+    Returns a float64 device tensor [n, 5]: snr, si_sdr, seg_snr, stoi, stoi_kept (_lib.EVAL_METRIC_NAMES)."""
+    rp, dp, off, dev, sr = _eval_packed(ref, deg, sample_rate, device)
+    n = off.size - 1
     ctx = _lib.context(dev)
     off_d = torch.from_numpy(off).to(dev)
     out = torch.empty((n, _lib.AVSE_EVAL_NMETRICS), dtype=torch.float64, device=dev)
@@ -705,6 +712,24 @@ def eval_pairs(ref, deg, sample_rate=16000, device=None):
         _lib.check(_lib.load().avse_eval_pairs_sized(ctx.handle, _lib.ptr(rp), _lib.ptr(dp), _lib.ptr(off_d), n,
                                                      int(off[-1] - off[0]), sr, _lib.ptr(out),
                                                      _lib.stream_handle(dev)), "avse_eval_pairs")
+    return out
+
+
+def eval_pairs_ext(ref, deg, sample_rate=16000, any_rate=True, device=None):
+    """eval_pairs with ESTOI as a sixth column, and (any_rate) STOI, its frame count and ESTOI at every sample rate in
+    8000 .. 48000 instead of NaN / 0 where max(up, down) > 24 (44100, 22050, 11025, ..): one avse_eval_pairs_ext call.
+    The same inputs and the same refusals as eval_pairs; columns 0 .. 4 are eval_pairs' bits wherever it computes them.
+    Returns a float64 device tensor [n, 6]: _lib.EVAL_METRIC_NAMES_EXT."""
+    rp, dp, off, dev, sr = _eval_packed(ref, deg, sample_rate, device)
+    n = off.size - 1
+    ctx = _lib.context(dev)
+    off_d = torch.from_numpy(off).to(dev)
+    out = torch.empty((n, _lib.AVSE_EVAL_NMETRICS_EXT), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_eval_pairs_ext(ctx.handle, _lib.ptr(rp), _lib.ptr(dp), _lib.ptr(off_d), n,
+                                                   int(off[-1] - off[0]), sr,
+                                                   _lib.AVSE_EVAL_ANY_RATE if any_rate else 0, _lib.ptr(out),
+                                                   _lib.stream_handle(dev)), "avse_eval_pairs_ext")
     return out
 
 

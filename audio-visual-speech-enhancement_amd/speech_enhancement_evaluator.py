@@ -3,8 +3,9 @@ computed on the device in PESQ's place: SNR, scale-invariant SDR, segmental SNR 
 include/avse.h avse_eval_pairs).  PESQ itself stays what it is in the reference, an external binary: when its path is
 given, it is run per sample as the reference runs it.
 
-    python speech_enhancement_evaluator.py ENHANCEMENT_DIR [PESQ_BIN_PATH]
+    python speech_enhancement_evaluator.py [--extended] ENHANCEMENT_DIR [PESQ_BIN_PATH]
 
+--extended adds ESTOI and computes STOI at every sample rate from 8 to 48 kHz (ops.eval_pairs_ext), 44.1 kHz included;
 walks ENHANCEMENT_DIR/<speaker>/<sample>/{source,enhanced,mixture}.wav as `predict` writes them."""
 import argparse
 import os
@@ -19,6 +20,7 @@ from . import _lib, ops
 from .audio_io import AudioSignal
 
 METRICS = ("snr", "si_sdr", "seg_snr", "stoi")      # the printed slots of avse_eval_pairs, in slot order
+ESTOI_SLOT = 5                                       # avse_eval_pairs_ext's sixth slot, printed after stoi
 WAVS = ("source", "enhanced", "mixture")
 MOS_LINE = re.compile(r"\(Raw MOS, MOS-LQO\):\s+= (-?[0-9.]+?)\s+([0-9.]+?)$", re.MULTILINE)
 SKIP = "failed to evaluate pesq (%s). skipping"      # the reference's message, kept although PESQ is optional here
@@ -60,12 +62,18 @@ def load_sample(directory):
     return signals, rates.pop()
 
 
+def columns(extended):
+    """(name, slot) of the printed metrics, in print order."""
+    return [(name, slot) for slot, name in enumerate(METRICS)] + ([("estoi", ESTOI_SLOT)] if extended else [])
+
+
 class _Batches:
     """Samples waiting for a device call, per sample rate; a full group (or, at the end, every group) is evaluated in
-    one ops.eval_pairs call over its (source, enhanced) pairs followed by its (source, mixture) pairs."""
+    one ops.eval_pairs call (extended: ops.eval_pairs_ext) over its (source, enhanced) pairs followed by its
+    (source, mixture) pairs."""
 
-    def __init__(self, size, done):
-        self.size, self.done, self.waiting = max(1, int(size)), done, {}
+    def __init__(self, size, done, extended=False):
+        self.size, self.done, self.waiting, self.extended = max(1, int(size)), done, {}, extended
 
     def add(self, row, signals):
         group = self.waiting.setdefault(row["sample_rate"], [])
@@ -78,9 +86,12 @@ class _Batches:
         if not group:
             return
         clean = [sig["source"] for _, sig in group]
+        degraded = [sig["enhanced"] for _, sig in group] + [sig["mixture"] for _, sig in group]
         try:
-            table = ops.eval_pairs(clean + clean, [sig["enhanced"] for _, sig in group] +
-                                   [sig["mixture"] for _, sig in group], sample_rate=rate).cpu().numpy()
+            if self.extended:
+                table = ops.eval_pairs_ext(clean + clean, degraded, sample_rate=rate).cpu().numpy()
+            else:
+                table = ops.eval_pairs(clean + clean, degraded, sample_rate=rate).cpu().numpy()
         except (_lib.AvseError, ValueError, TypeError) as refusal:
             # what the binding refuses costs this group only; any other error (a device error among them) ends the run
             for _ in group:
@@ -88,7 +99,7 @@ class _Batches:
             return
         for k, (row, _) in enumerate(group):
             row["enhanced"], row["mixture"] = table[k], table[len(group) + k]
-            for slot, name in enumerate(METRICS):
+            for name, slot in columns(self.extended):
                 print("mixture %s: %f, enhanced %s: %f" % (name, row["mixture"][slot], name, row["enhanced"][slot]))
             self.done.append(row)
 
@@ -97,12 +108,13 @@ class _Batches:
             self.run(rate)
 
 
-def evaluate(enhancement_dir_path, pesq_bin_path=None, batch=64):
+def evaluate(enhancement_dir_path, pesq_bin_path=None, batch=64, extended=False):
     """Per sample, the metrics of (source, enhanced) and (source, mixture), in device batches of up to `batch` samples
     of one sample rate.  Prints the reference's lines per metric and returns the per-sample table, in the reference's
-    order: [{speaker, sample, sample_rate, enhanced [5], mixture [5], (enhanced_pesq, mixture_pesq)}]."""
+    order: [{speaker, sample, sample_rate, enhanced [5], mixture [5], (enhanced_pesq, mixture_pesq)}].
+    extended: rows of 6 from ops.eval_pairs_ext (STOI at every sample rate, ESTOI), and the estoi lines after stoi's."""
     done = []
-    batches = _Batches(batch, done)
+    batches = _Batches(batch, done, extended)
     order = {}
     for speaker, sample, directory in sample_dirs(enhancement_dir_path):
         print("evaluating %s..." % sample)
@@ -122,8 +134,7 @@ def evaluate(enhancement_dir_path, pesq_bin_path=None, batch=64):
     batches.run_all()
     done.sort(key=lambda row: order[id(row)])     # groups finish out of order; the table keeps the walk's order
 
-    columns = [(name, slot) for slot, name in enumerate(METRICS)]
-    for name, slot in columns:
+    for name, slot in columns(extended):
         for kind in ("enhanced", "mixture"):
             values = [row[kind][slot] for row in done]
             print("mean %s %s: " % (kind, name), np.mean(values), "std %s %s: " % (kind, name), np.std(values))
@@ -139,8 +150,13 @@ def main(argv=None):
                                               "every sample under a predict output directory")
     cli.add_argument("enhancement_dir", help="<dir>/<speaker>/<sample>/{source,enhanced,mixture}.wav")
     cli.add_argument("pesq_bin_path", nargs="?", default=None, help="the external PESQ binary (optional)")
+    cli.add_argument("--extended", action="store_true",
+                     help="also ESTOI, and STOI at every sample rate from 8 to 48 kHz (44.1 kHz included)")
     given = cli.parse_args(argv)
-    evaluate(given.enhancement_dir, given.pesq_bin_path)
+    if given.extended:
+        evaluate(given.enhancement_dir, given.pesq_bin_path, extended=True)
+    else:
+        evaluate(given.enhancement_dir, given.pesq_bin_path)
 
 
 if __name__ == "__main__":

@@ -33,7 +33,7 @@ extern "C" {
  * 3: AVSE_F32_SPLIT range guard (avse_forward_checked, avse_range_status, status AVSE_ERR_RANGE), per-layer activation
  *    exponents (avse_weights_act_exponents, option no_act_scale); later additions under the same version (new symbols
  *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
- *    avse_eval_pairs_sized */
+ *    avse_eval_pairs_sized, avse_eval_pairs_ext */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -460,7 +460,8 @@ int avse_build_flags(void);
 /* ---- evaluate ---------------------------------------------------------------------------- */
 
 enum avse_eval_metric { AVSE_EVAL_SNR = 0, AVSE_EVAL_SI_SDR = 1, AVSE_EVAL_SEG_SNR = 2,
-                        AVSE_EVAL_STOI = 3, AVSE_EVAL_STOI_KEPT = 4 };
+                        AVSE_EVAL_STOI = 3, AVSE_EVAL_STOI_KEPT = 4,
+                        AVSE_EVAL_ESTOI = 5 /* avse_eval_pairs_ext only */ };
 #define AVSE_EVAL_NMETRICS 5
 /* Replaces speech_enhancement_evaluator.py:34-64 (the per-sample measure; PESQ itself stays an external binary).
  * Four open measures of a (clean, degraded) pair, for a ragged group of pairs in one call.
@@ -493,7 +494,8 @@ enum avse_eval_metric { AVSE_EVAL_SNR = 0, AVSE_EVAL_SI_SDR = 1, AVSE_EVAL_SEG_S
  *       sum(h) / up == 1; n10 = ceil(n up / down) outputs, y10[k] = sum_j h[H + k down - j up] x[j] over the j that keep
  *       the tap index in [0, 2H].  up == down is a copy.  (This is scipy's filter, not the MATLAB / pystoi one: values
  *       may differ from those tools in the low decimals.)  STOI is computed when max(up, down) <= 24; otherwise slots
- *       3 and 4 are NaN and 0 and the other metrics are still computed.
+ *       3 and 4 are NaN and 0 and the other metrics are still computed (avse_eval_pairs_ext with AVSE_EVAL_ANY_RATE
+ *       computes STOI at every rate).
  *    2. Silent-frame removal: W[i] = 0.5 (1 - cos(2 pi (i + 1) / 257)), i < 256; frames start at i = 0, 128, .. while
  *       i < n10 - 256 (strict); e_i = 20 log10(||W x_i|| + eps) from the clean signal; a frame is kept when
  *       e_i > max(e) - 40.  K, the number of kept frames, is slot AVSE_EVAL_STOI_KEPT.  The kept windowed frames of
@@ -505,6 +507,13 @@ enum avse_eval_metric { AVSE_EVAL_SNR = 0, AVSE_EVAL_SI_SDR = 1, AVSE_EVAL_SEG_S
  *    4. For m = 30 .. M and each band j, over the 30 frames ending at m: a = sqrt(sum X^2 / (sum Y^2 + eps)),
  *       Y' = min(a Y, X (1 + 10^(15/20))), d = sum (X - mean X)(Y' - mean Y') / (||X - mean X|| ||Y' - mean Y'|| + eps).
  *       STOI = the mean of d over all j and m; NaN when M < 30 (no frames at all included).
+ *    5. ESTOI (Jensen & Taal 2016; avse_eval_pairs_ext only, slot AVSE_EVAL_ESTOI): the same X, Y of step 3, no
+ *       clipping and no factor a.  For m = 30 .. M, x = X[:, m-30:m] and y = Y[:, m-30:m] (15 bands x 30 frames) are
+ *       each normalised twice: per band, minus the mean over its 30 frames, then over (its Euclidean norm + eps); then
+ *       per frame, minus the mean over the 15 bands, then over (that column's norm + eps).
+ *       d_m = (1/30) sum_{j,k} x y; ESTOI = the mean of d_m over m = 30 .. M, NaN when M < 30.  (pystoi adds
+ *       eps-scaled random noise before each normalisation where this adds eps to the denominators: the value here is
+ *       deterministic and may differ from pystoi's in the low decimals.)
  * Determinism: no floating-point atomics; every sum has an order fixed by the pair's own length (16 partial sums per
  * pair combined in part order; frame and segment values stored, then summed in index order by contiguous runs), so two
  * calls agree bit for bit and a pair's five numbers are the same bits alone and inside any batch, at any offset.
@@ -523,6 +532,28 @@ int avse_eval_pairs(avse_ctx* ctx, const float* ref, const float* deg, const int
  * that pass it make their pairs empty (NaN rows), nothing is written out of bounds. */
 int avse_eval_pairs_sized(avse_ctx* ctx, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
                           int64_t total_samples, int sr, double* metrics, void* stream);
+
+#define AVSE_EVAL_NMETRICS_EXT 6   /* slots 0 .. 4 as avse_eval_pairs, slot 5 = AVSE_EVAL_ESTOI */
+enum avse_eval_flags { AVSE_EVAL_ANY_RATE = 1 };
+/* avse_eval_pairs_sized with a sixth slot per pair, ESTOI (step 5 above), and STOI at every rate on request.
+ *   metrics    [n_pairs][AVSE_EVAL_NMETRICS_EXT] float64
+ *   flags      0 or AVSE_EVAL_ANY_RATE; any other bit is AVSE_ERR_INVALID
+ * Arguments, refusals, the scratch rule (total_samples, 0 = unknown), asynchrony and capture rules are those of
+ * avse_eval_pairs_sized.
+ * flags == 0: slots 0 .. 4 are the bits avse_eval_pairs_sized writes (the same kernels in the same order); ESTOI is NaN
+ *   wherever STOI is NaN, the rates with max(up, down) > 24 included.
+ * AVSE_EVAL_ANY_RATE: STOI, K and ESTOI are computed for every sr in 8000 .. 48000.  Rates with max(up, down) <= 24
+ *   give the same bits as without the flag.  The larger ratios (44100: 100 / 441; a rate coprime to 10000: up = 10000)
+ *   use step 1's formula and filter unchanged, H = 10 max(up, down) up to 479,990, each output summed in ascending j
+ *   over its 2H / up + 1 taps; the filter is kept by phase on the device, up to 7.7 MB per rate.  At such a ratio a
+ *   scratch bound (total_samples, or the room behind ref / deg) above 2^40 samples is AVSE_ERR_OOM.
+ * ESTOI's sums: a band's mean and norm over its 30 frames in frame order; a frame's mean, norm and sum of x y over the
+ * 15 bands in band order; d_m from the 30 frame sums in frame order; the mean of d_m as STOI's mean of d.  A pair's six
+ * numbers are the same bits alone and inside any batch, at any offset, with or without the flag where both compute them.
+ * The context's four table sets are per (rate, large-ratio filter): an AVSE_EVAL_ANY_RATE call and a default call at
+ * 44100 use two of them. */
+int avse_eval_pairs_ext(avse_ctx* ctx, const float* ref, const float* deg, const int64_t* off, int64_t n_pairs,
+                        int64_t total_samples, int sr, int flags, double* metrics, void* stream);
 
 /* Number of forward scratch buffers reported by avse_debug_scratch. */
 #define AVSE_DEBUG_NBUF 20
