@@ -106,6 +106,19 @@ SIGNATURES = {
                                       _c_void_p]),
     "avse_trainer_step_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _c_void_p, _i64, _flt,
                                        _flt, ctypes.c_uint32, _int, _c_void_p, _c_void_p]),
+    # streaming sessions: create(ctx, weights, n_streams, sr, n_fft, hop, spf, n_mels, fmin, fmax, amin, top_db,
+    # video_dtype, max_slices, out); push(s, samples, n_new, stride, video, v_new, vmean, vstd, out, out_stride,
+    # host n_out, mel_db, pred_db, stream)
+    "avse_stream_create": (_int, [_c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _int, _flt, _flt, _flt, _flt, _int,
+                                  _i64, ctypes.POINTER(_c_void_p)]),
+    "avse_stream_counts": (_int, [_c_void_p, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                  ctypes.POINTER(_i64)]),
+    "avse_stream_push": (_int, [_c_void_p, _c_void_p, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64,
+                                ctypes.POINTER(_i64), _c_void_p, _c_void_p, _c_void_p]),
+    "avse_stream_flush": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, ctypes.POINTER(_i64), _c_void_p,
+                                 _c_void_p, _c_void_p]),
+    "avse_stream_reset": (_int, [_c_void_p, _c_void_p]),
+    "avse_stream_destroy": (None, [_c_void_p]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

@@ -110,39 +110,11 @@ int table_to_device(const std::vector<T>& h, Owned<D>& out) {
 }
 
 int ensure_spec_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, double fmax) {
-    SpecTables& t = c->spec;
-    if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
-    t = SpecTables();
-    const DftTables dft = dft_tables(n_fft);
-    const MelBands mb = mel_bands(sr, n_fft, n_mels, fmin, fmax);
-    if (int rc = table_to_device(dft.twiddle, t.twiddle)) return rc;
-    if (int rc = table_to_device(dft.window, t.window)) return rc;
-    if (int rc = table_to_device(mb.start, t.mel.start)) return rc;
-    if (int rc = table_to_device(mb.width, t.mel.width)) return rc;
-    if (int rc = table_to_device(mb.weight, t.mel.weight)) return rc;
-    t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
-    std::memcpy(t.mel.seg_nq, mb.seg_nq, sizeof(t.mel.seg_nq));
-    std::memcpy(t.mel.seg_nq4, mb.seg_nq4, sizeof(t.mel.seg_nq4));
-    t.mel.max_width = mb.max_width;
-    return 0;
+    return build_spec_tables(c->spec, sr, n_fft, n_mels, fmin, fmax);
 }
 
-// pinv(mel), the inverse-DFT tables and, where the bank allows it, the fused kernel's tridiagonal form (spec_tables.cpp)
 int ensure_istft_tables(avse_ctx* c, int sr, int n_fft, int n_mels, double fmin, double fmax) {
-    IstftTables& t = c->istft;
-    if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
-    t = IstftTables();
-    const IstftHostTables h = istft_tables(sr, n_fft, n_mels, fmin, fmax);
-    const DftTables dft = dft_tables(2 * (n_fft / 2));
-    if (int rc = table_to_device(h.pinvT, t.pinvT)) return rc;
-    if (int rc = table_to_device(dft.twiddle, t.twiddle)) return rc;
-    if (int rc = table_to_device(dft.window, t.window)) return rc;
-    if (!h.bins.empty())
-        if (int rc = table_to_device(h.bins, t.bins)) return rc;
-    if (!h.gram_inv.empty())
-        if (int rc = table_to_device(h.gram_inv, t.gram_inv)) return rc;
-    t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
-    return 0;
+    return build_istft_tables(c->istft, sr, n_fft, n_mels, fmin, fmax);
 }
 
 // the resampling filter for sr -> 10 kHz, STOI's window / bands / twiddles and the segmental SNR's window
@@ -305,6 +277,41 @@ int eval_pairs_call(avse_ctx* c, const float* ref, const float* deg, const int64
 }  // namespace
 
 namespace avse {
+// the STFT / mel tables of one geometry into `t` (kept when `t` already holds them); the current device's
+int build_spec_tables(SpecTables& t, int sr, int n_fft, int n_mels, double fmin, double fmax) {
+    if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
+    t = SpecTables();
+    const DftTables dft = dft_tables(n_fft);
+    const MelBands mb = mel_bands(sr, n_fft, n_mels, fmin, fmax);
+    if (int rc = table_to_device(dft.twiddle, t.twiddle)) return rc;
+    if (int rc = table_to_device(dft.window, t.window)) return rc;
+    if (int rc = table_to_device(mb.start, t.mel.start)) return rc;
+    if (int rc = table_to_device(mb.width, t.mel.width)) return rc;
+    if (int rc = table_to_device(mb.weight, t.mel.weight)) return rc;
+    t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
+    std::memcpy(t.mel.seg_nq, mb.seg_nq, sizeof(t.mel.seg_nq));
+    std::memcpy(t.mel.seg_nq4, mb.seg_nq4, sizeof(t.mel.seg_nq4));
+    t.mel.max_width = mb.max_width;
+    return 0;
+}
+
+// pinv(mel), the inverse-DFT tables and, where the bank allows it, the fused kernel's tridiagonal form (spec_tables.cpp)
+int build_istft_tables(IstftTables& t, int sr, int n_fft, int n_mels, double fmin, double fmax) {
+    if (t.sr == sr && t.n_fft == n_fft && t.n_mels == n_mels && t.fmin == fmin && t.fmax == fmax) return 0;
+    t = IstftTables();
+    const IstftHostTables h = istft_tables(sr, n_fft, n_mels, fmin, fmax);
+    const DftTables dft = dft_tables(2 * (n_fft / 2));
+    if (int rc = table_to_device(h.pinvT, t.pinvT)) return rc;
+    if (int rc = table_to_device(dft.twiddle, t.twiddle)) return rc;
+    if (int rc = table_to_device(dft.window, t.window)) return rc;
+    if (!h.bins.empty())
+        if (int rc = table_to_device(h.bins, t.bins)) return rc;
+    if (!h.gram_inv.empty())
+        if (int rc = table_to_device(h.gram_inv, t.gram_inv)) return rc;
+    t.sr = sr; t.n_fft = n_fft; t.n_mels = n_mels; t.fmin = fmin; t.fmax = fmax;
+    return 0;
+}
+
 // checked build: wait for the stream, then report the first device-side check that fired (avse_common.h DebugHit)
 int debug_poll(void* stream) {
     if constexpr (!kDebugBuild) return 0;

@@ -96,6 +96,11 @@ struct EvalTables {
     int up = 1, down = 1, H = 0, win = 0;
 };
 
+// The tables of one geometry on the current device, kept when `t` already holds them (capi.hip): the context's own
+// (replaced when a call names another geometry) and a streaming session's, which lives as long as the session.
+int build_spec_tables(SpecTables& t, int sr, int n_fft, int n_mels, double fmin, double fmax);
+int build_istft_tables(IstftTables& t, int sr, int n_fft, int n_mels, double fmin, double fmax);
+
 struct GpuLayer {
     LayerDef def;
     int cin_pad = 0;

@@ -19,6 +19,7 @@
 
 #include "avse_common.h"
 #include "fft_common.h"
+#include "frame640.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap
 #define AVSE_WPE4
@@ -30,10 +31,10 @@ namespace avse {
 AVSE_DEBUG_RECORD(debug_read_istft)
 namespace {
 
-constexpr int FPG = 3;
-// frame slot stride in float2: >= 340 (the 20 x 17 layout of the DFT steps); 353 makes 2 ZS = 2 (mod 32) dwords, so
-// the step-3 stores of 16 consecutive frames at one bin (ds_write_b64 lane groups) hit distinct bank pairs (340: 4-way)
-constexpr int ZS = 353;
+// the unfused 640-point frames and the overlap-add of one sample: frame640.h, shared with stream.hip
+using istft640::FPG;
+using istft640::ZS;
+using istft640::unit_phase;
 
 __device__ __forceinline__ float mel_at(const IstftArgs& a, long long u, int m, int t) {
     if (a.spf > 0) {
@@ -41,14 +42,6 @@ __device__ __forceinline__ float mel_at(const IstftArgs& a, long long u, int m, 
         return a.mel_db[((u * a.n_slices + sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
     }
     return a.mel_db[(u * a.n_mels + m) * (long long)a.T + t];
-}
-
-// D / |D| (librosa.magphase; 1 where D == 0) as D * rsq(|D|^2): one v_rsq_f32 and two multiplies instead of a
-// square root and two IEEE divisions (~10 instructions each; 16 per lane per chunk in k_istft_fused)
-__device__ __forceinline__ float2 unit_phase(float2 d) {
-    const float r2 = d.x * d.x + d.y * d.y;
-    const float s = __builtin_amdgcn_rsqf(r2);
-    return r2 > 0.f ? make_float2(d.x * s, d.y * s) : make_float2(1.f, 0.f);
 }
 
 // a D / |D| (1 where D == 0) in packed form
@@ -61,94 +54,17 @@ __device__ __forceinline__ v2f pk_unit_phase(v2f d, float a) {
 
 // X[k] = (pinv(mel) @ 10^(dB/20))[k] * D[k]/|D[k]| for one frame, k in [0, nb)
 __device__ __forceinline__ float2 spectrum_bin(const IstftArgs& a, const float* amp, long long u, int k, int t) {
-    float acc = 0.f;
-    for (int m = 0; m < a.n_mels; ++m) acc = fmaf(a.pinvT[m * a.nb + k], amp[m], acc);
-    const float2 d = a.stft[(u * a.nb + k) * (long long)a.stft_frames + t];
-    const float2 ph = unit_phase(d);
-    return make_float2(acc * ph.x, acc * ph.y);
+    return istft640::spectrum_bin(a.pinvT, a.n_mels, a.nb, amp, k, a.stft[(u * a.nb + k) * (long long)a.stft_frames + t]);
 }
 
+// one 64-lane block per 3 frames of one utterance (istft640::synth_frames) into the frame scratch for k_ola
 __global__ __launch_bounds__(64) void k_istft640(IstftArgs a) {
-    __shared__ float amp[FPG][80];
-    __shared__ float2 xb[FPG][324];
-    __shared__ float2 zbuf[FPG * ZS];
-    const int lane = threadIdx.x;
     const long long u = blockIdx.y;
     const int t0 = blockIdx.x * FPG;
-    const int ng = min(FPG, a.T - t0);
-    const float2* __restrict__ tw = a.twiddle;   // W640^k
-
-    // db_to_amplitude: (10^(0.1 S))^0.5
-    for (int it = lane; it < ng * a.n_mels; it += 64) {
-        const int f = it / a.n_mels, m = it - f * a.n_mels;
-        amp[f][m] = sqrtf(exp10f(0.1f * mel_at(a, u, m, t0 + f)));
-    }
-    __syncthreads();
-    for (int it = lane; it < ng * 321; it += 64) {
-        const int f = it / 321, k = it - f * 321;
-        float2 x = spectrum_bin(a, amp[f], u, k, t0 + f);
-        if (k == 0 || k == 320) x.y = 0.f;            // irfft ignores the DC / Nyquist imaginary parts
-        xb[f][k] = x;
-    }
-    __syncthreads();
-    // fold into Z'[k] = conj(E[k] + i O[k]), k in [0,320):
-    //   E = (X[k] + conj X[320-k]) / 2,  O = (X[k] - conj X[320-k]) W640^{-k} / 2
-    for (int it = lane; it < ng * 320; it += 64) {
-        const int f = it / 320, k = it - f * 320;
-        const float2 xk = xb[f][k], xm = cconj(xb[f][320 - k]);
-        const float2 E = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y + xm.y));
-        const float2 O = cmul(make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y - xm.y)), cconj(tw[k]));
-        const float2 Z = make_float2(E.x - O.y, E.y + O.x);   // E + i O
-        zbuf[f * ZS + k] = cconj(Z);
-    }
-    __syncthreads();
-    // forward 320-point DFT of Z' (step 1: 20-point over n2 of z[n1 + 16 n2], lane = (f, n1))
-    {
-        const int f = lane >> 4, n1 = lane & 15;
-        float2 v[20];
-        const bool act = f < ng;
-        if (act) {
-#pragma unroll
-            for (int n2 = 0; n2 < 20; ++n2) v[n2] = zbuf[f * ZS + n1 + 16 * n2];
-        }
-        __syncthreads();
-        if (act) {
-            dft20(v, tw);
-            float2* zf = zbuf + f * ZS;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int d = 0; d < 5; ++d) {
-                    const int k2 = c + 4 * d;
-                    float2 y = v[5 * c + d];
-                    if (k2) y = cmul(y, tw[(2 * n1 * k2) % 640]);
-                    zf[k2 * 17 + n1] = y;
-                }
-        }
-    }
-    __syncthreads();
-    // step 2: 16-point DFT over n1, lane = (f, k2); write the time samples
-    {
-        const int f = lane / 20, k2 = lane - 20 * (lane / 20);
-        if (f < ng) {
-            float2 v[16];
-            const float2* zf = zbuf + f * ZS;
-#pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) v[n1] = zf[k2 * 17 + n1];
-            dft16(v, tw);
-            float* fr = a.frames + ((u * a.T) + t0 + f) * 640LL;
-            const float s = 1.0f / 320.0f;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const int n = k2 + 20 * (c + 4 * d);       // z[n] = conj(out[n]) / 320
-                    const float2 o = v[4 * c + d];
-                    fr[2 * n] = o.x * s * a.window[2 * n];
-                    fr[2 * n + 1] = -o.y * s * a.window[2 * n + 1];
-                }
-        }
-    }
+    istft640::synth_frames(
+        a, min(FPG, a.T - t0), [&](int m, int f) { return mel_at(a, u, m, t0 + f); },
+        [&](int k, int f) { return a.stft[(u * a.nb + k) * (long long)a.stft_frames + t0 + f]; },
+        [&](int f) { return a.frames + ((u * a.T) + t0 + f) * 640LL; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -729,18 +645,8 @@ __global__ void k_ola(IstftArgs a) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long u = i / L;
         const long long p = i - u * L + N / 2;            // position in the untrimmed signal
-        // frames t with t*hop <= p <= t*hop + N - 1
-        const long long tlo = (p - N + 1 <= 0) ? 0 : (p - N + 1 + a.hop - 1) / a.hop;
-        const long long thi = min((long long)a.T - 1, p / a.hop);
-        float y = 0.f, wss = 0.f;
-        for (long long t = tlo; t <= thi; ++t) {
-            const int o = (int)(p - t * a.hop);
-            y += a.frames[(u * a.T + t) * (long long)N + o];
-            const float w = a.window[o];
-            wss += w * w;
-        }
-        if (wss > 1.17549435e-38f) y /= wss;
-        a.sig[i] = y;
+        a.sig[i] = istft640::ola_sample(p, a.T, N, a.hop, a.window,
+                                        [&](long long t, int o) { return a.frames[(u * a.T + t) * (long long)N + o]; });
     }
 }
 

@@ -29,6 +29,7 @@
 
 #include "avse_common.h"
 #include "fft_common.h"
+#include "frame640.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap
 #define AVSE_WPE4
@@ -41,9 +42,9 @@ AVSE_DEBUG_RECORD(debug_read_stft)
 
 namespace {
 
-constexpr int FPG = 3;          // frames per pass
-constexpr int CHUNK = 21;       // frames per block (7 passes)
-constexpr int ZS = 340;         // float2 slots per frame in LDS (20 rows x 17, padded)
+// the per-frame arithmetic (frame load, DFT steps, untangling, band dots, dB): frame640.h, shared with stream.hip
+using namespace spec640;
+constexpr int CHUNK = 21;       // frames per block (7 passes of FPG)
 
 __device__ __forceinline__ float sample_at(const float* __restrict__ s, long long L, long long i, int pad_mode) {
     if (i < 0) {
@@ -56,14 +57,6 @@ __device__ __forceinline__ float sample_at(const float* __restrict__ s, long lon
     return s[i];
 }
 
-
-__device__ __forceinline__ unsigned int f2ord(float f) {
-    unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 
 __device__ __forceinline__ long long out_index(int spf, int n_slices, int n_mels, int T, long long u, int m, int t) {
     if (spf > 0) {
@@ -89,52 +82,7 @@ __device__ __forceinline__ long long out_index(int spf, int n_slices, int n_mels
 // per CU): 0.224 ms.  PMC (r02, B = 4096): 1,907 VALU instructions per wave (636 per frame), 48 % of wave
 // cycles parked on waitcnt / barrier, 21 % issue-stalled.
 constexpr int WAVES = CHUNK / FPG;     // 7
-constexpr int MW = 24;                 // padded Slaney band width of the LDS table (host-checked)
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// wave-synchronous LDS hand-off: a wave's LDS operations complete in issue order, so draining lgkmcnt (and keeping the
-// compiler from moving memory operations across) is enough when every lane that wrote belongs to the reading wave
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// index of sample i after centre padding: reflect (librosa's 2017 default) or zero (then `keep` is false)
-__device__ __forceinline__ int padded_index(int i, int L, int pad_mode, bool& keep) {
-    keep = pad_mode == 0 || (i >= 0 && i < L);
-    if (pad_mode == 0) {
-        const int j = abs(i);
-        return min(j, 2 * (L - 1) - j);
-    }
-    return min(max(i, 0), L - 1);
-}
-
-// |X| by the hardware v_sqrt_f32 (1 ulp; sqrtf's correctly rounded sequence is ~12 instructions, 16 per lane per
-// chunk, and the magnitudes only feed the mel sums, dB tolerance 1e-3) of the packed square
-__device__ __forceinline__ float pk_abs(v2f x) {
-    const v2f x2 = x * x;
-    return __builtin_amdgcn_sqrtf(x2.x + x2.y);
-}
-
-// Slaney band dot of NQ weight quads against the band's magnitudes (k_spec_seg step 4, k_spec640): loads first,
-// then the FMAs (same summation order as the quad loop it replaced)
-template <int NQ>
-__device__ __forceinline__ float band_dot(const float4* wm, const v2f* mf) {
-    float4 w[NQ];
-    v2f x[2 * NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        w[q] = wm[q];
-        x[2 * q] = mf[2 * q];
-        x[2 * q + 1] = mf[2 * q + 1];
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        acc = fmaf(x[2 * q].x, w[q].x, acc);
-        acc = fmaf(x[2 * q].y, w[q].y, acc);
-        acc = fmaf(x[2 * q + 1].x, w[q].z, acc);
-        acc = fmaf(x[2 * q + 1].y, w[q].w, acc);
-    }
-    return acc;
-}
 // the same over 16-B magnitude quads from a 4-aligned band start (k_spec_seg): ds_read_b128 for weights and magnitudes
 template <int NQ>
 __device__ __forceinline__ float band_dot4(const float4* wm, const float4* mf) {
@@ -153,43 +101,6 @@ __device__ __forceinline__ float band_dot4(const float4* wm, const float4* mf) {
         acc = fmaf(x[q].w, w[q].w, acc);
     }
     return acc;
-}
-
-// real-FFT untangling of the packed 320-point transform Z of one frame (z[n] = x[2n] + i x[2n+1]):
-// packed form: X = X[k], Y = conj X[320 - k] from Z[k], Z[320 - k]; U = -i W640^k / 2 (a float2 table):
-// E = (Zk + conj Zm) / 2, W^k O = U (Zk - conj Zm), X = E + W^k O, Y = E - W^k O
-__device__ __forceinline__ void pk_untangle(const v2f* __restrict__ zf, int k, const v2f* __restrict__ ut, v2f& X, v2f& Y) {
-    const v2f zk = zf[k], zm = zf[k == 0 ? 0 : 320 - k];
-    const v2f S = pk_add_conj(zk, zm);
-    const v2f WO = pk_cmul_t(pk_sub_conj(zk, zm), ut[k]);
-    X = __builtin_elementwise_fma(v2f(0.5f), S, WO);
-    Y = __builtin_elementwise_fma(v2f(0.5f), S, -WO);
-}
-
-// lane (f1, n1) of step 1 loads z[n1 + 16 n2] = (x[s0 + 2(n1 + 16 n2)], x[s0 + 2(n1 + 16 n2) + 1]), n2 < 20
-// RG (ragged batches): an utterance may start at any element of the packed buffer, so a base that is not 8-byte
-// aligned loads the pair as two dwords (the same values)
-template <bool RG = false>
-__device__ __forceinline__ void load_frame(float2 (&x)[20], const float* __restrict__ s, int L, int s0, int n1,
-                                           int pad_mode) {
-    if (RG && s0 >= 0 && s0 + 640 <= L && (reinterpret_cast<uintptr_t>(s) & 7)) {
-        const float* p = s + s0 + 2 * n1;
-#pragma unroll
-        for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(p[32 * n2], p[32 * n2 + 1]);
-    } else if (s0 >= 0 && s0 + 640 <= L) {
-        const float2* p = reinterpret_cast<const float2*>(s + s0) + n1;
-#pragma unroll
-        for (int n2 = 0; n2 < 20; ++n2) x[n2] = p[16 * n2];
-    } else {   // edge frame: branch-free per-sample index arithmetic
-#pragma unroll
-        for (int n2 = 0; n2 < 20; ++n2) {
-            const int i = s0 + 2 * (n1 + 16 * n2);
-            bool k0, k1;
-            const int j0 = padded_index(i, L, pad_mode, k0), j1 = padded_index(i + 1, L, pad_mode, k1);
-            const float v0 = s[j0], v1 = s[j1];
-            x[n2] = make_float2(k0 ? v0 : 0.f, k1 ? v1 : 0.f);
-        }
-    }
 }
 
 // RI: the complex STFT is stored too (bin-major over the whole chunk: block barriers between the steps).  Without it
@@ -279,26 +190,8 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, Sp
 
         // ---- step 1: 20-point DFTs over n2, lane = (f, n1) (packed fp32, fft_common.h pk_*) ----
         v2f v[20];
-#pragma unroll
-        for (int n2 = 0; n2 < 20; ++n2) {
-            const float2 w = winl[n1 + 16 * n2];
-            v[n2] = v2f{x[n2].x, x[n2].y} * v2f{w.x, w.y};
-        }
-        if (f1 < ng) {
-            pk_dft20(v);
-            // v[5c + d] = Y[c + 4d]; twiddle W320^{n1 k2} = W640^{2 n1 k2} (2 n1 k2 <= 570)
-            v2f* zf = reinterpret_cast<v2f*>(zw + f1 * ZS);
-            const v2f* twv = reinterpret_cast<const v2f*>(twl);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int d = 0; d < 5; ++d) {
-                    const int k2 = c + 4 * d;
-                    v2f y = v[5 * c + d];
-                    if (k2) y = pk_cmul_t(y, twv[2 * n1 * k2]);
-                    zf[k2 * 17 + n1] = y;
-                }
-        }
+        window_frame(v, x, winl, n1);
+        if (f1 < ng) dft20_store(v, twl, zw + f1 * ZS, n1);
         if constexpr (RI) lds_barrier(); else wave_lds_sync();
         SPEC_STAMP(1)
         // ---- step 2: 16-point DFTs over n1, lane = (f, k2) ----
@@ -307,19 +200,10 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, Sp
             const bool act = f < ng;
             v2f w[16];
             v2f* zf = reinterpret_cast<v2f*>(zw + min(f, FPG - 1) * ZS);
-            if (act) {
-#pragma unroll
-                for (int n = 0; n < 16; ++n) w[n] = zf[k2 * 17 + n];
-            }
+            if (act) dft16_load(w, zf, k2);
             if constexpr (RI) lds_barrier(); else wave_lds_sync();
             SPEC_STAMP(2)
-            if (act) {
-                pk_dft16(w);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) zf[k2 + 20 * (c + 4 * d)] = w[4 * c + d];
-            }
+            if (act) dft16_store(w, zf, k2);
         }
         SPEC_STAMP(3)
         if constexpr (RI) {
@@ -407,20 +291,13 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec640(SpecArgs a, Sp
             if (FAST_MEL) {
                 const float4* wm = melw4 + m * (MW / 4);
                 const v2f* mf2 = reinterpret_cast<const v2f*>(mf);   // even band starts (host)
-                switch (a.mel_seg_nq[jj]) {   // straight-line loads per quad count (k_spec_seg step 4)
-                    case 1: acc = band_dot<1>(wm, mf2); break;
-                    case 2: acc = band_dot<2>(wm, mf2); break;
-                    case 3: acc = band_dot<3>(wm, mf2); break;
-                    case 4: acc = band_dot<4>(wm, mf2); break;
-                    case 5: acc = band_dot<5>(wm, mf2); break;
-                    default: acc = band_dot<MW / 4>(wm, mf2); break;
-                }
+                acc = band_dot_nq(wm, mf2, a.mel_seg_nq[jj]);
             } else {
                 const float* wm = a.mel_weight + m * mw;
                 const int wdt = mel_wd[m];
                 for (int j = 0; j < wdt; ++j) acc = fmaf(mf[j], wm[j], acc);
             }
-            const float db = acc > a.amin ? 6.0205999132796239f * __log2f(acc) : a.db_floor;
+            const float db = mel_to_db(acc, a.amin, a.db_floor);
             vmax = fmaxf(vmax, db);
             dbuf[m * CHUNK + g + f] = db;
         }
@@ -662,7 +539,7 @@ __global__ __launch_bounds__(64 * WAVES) AVSE_WPE4 void k_spec_seg(SpecArgs a) {
                 case 6: acc = band_dot4<6>(wm, mf); break;
                 default: acc = band_dot4<SEG_MW / 4>(wm, mf); break;
             }
-            db[j] = acc > a.amin ? 6.0205999132796239f * __log2f(acc) : a.db_floor;
+            db[j] = mel_to_db(acc, a.amin, a.db_floor);
             vmax = fmaxf(vmax, db[j]);
         }
         // one block barrier per utterance (the dB maximum): each wave keeps its frames' dB values in registers and

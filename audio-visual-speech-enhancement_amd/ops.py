@@ -755,6 +755,133 @@ def to_device(x, device=None):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
 
 
+def stream_counts(n_samples, n_video_slices, flushed=False, session=None):
+    """avse_stream_counts (host only, no GPU): (frames analysed, slices through the network, samples emitted) of a stream
+    that has received n_samples samples and n_video_slices video slices (flushed: after its flush).  session=None
+    is the 25-fps geometry (n_fft 640, hop 160, 20 frames per slice)."""
+    out = [ctypes.c_int64() for _ in range(3)]
+    _lib.check(_lib.load().avse_stream_counts(session.handle if session is not None else None, int(n_samples),
+                                              int(n_video_slices), int(bool(flushed)), *[ctypes.byref(o) for o in out]),
+               "avse_stream_counts")
+    return tuple(o.value for o in out)
+
+
+class StreamSession:
+    """avse_stream: the device state of n_streams lock-step streams (stream_create); n / v are the host totals."""
+
+    def __init__(self, weights, handle, n_streams, spf, video_dtype, max_slices):
+        self.weights, self.handle = weights, handle      # the weights (and their context) outlive the session
+        self.n_streams, self.spf, self.video_dtype, self.max_slices = n_streams, spf, video_dtype, max_slices
+        self.n = self.v = 0
+        self.flushed = False
+        self._cdll = _lib.load()
+
+    def __del__(self):
+        h, lib = getattr(self, "handle", None), getattr(self, "_cdll", None)
+        if h is not None and h.value and lib is not None:
+            lib.avse_stream_destroy(h)
+            self.handle = None
+
+
+def stream_create(weights, n_streams, sample_rate=16000, n_fft=640, hop_length=160, frames_per_slice=20, n_mels=80,
+                  fmin=0.0, fmax=8000.0, amin=1e-5, top_db=80.0, video_dtype=torch.float32, max_slices=4):
+    """avse_stream_create on the weights' context -> StreamSession.  video_dtype: torch.float32 or torch.uint8, the
+    element type every push's video will have.  Geometries the streaming kernels do not serve (29.97 / 30 fps) raise
+    _lib.AvseError (status 3)."""
+    if not isinstance(weights, DeviceWeights):
+        raise TypeError("weights must be DeviceWeights")
+    if int(n_streams) < 1 or int(max_slices) < 1:
+        raise ValueError("n_streams and max_slices must be positive")
+    if video_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"video_dtype must be torch.float32 or torch.uint8, got {video_dtype}")
+    vdt = _lib.AVSE_VIDEO_U8 if video_dtype == torch.uint8 else _lib.AVSE_VIDEO_F32
+    h = ctypes.c_void_p()
+    with torch.cuda.device(weights.ctx.device_index):
+        _lib.check(_lib.load().avse_stream_create(
+            weights.ctx.handle, weights.handle, int(n_streams), int(sample_rate), int(n_fft), int(hop_length),
+            int(frames_per_slice), int(n_mels), float(fmin), float(fmax), float(amin),
+            float(-1.0 if top_db is None else top_db), vdt, int(max_slices), ctypes.byref(h)), "avse_stream_create")
+    return StreamSession(weights, h, int(n_streams), int(frames_per_slice), vdt, int(max_slices))
+
+
+def _stream_call(sess, flush, samples, video, vnorm_mean, vnorm_std, return_spectrograms):
+    w = sess.weights
+    dev = torch.device("cuda", w.ctx.device_index)
+    B = sess.n_streams
+    n_new = v_new = 0
+    if samples is not None:
+        _dev_f32(samples, "samples")
+        if samples.dim() != 2 or samples.shape[0] != B:
+            raise ValueError(f"samples must be [{B}, n]")
+        n_new = int(samples.shape[1])
+    if video is not None:
+        if _dev_video(video, "video", (128, 128, w.F)) != sess.video_dtype:
+            raise TypeError(f"video is {video.dtype}, the session was created for the other video dtype")
+        if video.dim() != 5 or video.shape[0] != B:
+            raise ValueError(f"video must be [{B}, v, 128, 128, {w.F}]")
+        v_new = int(video.shape[1])
+    if (vnorm_mean is None) != (vnorm_std is None):
+        raise ValueError("vnorm_mean and vnorm_std must both be given")
+    if vnorm_mean is not None:
+        _dev_f32(vnorm_mean, "vnorm_mean", (128, 128))
+        _dev_f32(vnorm_std, "vnorm_std", (128, 128))
+    for t in (samples, video, vnorm_mean, vnorm_std):
+        if t is not None and t.device.index != dev.index:
+            raise ValueError(f"the session lives on {dev} but an argument is on {t.device}")
+    # what the call will emit, from the host totals (the library keeps no getter for them: n / v mirror its counters).
+    # A flush with n > slice * v is refused here by avse_stream_counts, as the library would; a call on a flushed
+    # session emits nothing and is left to the library to refuse.
+    _, k0, e0 = stream_counts(sess.n, sess.v, sess.flushed, sess)
+    k1, e1 = k0, e0
+    if not sess.flushed:
+        _, k1, e1 = stream_counts(sess.n + n_new, sess.v + v_new, flush, sess)
+    n_out, k_new = e1 - e0, k1 - k0
+    out = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+    mel = pred = None
+    if return_spectrograms:
+        mel = torch.empty((B, k_new, 80, sess.spf), dtype=torch.float32, device=dev)
+        pred = torch.empty_like(mel)
+    got = ctypes.c_int64()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if flush:
+            rc = lib.avse_stream_flush(sess.handle, _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), _lib.ptr(out), n_out,
+                                       ctypes.byref(got), _lib.ptr(mel), _lib.ptr(pred), _lib.stream_handle(dev))
+        else:
+            rc = lib.avse_stream_push(sess.handle, _lib.ptr(samples), n_new, n_new, _lib.ptr(video), v_new,
+                                      _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), _lib.ptr(out), n_out, ctypes.byref(got),
+                                      _lib.ptr(mel), _lib.ptr(pred), _lib.stream_handle(dev))
+    _lib.check(rc, "avse_stream_flush" if flush else "avse_stream_push")
+    if got.value != n_out:
+        raise _lib.AvseError(f"the session emitted {got.value} samples, the host totals give {n_out}")
+    sess.n += n_new
+    sess.v += v_new
+    sess.flushed = sess.flushed or flush
+    return (out, mel, pred) if return_spectrograms else out
+
+
+def stream_push(session, samples=None, video=None, vnorm_mean=None, vnorm_std=None, return_spectrograms=False):
+    """avse_stream_push: samples [B, n] float32 (or None), video [B, v, 128, 128, F] in the session's dtype (or None)
+    -> the [B, n_out] samples that became final; with return_spectrograms also the [B, k, 80, spf] slices the network saw
+    and predicted for the k slices this call completed.  Asynchronous on torch's current stream."""
+    return _stream_call(session, False, samples, video, vnorm_mean, vnorm_std, return_spectrograms)
+
+
+def stream_flush(session, vnorm_mean=None, vnorm_std=None, return_spectrograms=False):
+    """avse_stream_flush: closes the streams as the offline call on the zero-padded signal of the video's length and
+    returns the remaining samples (stream_push's return values).  Afterwards only stream_reset is legal."""
+    return _stream_call(session, True, None, None, vnorm_mean, vnorm_std, return_spectrograms)
+
+
+def stream_reset(session):
+    """avse_stream_reset: back to the state after stream_create, ordered on torch's current stream."""
+    dev = torch.device("cuda", session.weights.ctx.device_index)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_stream_reset(session.handle, _lib.stream_handle(dev)), "avse_stream_reset")
+    session.n = session.v = 0
+    session.flushed = False
+
+
 class Trainer:
     """libavse training step (avse_trainer_*, train.hip): one Keras fit step of SpeechEnhancementNetwork.train
     (network.py:177-206) — BatchNormalization on batch statistics, Dropout after each video pooling, MSE, Adam.

@@ -157,3 +157,58 @@ class Enhancer:
             if pipe.recomputed:      # a chunk was redone after the ISTFT had been queued: redo the ISTFT after it
                 out = istft()
         return out
+
+
+class StreamEnhancer:
+    """Enhancement of audio as it arrives: `n_streams` lock-step streams, e.g. the participants of
+    one call, pushed in chunks of any size.
+
+    The reference's predict loop needs the whole utterance (the reflect padding of both ends, the top_db floor from
+    the utterance's maximum, the window sum of the finished signal).  A session carries the sample tail, the running
+    floor, the mixture phase of frames awaiting their prediction and the overlap-add tail between pushes instead;
+    include/avse.h avse_stream_push states what each push computes.  Where the unclamped mel-dB range of a stream stays
+    below top_db the concatenated output is the offline Enhancer's, for all 3200 S - 160 samples.
+
+    Only geometries whose slices do not drift against the samples stream (25 fps at 16 kHz); 29.97 / 30 fps raise
+    _lib.AvseError at construction."""
+
+    def __init__(self, weights, n_streams, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, max_slices=4,
+                 video_dtype=torch.float32):
+        self.weights = weights
+        g = data_processor.frame_geometry(int(sample_rate), slice_duration_ms, 1, float(video_frame_rate))
+        self.geometry = g
+        spf = g["spectrogram_samples_per_slice"]
+        if spf != weights.T:
+            raise ValueError(f"{video_frame_rate} fps gives [80, {spf}] slices; the weights are for [80, {weights.T}]")
+        self.session = ops.stream_create(weights, n_streams, sample_rate=int(sample_rate), n_fft=g["n_fft"],
+                                         hop_length=g["hop_length"], frames_per_slice=spf, n_mels=data_processor.N_MELS,
+                                         fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX,
+                                         video_dtype=video_dtype, max_slices=max_slices)
+
+    def push(self, samples, video=None, vmean=None, vstd=None, return_spectrograms=False):
+        """samples [B, n] float32 (int16-scale), video [B, v, 128, 128, F] float32 or uint8 (the session's dtype) or
+        None -> the [B, n_out] newly final samples; with return_spectrograms also the [B, k, 80, spf] slices the
+        network saw and predicted for the k slices this push completed."""
+        return ops.stream_push(self.session, samples, video, vmean, vstd, return_spectrograms)
+
+    def flush(self, vmean=None, vstd=None, return_spectrograms=False):
+        """Close the streams as the offline call on the signal zero-padded to the video's length; returns the rest."""
+        return ops.stream_flush(self.session, vmean, vstd, return_spectrograms)
+
+    def reset(self):
+        ops.stream_reset(self.session)
+
+    @property
+    def counts(self):
+        """Host totals: dict(samples, video_slices, frames, slices, emitted)."""
+        s = self.session
+        f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
+        return dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+
+    @property
+    def range_bits(self):
+        """float32_split: the range-guard bits the pushes' forwards raised since the last read (waits for the stream;
+        Context.range_status); 0 for the other dtypes."""
+        if self.weights.dtype != _lib.AVSE_F32_SPLIT:
+            return 0
+        return self.weights.ctx.range_status()

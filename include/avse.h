@@ -33,7 +33,8 @@ extern "C" {
  * 3: AVSE_F32_SPLIT range guard (avse_forward_checked, avse_range_status, status AVSE_ERR_RANGE), per-layer activation
  *    exponents (avse_weights_act_exponents, option no_act_scale); later additions under the same version (new symbols
  *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
- *    avse_eval_pairs_sized, avse_eval_pairs_ext */
+ *    avse_eval_pairs_sized, avse_eval_pairs_ext, avse_stream_create, avse_stream_counts, avse_stream_push,
+ *    avse_stream_flush, avse_stream_reset, avse_stream_destroy */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -336,6 +337,88 @@ int avse_forward_profile(avse_ctx* ctx, const avse_weights* w, const float* audi
 int avse_forward_profile_video(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video,
                                int video_dtype, const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
                                void* stream, float* host_ms);
+
+/* ---- streaming enhancement ---------------------------------------------------------------- */
+
+/* A session enhances n_streams lock-step streams (e.g. the participants of one call) as their audio and video arrive.
+ * The calls below replace the per-sample predict path of the reference as it would run incrementally
+ * (speech_enhancer.py:70-85: preprocess_audio_signal, data_processor.py:35-57 -> VideoNormalizer.normalize + Model.predict
+ * -> reconstruct_speech_signal, data_processor.py:60-74, over signal_to_spectrogram / reconstruct_signal_from_spectrogram,
+ * :77-116), which needs the whole utterance: the reflect padding of both ends, the top_db floor from the utterance's
+ * maximum, the window sum of the finished signal.  A session carries the sample tail, the running floor, the mixture
+ * phase of frames awaiting their prediction and the overlap-add tail between calls instead.
+ *
+ * Geometry and dB parameters are avse_spectrogram's / avse_istft's, video_dtype avse_forward_video's; a slice is
+ * frames_per_slice * hop samples, and `weights` must have been loaded for frames_per_slice spectrogram frames
+ * (AVSE_ERR_INVALID otherwise).  A geometry streams when its slices do not drift against the samples: n_fft even and
+ * n_fft == 4 * hop, else AVSE_ERR_UNSUPPORTED (29.97 / 30 fps: n_fft 533, and 24 x 133 = 3192 samples per 3200-sample
+ * slice).  Built: n_fft 640 / hop 160 / 80 bands with a Slaney bank whose bands fit 24 bins (sr 16000, fmin 0, fmax
+ * 8000: the reference's 25-fps geometry), any frames_per_slice the weights have (20 at 25 fps), up to 1024 streams and
+ * max_slices 16; other geometries that pass the condition are AVSE_ERR_UNSUPPORTED too.
+ * max_slices: the most slices one call may complete, and the most either input may run ahead of the other.  All device
+ * state and scratch is sized from n_streams and max_slices here (the forward scratch through
+ * avse_ctx_reserve_weights(ctx, weights, n_streams * max_slices)); create synchronises, a push or a flush allocates
+ * nothing and never synchronises, and the host reads nothing back: the session's counters are functions of the call
+ * arguments alone (avse_stream_counts).  `weights` and `ctx` must outlive the session.
+ * Sessions of one context are independent of each other (each owns its tables and state) and follow the context's
+ * one-stream-at-a-time rule.  With AVSE_F32_SPLIT weights the pushes run the unchecked forward: the range-guard bits
+ * accumulate in the context, and avse_range_status / avse_range_snapshot read them as for avse_forward. */
+typedef struct avse_stream avse_stream;
+int avse_stream_create(avse_ctx* ctx, const avse_weights* weights, int64_t n_streams, int sr, int n_fft, int hop,
+                       int frames_per_slice, int n_mels, float fmin, float fmax, float amin, float top_db,
+                       int video_dtype, int64_t max_slices, avse_stream** out);
+
+/* Host-only: the totals of a stream that has received n_samples samples and n_video_slices video slices (flushed != 0:
+ * after its flush, which needs n_samples <= slice * n_video_slices): frames analysed, slices through the network,
+ * samples emitted.  Any of the three outputs may be NULL.  A NULL session means the 640 / 160 / 20 geometry. */
+int avse_stream_counts(const avse_stream* s, int64_t n_samples, int64_t n_video_slices, int flushed, int64_t* frames,
+                       int64_t* slices, int64_t* emitted);
+
+/* Feeds every stream n_new samples and v_new video slices (either may be 0; both 0 is a no-op) and appends to `out`
+ * the samples that became final.  With N = n_fft, H = hop, spf = frames_per_slice, after n samples and v slices in total:
+ *  - frame t is the offline frame t (window x[H t - N/2, H t + N/2), left reflection x[-i] = x[i]); it is computed as
+ *    soon as every sample it reads has arrived (n >= H t + N/2; n >= N/2 + 1 for t = 0), never again, and its complex
+ *    STFT is kept until its slice has been inverted;
+ *  - slice k is frames [spf k, spf k + spf); it runs through the network once its frames and its video slice are both
+ *    there: k_done = min(frames_done / spf, v);
+ *  - the network sees slice k clamped from below at (the maximum of the unclamped mel-dB of frames 0 .. spf k + spf - 1
+ *    of that stream) - top_db: the causal form of amplitude_to_db's whole-array maximum (data_processor.py:94); amin as
+ *    offline, top_db < 0 disables the clamp.  It depends on nothing after the slice, so not on how the input was cut
+ *    into calls; a stream on which the floor never binds (unclamped range below top_db) gives, in exact arithmetic,
+ *    the offline result;
+ *  - output sample i is final once every frame covering it is inverted; it is y[i] of librosa.istft over the frames so
+ *    far (frames added in increasing order, each sample over the window sum-square of the frames that cover it), so a
+ *    stream has emitted max(0, spf H k_done - N/2) samples: 480 samples (30 ms) of latency beyond the slice.
+ *   samples   [n_streams][n_new] at row stride sample_stride (>= n_new); NULL when n_new == 0
+ *   video     [n_streams][v_new][128][128][F] in the session's video_dtype (4-byte aligned); NULL when v_new == 0
+ *   vnorm_*   nullable, as avse_forward
+ *   out       [n_streams][out_stride]: row b receives *host_n_out new samples of stream b; NULL only when nothing is emitted.
+ *             A push emits at most spf H max_slices samples (3200 max_slices), so an out_stride of that many always serves
+ *   host_n_out  HOST: the samples appended per stream (the same for all)
+ *   mel_db    nullable [n_streams][slices completed by this call][n_mels][spf]: what the network saw
+ *   pred_db   nullable, same shape: what it predicted
+ * Refused with AVSE_ERR_INVALID before any GPU work, the session left exactly as it was: NULL arguments where not
+ * nullable, negative counts, sample_stride < n_new, a call that would complete more than max_slices slices or leave more
+ * than max_slices slices' worth of samples or of video queued ahead of the other input, out_stride below what the call
+ * emits, a push after a flush.  A failure after launches have begun marks the session broken: every later call is
+ * AVSE_ERR_INVALID until avse_stream_reset. */
+int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_t sample_stride, const void* video,
+                     int64_t v_new, const float* vnorm_mean, const float* vnorm_std, float* out, int64_t out_stride,
+                     int64_t* host_n_out, float* mel_db /* nullable */, float* pred_db /* nullable */, void* stream);
+
+/* Closes every stream as the offline call on fit_length(x, slice * v): needs n <= slice * v (AVSE_ERR_INVALID
+ * otherwise); missing samples are zeros, as in preprocess_audio_signal (data_processor.py:39-42), the remaining frames
+ * take the right reflection of that signal, the remaining slices run, and the rest of the slice * v - hop samples is
+ * emitted (frames 0 .. spf v - 1: the offline call drops frame spf v the same way).  Arguments as avse_stream_push.
+ * A flush emits at most spf H max_slices + N/2 - H samples (3200 max_slices + 160: max_slices pending slices plus the
+ * tail the pushes held back), more than any push: size `out` for it.
+ * After a flush only avse_stream_reset is legal. */
+int avse_stream_flush(avse_stream* s, const float* vnorm_mean, const float* vnorm_std, float* out, int64_t out_stride,
+                      int64_t* host_n_out, float* mel_db /* nullable */, float* pred_db /* nullable */, void* stream);
+
+/* Back to the state after create (no samples, no video, not flushed, not broken), ordered on `stream`. */
+int avse_stream_reset(avse_stream* s, void* stream);
+void avse_stream_destroy(avse_stream* s);
 
 /* VideoNormalizer.normalize (data_processor.py:208-212), in place on device (float32 only: uint8 video takes the
  * normaliser fused into the forward, vnorm_mean / vnorm_std):
