@@ -191,22 +191,15 @@ struct ConvArgs {
     float fuse_bias;
     float* fuse_out;
     int out_s16;         // 1: the output in the split pair layout (strides and offset in halves), else T / fp32
-    // AVSE_F32_SPLIT range guard (pair_out_of_range): a stored pair value, or an fp32 input value split on load,
-    // outside the f16 range ORs range_bit / range_in_bit into *range_flag (nullable)
+    // AVSE_F32_SPLIT range guard (mfma_util.h pair_out_of_range): a stored pair value, or an fp32 input value split
+    // on load, outside the f16 range ORs range_bit / range_in_bit into *range_flag (nullable)
     unsigned* range_flag;
     unsigned range_bit, range_in_bit;
     ConvPhase ph[MAX_PHASES];
 };
 
-// AVSE_F32_SPLIT range guard: x cannot be carried as the pair h = f16(x), l = f16(x - h) when h would be infinite
-// (|x| >= 65520, the f16 overflow threshold under round-to-nearest-even) or x is NaN.  Kernels fold the test over the
-// values a lane stores and report once (one vector atomic from the lanes that saw one; the flag word is sticky until
-// avse_range_status / avse_forward_checked read it).
-__device__ __forceinline__ bool pair_out_of_range(float x) { return !(__builtin_fabsf(x) < 65520.f); }
-__device__ __forceinline__ void range_report(unsigned* flag, unsigned bit, bool bad) {
-    if (bad && flag) atomicOr(flag, bit);
-}
-// range flag bits: bit i = layer i of the plan (a_conv1 = 0 .. d_deconv5 = 18), the split network inputs below
+// AVSE_F32_SPLIT range guard (mfma_util.h pair_out_of_range / range_report), the bits of its flag word: bit i = layer i
+// of the plan (a_conv1 = 0 .. d_deconv5 = 18), the split network inputs below
 constexpr unsigned kRangeAudioIn = 1u << 24, kRangeVideoIn = 1u << 25;
 int launch_flag_or(unsigned* flag, unsigned bits, hipStream_t s);
 

@@ -21,21 +21,18 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
 constexpr int BM = 128;
 constexpr int MAX_TAPS_LDS = 64;   // taps of one phase (largest: 25)
-constexpr float LRELU = 0.3f;
 
 template <typename T> struct Vec16;
 template <> struct Vec16<bf16_t> { typedef i32x4 type; };
 template <> struct Vec16<float> { typedef i32x4 type; };
 template <> struct Vec16<_Float16> { typedef i32x4 type; };
-
-__device__ __forceinline__ int swz(int row) { return ((row >> 3) & 1) * 3; }
 
 __device__ __forceinline__ float to_f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ float to_f(float v) { return v; }
@@ -49,10 +46,10 @@ template <> __device__ __forceinline__ float from_f<float>(float v) { return v; 
 template <typename OutT>
 __device__ __forceinline__ bool store_val(const ConvArgs& a, long long rowbase, int n, float x) {
     if (a.out_s16) {
-        _Float16* o = reinterpret_cast<_Float16*>(a.out) + rowbase + 32 * (n >> 4) + (n & 15);
-        const _Float16 h = (_Float16)x;
-        o[0] = h;
-        o[16] = (_Float16)(x - (float)h);
+        _Float16* o = pair_slot(reinterpret_cast<_Float16*>(a.out) + rowbase, n);
+        const SplitPair p = split_pair(x);
+        o[0] = p.h;
+        o[kPairL] = p.l;
         return pair_out_of_range(x);
     }
     reinterpret_cast<OutT*>(a.out)[rowbase + n] = from_f<OutT>(x);
@@ -65,13 +62,8 @@ struct RowInfo {
     bool valid;
 };
 
-// Buffer-resource loads: out-of-range offsets return zeros in hardware, so padding / ragged tiles
-// need no branch around the load (a "load or zero" branch makes hipcc drain vmcnt per load).
-constexpr int kOOB = 0x7fffff00;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, nrec, 0x00020000);
-}
+// Buffer-resource loads (mfma_util.h make_rsrc, kOOB): out-of-range offsets return zeros in hardware, so padding /
+// ragged tiles need no branch around the load (a "load or zero" branch makes hipcc drain vmcnt per load).
 
 // FAST (Ci a multiple of the slab, i.e. every layer but a_conv1): a slab never straddles a tap, so the A row
 // offsets are computed once per tap and a slab's channel offset is the buffer load's scalar soffset; three LDS
@@ -279,8 +271,8 @@ __global__ __launch_bounds__(256, (conv_occupancy<T, BN, FAST, S16>())) void k_c
                 f16x4 hi, lo;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    hi[e] = (_Float16)x[e];
-                    lo[e] = (_Float16)(x[e] - (float)hi[e]);
+                    hi[e] = pair_h(x[e]);
+                    lo[e] = pair_l(x[e], hi[e]);
                     in_bad |= pair_out_of_range(x[e]);
                 }
                 char* rp = AS(buf) + row * 64 + (g & 1) * 8;
@@ -344,13 +336,10 @@ __global__ __launch_bounds__(256, (conv_occupancy<T, BN, FAST, S16>())) void k_c
                 if constexpr (FAST && (KABL & 4)) {
                     part[i][j][0] += __builtin_bit_cast(float, fa[i][0] ^ fb[j][1] ^ fl[j][2]);
                 } else if constexpr (S16) {
-                    part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                        __builtin_bit_cast(f16x8, fa[i]), __builtin_bit_cast(f16x8, fb[j]), part[i][j], 0, 0, 0);
-                    part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                        __builtin_bit_cast(f16x8, fa[i]), __builtin_bit_cast(f16x8, fl[j]), part[i][j], 0, 0, 0);
+                    part[i][j] = mfma_f16(fa[i], fb[j], part[i][j]);
+                    part[i][j] = mfma_f16(fa[i], fl[j], part[i][j]);
                 } else if constexpr (sizeof(T) == 2) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        __builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+                    acc[i][j] = mfma_bf16(fa[i], fb[j], acc[i][j]);
                 } else {
                     const f32x4 av = __builtin_bit_cast(f32x4, fa[i]);
                     const f32x4 bv = __builtin_bit_cast(f32x4, fb[j]);
@@ -451,7 +440,7 @@ __global__ __launch_bounds__(256, (conv_occupancy<T, BN, FAST, S16>())) void k_c
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float x = acc[i][j][r] * esc[j] + esh[j];
-                        if (a.act) x = x >= 0.f ? x : LRELU * x;
+                        if (a.act) x = lrelu_select(x);
                         part[i][r] = fmaf(S16 ? x : to_f(from_f<OutT>(x)), ewf[j], part[i][r]);
                     }
             }
@@ -500,14 +489,14 @@ __global__ __launch_bounds__(256, (conv_occupancy<T, BN, FAST, S16>())) void k_c
             if (a.pool) {
                 if (orow[i][0] < 0) continue;
                 float x = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-                if (a.act) x = x >= 0.f ? x : LRELU * x;
+                if (a.act) x = lrelu_select(x);
                 bad |= store_val<OutT>(a, orow[i][0], n, x);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (orow[i][r] < 0) continue;
                     float x = v[r];
-                    if (a.act) x = x >= 0.f ? x : LRELU * x;
+                    if (a.act) x = lrelu_select(x);
                     bad |= store_val<OutT>(a, orow[i][r], n, x);
                 }
             }
@@ -539,14 +528,14 @@ __global__ void k_splitk_reduce_tiles(ConvArgs a) {
         const float sc = a.scale[n], sh = a.shift[n];
         if (a.pool) {
             float x = fmaxf(fmaxf(acc[0] * sc + sh, acc[1] * sc + sh), fmaxf(acc[2] * sc + sh, acc[3] * sc + sh));
-            if (a.act) x = x >= 0.f ? x : LRELU * x;
+            if (a.act) x = lrelu_select(x);
             const int p = mb >> 2, pw = a.Wq >> 1, phh = a.Hq >> 1;
             const int clip = p / (phh * pw), rr = p - clip * phh * pw;
             bad |= store_val<T>(a, clip * a.out_clip_stride + (long long)rr * a.out_pix_stride + a.out_c_off, n, x);
         } else {
             for (int r = 0; r < 4 && mb + r < M; ++r) {
                 float x = acc[r] * sc + sh;
-                if (a.act) x = x >= 0.f ? x : LRELU * x;
+                if (a.act) x = lrelu_select(x);
                 const int m = mb + r, clip = m / (a.Hq * a.Wq), rr = m - clip * a.Hq * a.Wq;
                 const int oy = (rr / a.Wq) * a.oys, ox = (rr % a.Wq) * a.oxs;
                 bad |= store_val<T>(a, clip * a.out_clip_stride + (long long)(oy * a.Wo + ox) * a.out_pix_stride + a.out_c_off, n, x);
@@ -669,13 +658,12 @@ __global__ __launch_bounds__(256) void k_aconv1_split(AConv1Args a) {
                 const int n = 16 * g + c;
                 float y0 = fmaf(acc[n], ssc[n], ssh[n]);
                 float y1 = fmaf(acc[n + 1], ssc[n + 1], ssh[n + 1]);
-                y0 = y0 >= 0.f ? y0 : 0.3f * y0;
-                y1 = y1 >= 0.f ? y1 : 0.3f * y1;
+                y0 = lrelu_select(y0);
+                y1 = lrelu_select(y1);
                 bad = bad || pair_out_of_range(y0) || pair_out_of_range(y1);
-                const _Float16 h0 = (_Float16)y0, h1 = (_Float16)y1;
-                const _Float16 l0 = (_Float16)(y0 - (float)h0), l1 = (_Float16)(y1 - (float)h1);
-                hw[c / 2] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-                lw[c / 2] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
+                const SplitPair p0 = split_pair(y0), p1 = split_pair(y1);
+                hw[c / 2] = (unsigned)__builtin_bit_cast(unsigned short, p0.h) | ((unsigned)__builtin_bit_cast(unsigned short, p1.h) << 16);
+                lw[c / 2] = (unsigned)__builtin_bit_cast(unsigned short, p0.l) | ((unsigned)__builtin_bit_cast(unsigned short, p1.l) << 16);
             }
             o[4 * g + 0] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
             o[4 * g + 1] = make_uint4(hw[4], hw[5], hw[6], hw[7]);

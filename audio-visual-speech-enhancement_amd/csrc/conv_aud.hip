@@ -22,12 +22,11 @@
 #include <cstdlib>
 #include <utility>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
 constexpr int NW = 8, NT = 64 * NW;
 // a_conv2 input: 2 chunk buffers, 43 rows x 14 pixels x 96 B; pixel (y + ky, x + kx) for output (y, x), tap (ky, kx)
 constexpr int P2 = 14, S2 = 96, W2BUF = 43 * P2 * S2;                 // 57,792
@@ -47,35 +46,13 @@ constexpr int LDS_BYTES = MEL + 83 * MP * 2;                          // 156,432
 constexpr int DA = 6;                                                 // a_conv3..5 weight pieces in flight (registers)
 static_assert(IMG3B <= BOFF && IMG4B <= IMG5 && IMG5 + IMG5B <= BOFF && 400 * 64 <= 32768, "LDS map");
 
-typedef int i32x2 __attribute__((ext_vector_type(2)));
 struct Pre { i32x4 w[DA + 2]; };   // a layer's first DA + 2 weight pieces (see prefetch)
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ int wsw(int row) { return 2 * ((row >> 2) & 1); }
-__device__ __forceinline__ i32x4 lds16(const char* base, int off) { return *reinterpret_cast<const i32x4*>(base + off); }
-template <int... I, typename F>
-__device__ __forceinline__ void unroll(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-__device__ __forceinline__ float bn_lrelu(float acc, float sc, float sh) {
-    const float v = fmaf(acc, sc, sh);
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(LRELU * v));   // LeakyReLU, no canonicalise
-    return r;
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // BN + LeakyReLU of an accumulator quad (4 consecutive channels) -> 4 bf16 (RNE, as (bf16_t) casts)
 __device__ __forceinline__ i32x2 bn_pack4(f32x4 v, f32x4 sc, f32x4 sh) {
-    const float a = bn_lrelu(v[0], sc[0], sh[0]), b = bn_lrelu(v[1], sc[1], sh[1]);
-    const float c = bn_lrelu(v[2], sc[2], sh[2]), d = bn_lrelu(v[3], sc[3], sh[3]);
-    const bf16x2 lo = __builtin_convertvector((f32x2){a, b}, bf16x2), hi = __builtin_convertvector((f32x2){c, d}, bf16x2);
-    return (i32x2){__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi)};
-}
-__device__ __forceinline__ f32x4 mfma(i32x4 a, i32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    const float a = bn_lrelu_vmax(v[0], sc[0], sh[0]), b = bn_lrelu_vmax(v[1], sc[1], sh[1]);
+    const float c = bn_lrelu_vmax(v[2], sc[2], sh[2]), d = bn_lrelu_vmax(v[3], sc[3], sh[3]);
+    return pack4_bf16(a, b, c, d);
 }
 
 // STAMP (tools/aud_stamp.hip only; 0 in the library): thread 0 records s_memtime at the phase boundaries into
@@ -92,7 +69,7 @@ __global__ __launch_bounds__(NT, 1) void k_aud_enc(AudEncArgs a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, kg = lane >> 4;
     const int clip = blockIdx.x;
-    auto st16 = [&](int addr, i32x4 v) { *reinterpret_cast<i32x4*>(lds + addr) = v; };
+    auto st16 = [&](int addr, i32x4 v) { avse::st16(lds + addr, v); };
     auto zero = [&](int from, int to) {
         for (int o = from + tid * 16; o < to; o += NT * 16) st16(o, (i32x4){0, 0, 0, 0});
     };
@@ -152,7 +129,7 @@ __global__ __launch_bounds__(NT, 1) void k_aud_enc(AudEncArgs a) {
             const i32x4 fa = {(int)(v[0] | (v[1] << 16)), (int)(v[2] | (v[3] << 16)), (int)(v[4] | (v[5] << 16)),
                               (int)(v[6] | (v[7] << 16))};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma(fb1[j], fa, (f32x4){0.f, 0.f, 0.f, 0.f});   // W x A
+            for (int j = 0; j < 4; ++j) acc[i][j] = mfma_bf16(fb1[j], fa, (f32x4){0.f, 0.f, 0.f, 0.f});   // W x A
         }
         // -> a_conv2's input: chunk (n / 32) buffer, padded pixel (oy + 1, ox + 1); lane = pixel row r16,
         // channels 16 j + 4 kg .. + 3 (scale / shift quads read once per j: the stores in between are LDS stores,
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(NT, 1) void k_aud_enc(AudEncArgs a) {
             read_a(std::integral_constant<int, S + RA - 1>{});
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < NFR; ++i) acc[i] = mfma(fb, fa[S % RA][i], S == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i]);
+            for (int i = 0; i < NFR; ++i) acc[i] = mfma_bf16(fb, fa[S % RA][i], S == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i]);
         });
     };
     Pre pre3{}, pre4{}, pre5{};
@@ -227,8 +204,8 @@ __global__ __launch_bounds__(NT, 1) void k_aud_enc(AudEncArgs a) {
     {
         // weight slabs (64 rows x 64 B = 4 KB) through the ring in groups of 4: lane moves 8 B per slab
         const int brow = tid >> 3, kq = (tid >> 1) & 3, kh = tid & 1;
-        const int bst = BOFF + brow * 64 + ((kq ^ wsw(brow)) << 4) + kh * 8;   // + slot 16384 + pos 4096
-        const int bfr = BOFF + r16 * 64 + ((kg ^ wsw(r16)) << 4);              // + slot 16384 + pos 4096 + 1024 j
+        const int bst = slab_row_addr(brow, kq, BOFF) + kh * 8;   // + slot 16384 + pos 4096
+        const int bfr = slab_slot_addr(r16, kg ^ wsw(r16), BOFF);   // + slot 16384 + pos 4096 + 1024 j
         const __amdgpu_buffer_rsrc_t rsW = make_rsrc(a.w2, 64 * 1024 * 2);
         const int vbl = brow * 2048 + kq * 16 + kh * 8;
         auto bpiece = [&](auto tt, int csoff) {   // slab (chunk, tap t): k = t * 64 + chunk * 32
@@ -300,8 +277,8 @@ __global__ __launch_bounds__(NT, 1) void k_aud_enc(AudEncArgs a) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = mfma(fb[t & 1][j], fa[t & 1][i], acc[i][j]);   // W x A
-                if (xw) acc[3][0] = mfma(fbx[t & 1], fa[t & 1][3], acc[3][0]);
+                    for (int j = 0; j < 4; ++j) acc[i][j] = mfma_bf16(fb[t & 1][j], fa[t & 1][i], acc[i][j]);   // W x A
+                if (xw) acc[3][0] = mfma_bf16(fbx[t & 1], fa[t & 1][3], acc[3][0]);
             });
         }
         __syncthreads();   // every read of a_conv2's input done: a_conv3's image goes over it

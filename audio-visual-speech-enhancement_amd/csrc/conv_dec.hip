@@ -38,13 +38,11 @@
 #include <cstdlib>
 #include <utility>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
-constexpr int kOOB = 0x7fffff00;
 constexpr int H = 40, W = 10, HW = H * W;           // d_deconv4 / d_deconv5 phase grid
 constexpr int CI4 = 128, CO = 64;                    // d_deconv4 128 -> 64, d_deconv5 64 -> 64
 constexpr int NW = 8, NT = 64 * NW;                  // waves (two per SIMD), threads
@@ -72,30 +70,6 @@ constexpr int ph_woff(int p) { int s = 0; for (int q = 0; q < p; ++q) s += CO * 
 constexpr int ph_pstart(int p) { int s = 0; for (int q = 0; q < p; ++q) s += (2 * ph_nt(q) + 3) / 4 * 4; return s; }  // padded
 constexpr int ph_ofp(int g) { int p = 0; while (p < 3 && g >= ph_pstart(p + 1)) ++p; return p; }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-__device__ __forceinline__ int wsw(int row) { return 2 * ((row >> 2) & 1); }   // weight-slab slot swizzle
-__device__ __forceinline__ i32x4 lds16(const char* base, int off) { return *reinterpret_cast<const i32x4*>(base + off); }
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float bn_lrelu(float acc, float sc, float sh) {
-    const float v = fmaf(acc, sc, sh);
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(LRELU * v));   // LeakyReLU, no canonicalise
-    return r;
-}
-__device__ __forceinline__ auto pack4(float a, float b, float c, float d) {   // 4 bf16 (RNE, as (bf16_t) casts)
-    typedef int i32x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 lo = __builtin_convertvector((f32x2){a, b}, bf16x2), hi = __builtin_convertvector((f32x2){c, d}, bf16x2);
-    return (i32x2){__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi)};
-}
-template <int... I, typename F>
-__device__ __forceinline__ void unroll(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-
 __global__ __launch_bounds__(NT, 1) void k_dec_tail(DecTailArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
 
@@ -118,15 +92,15 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail(DecTailArgs a) {
     // tid >> 2; slab S sits in group S / 4, slot (S / 4) & 1, position S % 4; B fragment j of lane (r16, kg) =
     // row 16 j + r16, k-group kg (16-B slots XOR-swizzled by wsw(row): conflict-free) ----
     const int brow = tid >> 3, kq = (tid >> 1) & 3, kh = tid & 1;   // 8 B per lane: half kh of 16-B group kq
-    const int bst = BOFF + brow * 64 + ((kq ^ wsw(brow)) << 4) + kh * 8;   // + slot * 16384 + pos * 4096
-    const int bfr = BOFF + r16 * 64 + ((kg ^ wsw(r16)) << 4);        // + slot * 16384 + pos * 4096 + 1024 j
+    const int bst = slab_row_addr(brow, kq, BOFF) + kh * 8;         // + slot * 16384 + pos * 4096
+    const int bfr = slab_slot_addr(r16, kg ^ wsw(r16), BOFF);   // + slot * 16384 + pos * 4096 + 1024 j
     const bool xw = w < 4;   // this wave computes slot 3 (fragment 24 x channel block w)
     auto read_b = [&](int base, i32x4 (&f)[4], i32x4& fx) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) f[j] = lds16(lds, base + 1024 * j);
         if (xw) fx = lds16(lds, base + 1024 * w);
     };
-    auto st16 = [&](int addr, i32x4 v) { *reinterpret_cast<i32x4*>(lds + addr) = v; };
+    auto st16 = [&](int addr, i32x4 v) { avse::st16(lds + addr, v); };
     typedef int i32x2 __attribute__((ext_vector_type(2)));
     auto st8 = [&](int addr, i32x2 v) { *reinterpret_cast<i32x2*>(lds + addr) = v; };
 
@@ -142,11 +116,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail(DecTailArgs a) {
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[j]),   // W x A
-                                                                     __builtin_bit_cast(bf16x8, fa[i]), acc[i][j], 0, 0, 0);
-        if (xw)
-            acc[3][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fbx), __builtin_bit_cast(bf16x8, fa[3]),
-                                                                acc[3][0], 0, 0, 0);
+                acc[i][j] = mfma_bf16(fb[j], fa[i], acc[i][j]);   // W x A
+        if (xw) acc[3][0] = mfma_bf16(fbx, fa[3], acc[3][0]);
     };
 
     // =============================== d_deconv4 ===============================
@@ -262,8 +233,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail(DecTailArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { sc4q[j] = par4(PSC4, j); sh4q[j] = par4(PSH4, j); }
         auto st_quad = [&](int px, int j, const f32x4& v, const f32x4& sc, const f32x4& sh) {   // channels 16 j + 4 kg + e
-            st8(px + 32 * j, pack4(bn_lrelu(v[0], sc[0], sh[0]), bn_lrelu(v[1], sc[1], sh[1]),
-                                   bn_lrelu(v[2], sc[2], sh[2]), bn_lrelu(v[3], sc[3], sh[3])));
+            st8(px + 32 * j, pack4_bf16(bn_lrelu_vmax(v[0], sc[0], sh[0]), bn_lrelu_vmax(v[1], sc[1], sh[1]),
+                                        bn_lrelu_vmax(v[2], sc[2], sh[2]), bn_lrelu_vmax(v[3], sc[3], sh[3])));
         };
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
@@ -317,13 +288,13 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail(DecTailArgs a) {
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)   // y rounded to bf16 as the unfused path stores it
-                    part[i] = fmaf((float)(bf16_t)bn_lrelu(acc[i][j][e], sc[e], sh[e]), w6[e], part[i]);
+                    part[i] = fmaf((float)(bf16_t)bn_lrelu_vmax(acc[i][j][e], sc[e], sh[e]), w6[e], part[i]);
         }
         if (xw) {   // slot 3: fragment 24, channels 16 w + 4 kg + e
             const f32x4 sc = par5(PSC5, w), sh = par5(PSH5, w), w6 = par5(PW6, w);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                part[3] = fmaf((float)(bf16_t)bn_lrelu(acc[3][0][e], sc[e], sh[e]), w6[e], part[3]);
+                part[3] = fmaf((float)(bf16_t)bn_lrelu_vmax(acc[3][0][e], sc[e], sh[e]), w6[e], part[3]);
         }
         // sum over the four lane rows (kg) of a slot, three swaps for four slots: lanes 0-31 <-> 32-63 pairs slots
         // (0, 1) and (2, 3), then rows 0 / 2 <-> 1 / 3: lane row kg ends with the total of slot {0, 2, 1, 3}[kg]

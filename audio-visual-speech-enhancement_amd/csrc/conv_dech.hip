@@ -23,12 +23,11 @@
 #include <cstdlib>
 #include <utility>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
 constexpr int NW = 8, NT = 64 * NW;
 constexpr int NC = 2;                                        // clips per workgroup
 constexpr int S = 288;                                       // image pixel stride (128 bf16 channels + 32 B)
@@ -48,33 +47,7 @@ __device__ __forceinline__ int border_px(int i) {
     return i < 7 ? i : i < 13 ? ((i - 7) / 2 + 1) * P3 + ((i - 7) & 1) * 6 : 4 * P3;
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
 struct Pre { i32x4 w[DA + 2]; };   // a layer's first DA + 2 weight pieces
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ int wsw(int row) { return 2 * ((row >> 2) & 1); }
-__device__ __forceinline__ i32x4 lds16(const char* base, int off) { return *reinterpret_cast<const i32x4*>(base + off); }
-template <int... I, typename F>
-__device__ __forceinline__ void unroll(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-__device__ __forceinline__ f32x4 mfma(i32x4 a, i32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float bn_lrelu(float acc, float sc, float sh) {
-    const float v = fmaf(acc, sc, sh);
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(LRELU * v));   // LeakyReLU, no canonicalise
-    return r;
-}
-__device__ __forceinline__ i32x2 pack4(float a, float b, float c, float d) {   // 4 bf16 (RNE, as (bf16_t) casts)
-    const bf16x2 lo = __builtin_convertvector((f32x2){a, b}, bf16x2), hi = __builtin_convertvector((f32x2){c, d}, bf16x2);
-    return (i32x2){__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi)};
-}
 
 // Layer geometry.  L = 1, 2: phases py in {0, 1} (px = 0), taps b in {0, 1}: input (yq, xq - b); grid HQ x 5.
 // L = 3: phases (py, px), taps (a, b) in {0, 1}^2: input (yq + py - a, xq + px - b); grid 20 x 5.
@@ -107,11 +80,11 @@ __global__ __launch_bounds__(NT, 1) void k_dec_head(DecHeadArgs a) {
     const int r16 = lane & 15, kg = lane >> 4;
     const int clip0 = NC * blockIdx.x;
     const int mh = w >> 2, nq = w & 3;   // d_deconv3's wave split: clip mh, channels 32 nq .. + 31
-    auto st16 = [&](int addr, i32x4 v) { *reinterpret_cast<i32x4*>(lds + addr) = v; };
+    auto st16 = [&](int addr, i32x4 v) { avse::st16(lds + addr, v); };
 
     // ---- weight ring: lane tid moves 16 B (kq = tid & 3) of row tid >> 2 of an 8-KB slab ----
     const int brow = tid >> 2, kq = tid & 3;
-    const int bst = BOFF + brow * 64 + ((kq ^ wsw(brow)) << 4);   // + slot 16384 + pos 8192
+    const int bst = slab_row_addr(brow, kq, BOFF);   // + slot 16384 + pos 8192
     const __amdgpu_buffer_rsrc_t rsW1 = make_rsrc(a.w1, 2 * 128 * 256 * 2), rsW2 = make_rsrc(a.w2, 2 * 128 * 256 * 2),
                                  rsW3 = make_rsrc(a.w3, 4 * 128 * 512 * 2);
     // ring piece of slab s of layer L (phase s / NSL, slab within phase s % NSL): k = tap * 128 + chunk * 32
@@ -197,8 +170,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_head(DecHeadArgs a) {
             if constexpr (!DIRECT)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                fb[buf][j] = lds16(lds, BOFF + (((s / 2) & 1) * 16384 + (s % 2) * 8192) + (row0 + 16 * j + r16) * 64 +
-                                            ((kg ^ wsw(r16)) << 4));
+                fb[buf][j] = lds16(lds, slab_row_addr(row0 + 16 * j + r16, kg,
+                                                      BOFF + (((s / 2) & 1) * 16384 + (s % 2) * 8192)));
         };
         constexpr int NS = G::NP * G::NSL;
         // register ring: pb[s % DA] holds slab s + 2 at step s (LDS ring); pd[s % (DA + 2)] holds slab s (DIRECT)
@@ -236,7 +209,7 @@ __global__ __launch_bounds__(NT, 1) void k_dec_head(DecHeadArgs a) {
             for (int i = 0; i < NI; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
-                    if constexpr (!(ABL & 1)) acc[i][j] = mfma(DIRECT ? fbd : fb[s & 1][j], fa[s & 1][i], acc[i][j]);   // W x A
+                    if constexpr (!(ABL & 1)) acc[i][j] = mfma_bf16(DIRECT ? fbd : fb[s & 1][j], fa[s & 1][i], acc[i][j]);   // W x A
                     else acc[i][j][0] += __builtin_bit_cast(float, fa[s & 1][i][0] ^ fb[s & 1][j][0]);
             if constexpr (last) {
                 if constexpr (p + 1 == G::NP) {   // layer done: the next layer's first slabs load under this epilogue
@@ -256,8 +229,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_head(DecHeadArgs a) {
                     for (int j = 0; j < NJ; ++j) {
                         const f32x4 v = acc[i][j];
                         store(c, 2 * yq + py, (LL == 3 ? 2 : 1) * xq + px, row0 + 16 * j + 4 * kg,
-                              pack4(bn_lrelu(v[0], sc[j][0], sh[j][0]), bn_lrelu(v[1], sc[j][1], sh[j][1]),
-                                    bn_lrelu(v[2], sc[j][2], sh[j][2]), bn_lrelu(v[3], sc[j][3], sh[j][3])));
+                              pack4_bf16(bn_lrelu_vmax(v[0], sc[j][0], sh[j][0]), bn_lrelu_vmax(v[1], sc[j][1], sh[j][1]),
+                                         bn_lrelu_vmax(v[2], sc[j][2], sh[j][2]), bn_lrelu_vmax(v[3], sc[j][3], sh[j][3])));
                     }
                 }
                 if constexpr (p + 1 < G::NP) {

@@ -40,7 +40,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
@@ -54,8 +54,6 @@ namespace {
 #define AVSE_DECTS_ABL 0
 #endif
 constexpr int DABL = AVSE_DECTS_ABL;
-constexpr float LRELU = 0.3f;
-constexpr int kOOB = 0x7fffff00;
 constexpr int H = 40, W = 10;                        // d_deconv4 / d_deconv5 grid of a clip
 constexpr int CI4 = 128, CO = 64;                    // d_deconv4 128 -> 64, d_deconv5 64 -> 64 (real channels)
 constexpr int NW = 8, NT = 64 * NW;
@@ -86,31 +84,9 @@ constexpr int ph_of(int g) { int p = 0; while (p < 3 && g >= ph_gstart(p + 1)) +
 static_assert(ph_gstart(4) % 4 == 0 && (4 * ph_nt(0)) % 4 == 0, "every phase is whole ring groups");
 static_assert(ph_gstart(1) % 2 == 0 && ph_gstart(2) % 2 == 0 && ph_gstart(3) % 2 == 0, "every phase is whole slab pairs");
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-__device__ __forceinline__ int wsw(int row) { return 2 * ((row >> 2) & 1); }   // weight-slab slot swizzle (k_conv's)
-__device__ __forceinline__ i32x4 lds16(const char* base, int off) { return *reinterpret_cast<const i32x4*>(base + off); }
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float bn_lrelu(float acc, float sc, float sh) {
-    const float v = fmaf(acc, sc, sh);
-    return fmaxf(v, LRELU * v);
-}
-// LDS stores of this wave drained, then the workgroup barrier (global loads stay in flight across it)
-__device__ __forceinline__ void lds_barrier_raw() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-}
-__device__ __forceinline__ void lds_barrier() { lds_barrier_raw(); }
 __device__ __forceinline__ void loop_barrier() {
-    if constexpr (!(DABL & 4)) lds_barrier_raw();
+    if constexpr (!(DABL & 4)) lds_barrier_split();
 }
-template <int... I, typename F>
-__device__ __forceinline__ void unroll(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-
 template <bool PR>
 __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
@@ -124,12 +100,12 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 
     // weight slabs through the LDS ring: lane tid moves 8 B (half kh of 16-B group kq) of row tid >> 3
     const int brow = tid >> 3, kq = (tid >> 1) & 3, kh = tid & 1;
-    const int bst = BOFF + brow * 64 + ((kq ^ wsw(brow)) << 4) + kh * 8;           // + slot * 16384 + pos * 4096
+    const int bst = slab_row_addr(brow, kq, BOFF) + kh * 8;   // + slot * 16384 + pos * 4096
     // this wave's Wh / Wl fragments: row 16 cb + r16, 16-B group (kg & 1) / 2 + (kg & 1) (PR: k-groups 2, 3 from the
     // pair's second slab)
     const int brd = 16 * cb + r16, bps = PR ? (kg >> 1) * 4096 : 0;
-    const int bfh = BOFF + bps + brd * 64 + (((kg & 1) ^ wsw(brd)) << 4);
-    const int bfl = BOFF + bps + brd * 64 + (((2 + (kg & 1)) ^ wsw(brd)) << 4);
+    const int bfh = slab_row_addr(brd, kg & 1, BOFF + bps);
+    const int bfl = slab_row_addr(brd, 2 + (kg & 1), BOFF + bps);
     auto st8 = [&](int addr, i32x2 v) { *reinterpret_cast<i32x2*>(lds + addr) = v; };
     auto read_w = [&](int off, i32x4 (&f)[2]) {
         f[0] = lds16(lds, bfh + off);
@@ -159,10 +135,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             if (i == SL - 1 && !slot6) continue;
-            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[0]), __builtin_bit_cast(f16x8, fa[i]),
-                                                             part[i], 0, 0, 0);
-            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[1]), __builtin_bit_cast(f16x8, fa[i]),
-                                                             part[i], 0, 0, 0);
+            part[i] = mfma_f16(fw[0], fa[i], part[i]);
+            part[i] = mfma_f16(fw[1], fa[i], part[i]);
         }
     };
 
@@ -178,8 +152,7 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             if (i == SL - 1 && !slot6) continue;
-            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[0]), __builtin_bit_cast(f16x8, fl[i]),
-                                                             part[i], 0, 0, 0);
+            part[i] = mfma_f16(fw[0], fl[i], part[i]);
         }
     };
     auto mfma_h = [&](const i32x4 (&fa)[SL], const i32x4 (&fw)[2], bool slot6) {
@@ -192,10 +165,8 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             if (i == SL - 1 && !slot6) continue;
-            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[0]), __builtin_bit_cast(f16x8, fa[i]),
-                                                             part[i], 0, 0, 0);
-            part[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[1]), __builtin_bit_cast(f16x8, fa[i]),
-                                                             part[i], 0, 0, 0);
+            part[i] = mfma_f16(fw[0], fa[i], part[i]);
+            part[i] = mfma_f16(fw[1], fa[i], part[i]);
         }
     };
 
@@ -264,7 +235,7 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
             for (int t = 0; t < 4; ++t) st8(bst + t * 4096, w0[t]);
         }
         zero_all();
-        lds_barrier();
+        lds_barrier_split();
 
         i32x4 fa[2][SL], fl[SL], fw[2][2];
         // next chunk's window pieces: loaded at tap k < NPC, stored at tap k + 12, before the chunk's last barrier
@@ -360,7 +331,7 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
                 if constexpr (t % 8 == 7) flush();
             });
         }
-        lds_barrier();   // every window read done: the d_deconv5 image goes over the windows
+        lds_barrier_split();   // every window read done: the d_deconv5 image goes over the windows
 
         // image border: the zero row (h = 0: image row 0 = d_deconv4 row -1; h = 1: row 21 = row 40) and columns 0, 11
         // of rows 0..21 (256 data bytes per pixel = 16 pieces)
@@ -387,15 +358,15 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
             f16x4 hv, lv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float y = bn_lrelu(acc[i][e], sc[e], sh[e]);
+                const float y = bn_lrelu_fmax(acc[i][e], sc[e], sh[e]);
                 range_bad |= pair_out_of_range(y);
-                hv[e] = (_Float16)y;
-                lv[e] = (_Float16)(y - (float)hv[e]);
+                hv[e] = pair_h(y);
+                lv[e] = pair_l(y, hv[e]);
             }
             *reinterpret_cast<f16x4*>(lds + px) = hv;
             *reinterpret_cast<f16x4*>(lds + px + 32) = lv;
         }
-        lds_barrier();
+        lds_barrier_split();
     }
     range_report(a.range_flag, a.range_bit, range_bad);
 
@@ -456,13 +427,13 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
             if (i == SL - 1 && !s6) continue;
             float d = 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) d = fmaf(bn_lrelu(acc[i][e], sc[e], sh[e]), w6[e], d);
+            for (int e = 0; e < 4; ++e) d = fmaf(bn_lrelu_fmax(acc[i][e], sc[e], sh[e]), w6[e], d);
             d += __shfl_xor(d, 16);
             d += __shfl_xor(d, 32);
             const int q = 16 * (fr0 + i) + r16;
             if (kg == 0 && q < H / 2 * W) xp[cb * (16 * F5) + q] = d;   // this block's 16-channel share
         }
-        lds_barrier();
+        lds_barrier_split();
         if (tid < H / 2 * W) {   // the four channel blocks in a fixed order, + bias
             const int q = tid, yl = q / W, x = q - yl * W;
             const float v = ((xp[q] + xp[16 * F5 + q]) + xp[32 * F5 + q]) + xp[48 * F5 + q];
@@ -484,7 +455,7 @@ __global__ __launch_bounds__(NT, 1) void k_dec_tail_s16(DecTailArgs a) {
         for (int t = 0; t < 4; ++t) st8(bst + t * 4096, w0[t]);
     }
     zero_all();
-    lds_barrier();
+    lds_barrier_split();
     i32x4 fa[2][SL], fl[SL], fw[2][2];
     read_a5(std::integral_constant<int, 0>{}, fa[0]);   // PR: vb5 makes this the pair's h halves
     if constexpr (PR) read_a5p(std::integral_constant<int, 0>{}, kL, fl);

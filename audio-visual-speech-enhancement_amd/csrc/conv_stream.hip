@@ -41,27 +41,18 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
-constexpr int kOOB = 0x7fffff00;   // buffer offset that reads as zero (past every resource we build)
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// 16-B slot swizzles of the LDS images (found by exhaustive search over the ds_read_b128 lane groups of
-// the v_mfma_f32_32x32x16_bf16 operand layout, every tap offset and all three tile geometries)
-// M16 = the v_mfma_f32_16x16x32_bf16 operand layout (lane l: row l & 15, 16-B k-group l >> 4), 4x4-pixel
-// fragment blocks: found by the same search (tools/lds_swizzle_search.py)
-template <bool M16> __device__ __forceinline__ int wswz(int row) { return M16 ? 2 * ((row >> 2) & 1) : (row >> 2) & 3; }
+// 16-B slot swizzle of the halo images, the weight images' wswz<M16> (mfma_util.h) beside it: found by exhaustive
+// search over the ds_read_b128 lane groups of the v_mfma_f32_32x32x16_bf16 operand layout, every tap offset and all
+// three tile geometries; M16 = the v_mfma_f32_16x16x32_bf16 operand layout (lane l: row l & 15, 16-B k-group l >> 4),
+// 4x4-pixel fragment blocks: found by the same search (tools/lds_swizzle_search.py)
 template <bool M16> __device__ __forceinline__ int hsw(int y) { return M16 ? 2 * (y & 1) : y & 3; }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
 
 // cache-policy bits of the loaders' global loads (gfx950 buffer aux: 1 = sc0, 2 = nt, 16 = sc1), A/B switches
 #ifndef AVSE_HALO_AUX
@@ -76,16 +67,6 @@ __device__ __forceinline__ i32x4 ld16(__amdgpu_buffer_rsrc_t rs, int voff, int s
 __device__ __forceinline__ i32x4 ld16w(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {  // weight slices
     return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, AVSE_WGT_AUX);
 }
-__device__ __forceinline__ void st16(char* p, i32x4 v) { *reinterpret_cast<i32x4*>(p) = v; }
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) and a bare s_barrier, as asm with a memory clobber: the compiler may
-// not move LDS accesses across them, and adds no vmcnt(0) drain of the loads meant to stay in flight
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void barrier_raw() { asm volatile("s_barrier" ::: "memory"); }
 
 // LAT (load -> LDS store distance, steps): 10 for 5x5, 6 for 3x3; it divides the unrolled chunk pair
 // (2 KS^2 steps).  Measured on v_conv2 (runtime-tap loader): LAT 4 / 5 / 10 / 20 = 1.14 / 1.04-1.13 / 1.00 /
@@ -469,7 +450,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
         // output element (pooled pixel p, channel co): OUT_BF16 / OUT_F32 at p * out_pix_stride + out_c_off + co;
         // OUT_S16 (the next stream layer's split input, out_pix_stride = 2 Co) h at p * out_pix_stride + out_c_off +
         // 32 (co / 16) + co % 16 and l 16 halves further
-        bool range_bad = false;   // OUT_S16: range guard over all tiles (avse_common.h pair_out_of_range), reported once
+        bool range_bad = false;   // OUT_S16: range guard over all tiles (mfma_util.h pair_out_of_range), reported once
         auto epilogue_m = [&](auto modec, int clip0, int oy0, int ox0) {
             constexpr int OM = decltype(modec)::value;
             constexpr int ES = OM == OUT_F32 ? 4 : 2;
@@ -486,17 +467,16 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                 for (int j = 0; j < 8; ++j) {
                     const float mx = fmaxf(fmaxf(acc[i][j][0], acc[i][j][1]), fmaxf(acc[i][j][2], acc[i][j][3]));
                     float x = fmaf(mx, ssh[16 * j + r16], ssh[128 + 16 * j + r16]);
-                    x = fmaxf(x, LRELU * x);
+                    x = lrelu_fmax(x);
                     if constexpr (OM == OUT_BF16) {
                         __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (bf16_t)x), ors,
                                                               (pbase + 16 * j) * 2, 0, 0);
                     } else if constexpr (OM == OUT_S16) {
-                        const _Float16 h = (_Float16)x;
-                        const _Float16 l = (_Float16)(x - (float)h);
+                        const SplitPair p = split_pair(x);
                         range_bad |= pair_out_of_range(x);
-                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h), ors,
+                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.h), ors,
                                                               (pbase + 32 * j) * 2, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, l), ors,
+                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.l), ors,
                                                               (pbase + 32 * j + 16) * 2, 0, 0);
                     } else {
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, x), ors, (pbase + 16 * j) * 4, 0, 0);
@@ -579,7 +559,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
             frags(0, 0, 0, fa, fb);
             if constexpr ((ABL & 8) != 0) frags(0, 0, 0, na, nb);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // slice 0 read: the loaders may now overwrite weight slot 0
 
         // bar: the step closes a BP-step group (t % BP == BP - 1; t is even on the first call of each pair)
@@ -591,8 +571,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                                __builtin_bit_cast(bf16x8, ca[i]), __builtin_bit_cast(bf16x8, cb[j]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = mfma_bf16(ca[i], cb[j], acc[i][j]);
             }
             // the next slice's 12 fragment reads one per MFMA from the start of the step (measured against two
             // MFMAs per read over 24 MFMAs, 3:2, 1:2 and all reads first: -1 to -2 % on v_conv2 / v_conv4, the
@@ -610,7 +589,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
             }
             if constexpr (!(ABL & 4) && decltype(bar)::value) {
                 if constexpr ((ABL & 128) != 0) pt0 = __builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wave_lds_sync();
                 if constexpr ((ABL & 128) != 0) pt1 = __builtin_amdgcn_s_memtime();
                 barrier_raw();
                 if constexpr ((ABL & 128) != 0) {
@@ -635,8 +614,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                     for (int j = 0; j < 8; ++j)
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                                __builtin_bit_cast(f16x8, ca[i]), __builtin_bit_cast(f16x8, cb[j]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = mfma_f16(ca[i], cb[j], acc[i][j]);
             };
             auto sched = [](auto nds, auto per) {
                 constexpr int ND = decltype(nds)::value, PER = decltype(per)::value;
@@ -673,7 +651,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                 sched(std::integral_constant<int, 12>{}, std::integral_constant<int, 1>{});
                 if constexpr (!(ABL & 4) && decltype(bar)::value) {
                     if constexpr ((ABL & 128) != 0) pt0 = __builtin_amdgcn_s_memtime();
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    wave_lds_sync();
                     if constexpr ((ABL & 128) != 0) pt1 = __builtin_amdgcn_s_memtime();
                     barrier_raw();
                     if constexpr ((ABL & 128) != 0) {
@@ -706,7 +684,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                 sched(std::integral_constant<int, 12>{}, std::integral_constant<int, 1>{});
                 if constexpr (!(ABL & 4) && decltype(bar)::value) {
                     if constexpr ((ABL & 128) != 0) pt0 = __builtin_amdgcn_s_memtime();
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    wave_lds_sync();
                     if constexpr ((ABL & 128) != 0) pt1 = __builtin_amdgcn_s_memtime();
                     barrier_raw();
                     if constexpr ((ABL & 128) != 0) {
@@ -819,7 +797,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
                     const float mx = fmaxf(fmaxf(acc[i][jb][4 * g], acc[i][jb][4 * g + 1]),
                                            fmaxf(acc[i][jb][4 * g + 2], acc[i][jb][4 * g + 3]));
                     float x = fmaf(mx, sc[jb], sh[jb]);
-                    x = fmaxf(x, LRELU * x);
+                    x = lrelu_fmax(x);
                     __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (bf16_t)x), ors,
                                                           (cbase + (py * Wp + px) * a.out_pix_stride + co) * 2, 0, 0);
                 }
@@ -834,7 +812,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
     i32x4 fa[4], fb[8], na[4], nb[8];
     frags(0, 0, 0, fa, fb);
     if constexpr ((ABL & 8) != 0) frags(0, 0, 0, na, nb);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_sync();
     barrier_raw();   // slice 0 read: the loaders may now overwrite weight slot 0
 
     // first: the tile's first step (accumulate onto zero); bar: the step closes a BP-step group
@@ -861,7 +839,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_stream(HaloArgs a) {
         if constexpr (!(ABL & 4) && decltype(bar)::value) {
             if constexpr ((ABL & 128) != 0) pt0 = __builtin_amdgcn_s_memtime();
             // LDS reads only: the epilogue's global stores (vmcnt on gfx9) are never waited for
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wave_lds_sync();
             if constexpr ((ABL & 128) != 0) pt1 = __builtin_amdgcn_s_memtime();
             barrier_raw();
             if constexpr ((ABL & 128) != 0) {

@@ -18,26 +18,13 @@
 //     output channels; block row r = 4 q + 2 dy + dx is pixel (2 (q >> 1) + dy, 2 (q & 1) + dx), so a lane's
 //     4 accumulator rows are one 2x2 pool window and BN / pool / LeakyReLU happen in registers.
 // Persistent over tiles in XCD-aware order (as conv_stream.hip).
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 AVSE_DEBUG_RECORD(debug_read_v1r)
 namespace {
 
-constexpr float LRELU = 0.3f;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-constexpr int kOOB = 0x7fffff00;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-__device__ __forceinline__ void barrier_raw() { asm volatile("s_barrier" ::: "memory"); }
-// weights image: row (slice, co) 64 B, 16-B k-group s at s ^ wsw(co) (conflict-free for the 16x16x32
-// B-operand lane groups, tools/lds_swizzle_search.py)
-__device__ __forceinline__ int wsw(int co) { return 2 * ((co >> 2) & 1); }
+// weights image: row (slice, co) 64 B, 16-B k-group s at s ^ wsw(co) (mfma_util.h)
 
 // VT (template, the loader waves' video element type): float, or unsigned char for uint8 crops (HaloArgs::video_u8).
 // A uint8 window pixel is NF bytes at byte offset pix * NF of its clip, which is not dword aligned: it lies inside the
@@ -240,11 +227,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float x = fmaf(m[e], osc[e], osh[e]);
-                    asm("v_max_f32 %0, %1, %2" : "=v"(v[e]) : "v"(x), "v"(LRELU * x));   // LeakyReLU, no canonicalise
+                    v[e] = lrelu_vmax(x);
                 }
-                const bf16x2 lo = __builtin_convertvector((f32x2){v[0], v[1]}, bf16x2);
-                const bf16x2 hi = __builtin_convertvector((f32x2){v[2], v[3]}, bf16x2);
-                const i32x2 o = {__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi)};
+                const i32x2 o = pack4_bf16(v[0], v[1], v[2], v[3]);
                 __builtin_amdgcn_raw_buffer_store_b64(o, ors, ovlane, otile + r * orow, 0);
             }
         };
@@ -267,7 +252,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
         }
         if (nmine > 2) win_load(Q0{}, 2);
         if (nmine > 3) win_load(Q1{}, 3);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // B_-1: weights, BN tail, windows 0 and 1
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
                 tag((k + 2) % NWS, k + 2);
                 if (k + 4 < nmine) win_load(set, k + 4);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wave_lds_sync();
             if constexpr (!(ABL & 8)) barrier_raw();   // B_k: staging k written, window k+2 stored
         };
         for (int k = 0; k < nmine; k += 2) {
@@ -343,9 +328,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ca[i]),
-                                                                     __builtin_bit_cast(bf16x8, cb[j]),
-                                                                     first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j], 0, 0, 0);
+                acc[i][j] = mfma_bf16(ca[i], cb[j], first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j]);
     };
     // slice s: MFMAs on (ca, cb) interleaved with the fragment reads of slice s+1 into (xa, xb)
     auto slice = [&](int hs, int ky_next, i32x4 (&ca)[4], i32x4 (&cb)[8], i32x4 (&xa)[4], i32x4 (&xb)[8], bool first) {
@@ -376,7 +359,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_v1r(HaloArgs a) {
         slice(hn, 0, xa, xb, ya, yb, false);
         if (kDebugBuild && lane == 0) AVSE_CHECK_DEV(tags[hs] == k, DK_V1R, 3, tags[hs], k);   // not yet replaced
         epilogue(k);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         if constexpr (!(ABL & 8)) barrier_raw();   // B_k: staging k is written; window k is no longer read
     };
     frags(0, 0, fa, fb);
@@ -505,7 +488,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
             }
         };
         // VideoNormalizer ((v - mean) / std: an IEEE division, the reference's numpy op), 'same' zero padding, split
-        bool in_bad = false;   // range guard of the split video input (avse_common.h pair_out_of_range)
+        bool in_bad = false;   // range guard of the split video input (mfma_util.h pair_out_of_range)
         auto win_store = [&](auto set, int hs) {
             constexpr int Q = decltype(set)::value;
 #pragma unroll
@@ -529,8 +512,9 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
                 _Float16 h[6], l[6];
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {
-                    h[i] = (_Float16)f[i];
-                    l[i] = (_Float16)(f[i] - (float)h[i]);
+                    const SplitPair p = split_pair(f[i]);
+                    h[i] = p.h;
+                    l[i] = p.l;
                     in_bad |= pair_out_of_range(f[i]);
                 }
                 const int wy = P / HW, wx = P - wy * HW;
@@ -555,14 +539,14 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
         }
         if (nmine > 2) win_load(Q0{}, 2);
         if (nmine > 3) win_load(Q1{}, 3);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // B_-1: weights, BN tail, windows 0 and 1
         auto iter = [&](auto set, int k) {
             if (k + 2 < nmine) {
                 if constexpr (!(V1S_ABL & 2)) win_store(set, (k + 2) % NWS);   // slot of window k-1, last read during tile k-1
                 if (k + 4 < nmine) win_load(set, k + 4);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wave_lds_sync();
             barrier_raw();   // B_k: window k+2 stored; window k is no longer read
         };
         for (int k = 0; k < nmine; k += 2) {
@@ -605,9 +589,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ca[i]),
-                                                                    __builtin_bit_cast(f16x8, cb[j]),
-                                                                    first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j], 0, 0, 0);
+                acc[i][j] = mfma_f16(ca[i], cb[j], first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j]);
     };
     // a group of 4 NJ MFMAs with ND DS reads spread over it (at most one read per MFMA, the rest after the last)
     auto sched = [](auto nds) {
@@ -660,16 +642,15 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
                 const float mx = fmaxf(fmaxf(acc[i][j][0], acc[i][j][1]), fmaxf(acc[i][j][2], acc[i][j][3]));
                 const int co = 16 * (cb0 + j) + r16;
                 float x = fmaf(mx, ssh[co], ssh[128 + co]);
-                x = fmaxf(x, LRELU * x);
-                const _Float16 h = (_Float16)x;
-                const _Float16 l = (_Float16)(x - (float)h);
+                x = lrelu_fmax(x);
+                const SplitPair p = split_pair(x);
                 bad |= pair_out_of_range(x);
                 if constexpr (V1S_ABL & 1) {
-                    if (x == 12345.f) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h), ors, 0, 0, 0);
+                    if (x == 12345.f) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.h), ors, 0, 0, 0);
                     continue;
                 }
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h), ors, (pbase + 32 * j) * 2, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, l), ors, (pbase + 32 * j + 16) * 2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.h), ors, (pbase + 32 * j) * 2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.l), ors, (pbase + 32 * j + 16) * 2, 0, 0);
             }
         }
     };
@@ -684,7 +665,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1s(HaloArgs a) {
         // read hits a stale slot and is never used)
         slice(hs, 4, hn, 0, xa, xb, ya, yb, false);
         epilogue(k);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // B_k: window k is no longer read
     };
     fragA(0, 0, 0, fa);
@@ -830,8 +811,9 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
                 for (int i = 0; i < NF; ++i) {
                     const float n = norm ? (f[i] - pm[Q][e]) / ps[Q][e] : f[i];
                     f[i] = pok[Q][e] ? n : 0.f;
-                    h[i] = (_Float16)f[i];
-                    l[i] = (_Float16)(f[i] - (float)h[i]);
+                    const SplitPair p = split_pair(f[i]);
+                    h[i] = p.h;
+                    l[i] = p.l;
                     in_bad |= pair_out_of_range(f[i]);
                 }
                 const int wy = P / HW, wx = P - wy * HW;
@@ -870,14 +852,14 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
         }
         if (nmine > 2) win_load(Q0{}, 2);
         if (nmine > 3) win_load(Q1{}, 3);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // B_-1: weights, BN tail, windows 0 and 1
         auto iter = [&](auto set, int k) {
             if (k + 2 < nmine) {
                 if constexpr (!(V1S_ABL & 2)) win_store(set, (k + 2) % NWS);
                 if (k + 4 < nmine) win_load(set, k + 4);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wave_lds_sync();
             barrier_raw();   // B_k: window k+2 stored; window k is no longer read
         };
         for (int k = 0; k < nmine; k += 2) {
@@ -945,9 +927,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ca[i]),
-                                                                    __builtin_bit_cast(f16x8, cb[j]),
-                                                                    first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j], 0, 0, 0);
+                acc[i][j] = mfma_f16(ca[i], cb[j], first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[i][j]);
     };
     auto sched = [](auto nds) {
         constexpr int ND = decltype(nds)::value, NM = 4 * NJ, P = ND < NM ? ND : NM;
@@ -992,17 +972,16 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
                 const float mx = fmaxf(fmaxf(acc[i][j][0], acc[i][j][1]), fmaxf(acc[i][j][2], acc[i][j][3]));
                 const int co = 16 * (cb0 + j) + r16;
                 float x = fmaf(mx, ssh[co], ssh[128 + co]);
-                x = fmaxf(x, LRELU * x);
-                const _Float16 h = (_Float16)x;
-                const _Float16 l = (_Float16)(x - (float)h);
+                x = lrelu_fmax(x);
+                const SplitPair p = split_pair(x);
                 bad |= pair_out_of_range(x);
                 if constexpr (V1S_ABL & 1) {
-                    if (x == 12345.f) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h), ors, 0, 0, 0);
+                    if (x == 12345.f) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.h), ors, 0, 0, 0);
                     continue;
                 }
                 // (measured: dword channel pairs, the partner's pieces by DPP, 0.693 vs 0.663 ms, r06o)
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h), ors, (pbase + 32 * j) * 2, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, l), ors, (pbase + 32 * j + 16) * 2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.h), ors, (pbase + 32 * j) * 2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, p.l), ors, (pbase + 32 * j + 16) * 2, 0, 0);
             }
         }
     };
@@ -1022,7 +1001,7 @@ __global__ __launch_bounds__(64 * (CW + 4), 1) void k_conv_v1p(HaloArgs a) {
         // slice 3 reads tile k+1's first fragments (past the last tile a stale slot, never used)
         slice(hs, 3, hn, 0, ya, yb, xa, xb, false);
         if (!late) epilogue(k);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_sync();
         barrier_raw();   // B_k: window k is no longer read
     };
     fragA(0, 0, 0, fa);

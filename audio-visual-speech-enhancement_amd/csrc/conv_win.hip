@@ -23,7 +23,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
@@ -43,8 +43,6 @@ constexpr int LDS_BYTES = 2 * WIN_BYTES + 3 * BSL;   // 52 KB (TM 128: three wor
 static_assert(WIN_BYTES % (16 * NTH) == 0, "whole pieces per thread");
 constexpr int MAXREG = 8;                            // clips per tile (host-checked)
 constexpr int MAXTAP = 32;
-constexpr float LRELU = 0.3f;
-constexpr int kOOB = 0x7fffff00;
 
 struct WinPhase {
     int dymin, dxmin;    // the phase's smallest tap offsets
@@ -57,12 +55,6 @@ struct WinArgs {
     int WP;              // window pitch (pixels)
     WinPhase ph[MAX_PHASES];
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-__device__ __forceinline__ int bswz(int row) { return ((row >> 3) & 1) * 3; }   // k_conv's B-slab swizzle
 
 template <bool FUSE>
 __global__ __launch_bounds__(NTH, WGM == 2 ? 3 : 2) void k_conv_win(ConvArgs a, WinArgs g) {
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(NTH, WGM == 2 ? 3 : 2) void k_conv_win(ConvArgs a, 
     // ---- B: the thread's 16-B piece of a slab (row tid >> 2, quarter tid & 3) ----
     const int brow = tid >> 2, bq = tid & 3;
     const int bsrc = n0 + brow < a.Co ? ((n0 + brow) * ph.kpad) * 2 + bq * 16 : kOOB;
-    const int bdst = brow * 64 + ((bq ^ bswz(brow)) << 4);
+    const int bdst = brow * 64 + ((bq ^ swz(brow)) << 4);
     // B slab s's offset (chunk-outer, tap-inner): t CIH 2 + c 64; the prologue's slabs 0..3, then stepped per slab
     auto bslab_off = [&](int s) {
         const int c = s / ntap, t = s - c * ntap;
@@ -186,17 +178,15 @@ __global__ __launch_bounds__(NTH, WGM == 2 ? 3 : 2) void k_conv_win(ConvArgs a, 
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int row = wn * 16 * NJ + 16 * j + fr;
-            fb[j] = *reinterpret_cast<const i32x4*>(bs + q * BSL + row * 64 + (((fg & 1) ^ bswz(row)) << 4));
-            fl[j] = *reinterpret_cast<const i32x4*>(bs + q * BSL + row * 64 + (((2 + (fg & 1)) ^ bswz(row)) << 4));
+            fb[j] = *reinterpret_cast<const i32x4*>(bs + q * BSL + row * 64 + (((fg & 1) ^ swz(row)) << 4));
+            fl[j] = *reinterpret_cast<const i32x4*>(bs + q * BSL + row * 64 + (((2 + (fg & 1)) ^ swz(row)) << 4));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fa[i]),
-                                                                    __builtin_bit_cast(f16x8, fb[j]), part[i][j], 0, 0, 0);
-                part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fa[i]),
-                                                                    __builtin_bit_cast(f16x8, fl[j]), part[i][j], 0, 0, 0);
+                part[i][j] = mfma_f16(fa[i], fb[j], part[i][j]);
+                part[i][j] = mfma_f16(fa[i], fl[j], part[i][j]);
             }
         if (++nblk == kFp32Block) {
             nblk = 0;
@@ -269,7 +259,7 @@ __global__ __launch_bounds__(NTH, WGM == 2 ? 3 : 2) void k_conv_win(ConvArgs a, 
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     float x = acc[i][j][r] * esc[j] + esh[j];
-                    x = x >= 0.f ? x : LRELU * x;
+                    x = lrelu_select(x);
                     x0 = fmaf(x, ewf[j], x0);
                 }
                 x0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x0), 0x128, 0xf, 0xf, false));
@@ -310,11 +300,11 @@ __global__ __launch_bounds__(NTH, WGM == 2 ? 3 : 2) void k_conv_win(ConvArgs a, 
             for (int r = 0; r < 4; ++r) {
                 if (orow[i][r] < 0) continue;
                 float x = acc[i][j][r] * esc[j] + esh[j];
-                x = x >= 0.f ? x : LRELU * x;
-                _Float16* o = reinterpret_cast<_Float16*>(a.out) + orow[i][r] + 32 * (n >> 4) + (n & 15);
-                const _Float16 h = (_Float16)x;
-                o[0] = h;
-                o[16] = (_Float16)(x - (float)h);
+                x = lrelu_select(x);
+                _Float16* o = pair_slot(reinterpret_cast<_Float16*>(a.out) + orow[i][r], n);
+                const SplitPair p = split_pair(x);
+                o[0] = p.h;
+                o[kPairL] = p.l;
                 bad |= pair_out_of_range(x);
             }
     }

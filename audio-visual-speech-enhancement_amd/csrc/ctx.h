@@ -133,7 +133,7 @@ struct avse_ctx {
     avse::Owned<float> mse_partial;
     avse::Owned<float> zero_video;  // one all-zero [128][128][8] clip (video == NULL forwards, any F <= 8)
     avse::Owned<int> gemm_counters; // gemm.hip split-K tickets (zero between launches)
-    // AVSE_F32_SPLIT range guard words (avse_common.h pair_out_of_range): [0] sticky for avse_forward (read and cleared
+    // AVSE_F32_SPLIT range guard words (mfma_util.h pair_out_of_range): [0] sticky for avse_forward (read and cleared
     // by avse_range_status), [1] cleared and read by each avse_forward_checked, [2] the all-zero-video embedding
     avse::Owned<unsigned> range;
     avse::Owned<unsigned, true> range_host;   // pinned readback words

@@ -8,8 +8,8 @@
 //   istft640  the synthesis side: one block's <= 3 frames from mel-dB and the mixture's STFT to windowed time frames
 //             (k_istft640's body, its sources and its sink passed in), and one output sample's overlap-add (k_ola's)
 #pragma once
-#include "avse_common.h"
 #include "fft_common.h"
+#include "mfma_util.h"   // lds_barrier, wave_lds_sync
 
 namespace avse {
 namespace spec640 {
@@ -25,11 +25,6 @@ __device__ __forceinline__ unsigned int f2ord(float f) {
 __device__ __forceinline__ float ord2f(unsigned int u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// wave-synchronous LDS hand-off: a wave's LDS operations complete in issue order, so draining lgkmcnt (and keeping the
-// compiler from moving memory operations across) is enough when every lane that wrote belongs to the reading wave
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // index of sample i after centre padding: reflect (librosa's 2017 default) or zero (then `keep` is false)
 __device__ __forceinline__ int padded_index(int i, int L, int pad_mode, bool& keep) {

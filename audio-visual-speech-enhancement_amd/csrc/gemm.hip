@@ -19,24 +19,15 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "avse_common.h"
+#include "mfma_util.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
-constexpr int kOOB = 0x7fffff00;
 constexpr int NT = 512;
 constexpr int SLAB = 16384;                     // A (8 KB) + W (8 KB) per 32-deep slab
 constexpr int GRP = 4 * SLAB;                   // one ring slot: 4 slabs
 constexpr int LDS_BYTES = 2 * GRP;              // 128 KB
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > kOOB ? kOOB : (bytes < 0 ? 0 : (int)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-__device__ __forceinline__ int wsw(int row) { return 2 * ((row >> 2) & 1); }
-__device__ __forceinline__ i32x4 lds16(const char* p) { return *reinterpret_cast<const i32x4*>(p); }
 
 // ABL: timing ablations (0 in the library; tools/gemm_ablate.hip, AVSE_GEMM_ABL variant libraries): 1 = the tile's
 // last workgroup skips reading the other partials, 2 = S16: no global loads, 4 = S16: no MFMAs (outputs meaningless)
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
 
     // ---- loader lane: row = tid / 4 of the A and W tiles, 16-B part tid % 4 of a 64-B slab row ----
     const int lrow = tid >> 2, part = tid & 3;
-    const int ldst = lrow * 64 + ((part ^ wsw(lrow)) << 4);   // + slot GRP + pos SLAB (+ 8192 for W)
+    const int ldst = slab_row_addr(lrow, part);   // + slot GRP + pos SLAB (+ 8192 for W)
     const __amdgpu_buffer_rsrc_t rsW = make_rsrc(g.w, (long long)g.N * g.kpad * KB);
     const int wvoff = (n0 + lrow < g.N) ? (n0 + lrow) * g.kpad * KB + part * 16 : kOOB;
     constexpr int PIXB = 512 * KB, CPT = PIXB / 64;   // mode 1: bytes per input pixel, 64-B chunks per tap
@@ -113,35 +104,36 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
         *reinterpret_cast<i32x4*>(d + 8192) = vw;
     };
     // ---- fragments: A rows 64 wm + 16 i + r16, W rows 32 wn + 16 j + r16 (16-B k-group kg, swizzled) ----
+    // (afr, bfr and bfl stay written out: through slab_row_addr / slab_slot_addr the address prologue's registers move)
     const int afr = (64 * wm + r16) * 64 + ((kg ^ wsw(r16)) << 4);
     // S16: the h half of W read by every lane (k-group kg & 1) and the l half (2 + (kg & 1))
     const int bfr = 8192 + (32 * wn + r16) * 64 + (((S16 ? kg & 1 : kg) ^ wsw(r16)) << 4);
     const int bfl = 8192 + (32 * wn + r16) * 64 + (((2 + (kg & 1)) ^ wsw(r16)) << 4);
     // PR: slab (s & ~1) + (kg >> 1) of the pair; h halves (16-B group kg & 1) and l halves (2 + (kg & 1)) of A and W
     const int pso = (kg >> 1) * SLAB;
-    const int pah = pso + (64 * wm + r16) * 64 + (((kg & 1) ^ wsw(r16)) << 4);
-    const int pal = pso + (64 * wm + r16) * 64 + (((2 + (kg & 1)) ^ wsw(r16)) << 4);
+    const int pah = slab_row_addr(64 * wm + r16, kg & 1, pso);
+    const int pal = slab_row_addr(64 * wm + r16, 2 + (kg & 1), pso);
     i32x4 fa[2][4], fb[2][2], fl[2][2], fal[2][4];
     auto read_pair = [&](int s, int buf) {   // s even: fa = A'h, fal = A'l, fb = W'h, fl = W'l
         const char* const b = lds + ((s >> 2) & 1) * GRP + (s & 3) * SLAB;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[buf][i] = lds16(b + pah + 1024 * i);
+        for (int i = 0; i < 4; ++i) fa[buf][i] = lds16(b, pah + 1024 * i);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fal[buf][i] = lds16(b + pal + 1024 * i);
+        for (int i = 0; i < 4; ++i) fal[buf][i] = lds16(b, pal + 1024 * i);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fb[buf][j] = lds16(b + pso + bfr + 1024 * j);
+        for (int j = 0; j < 2; ++j) fb[buf][j] = lds16(b, pso + bfr + 1024 * j);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fl[buf][j] = lds16(b + pso + bfl + 1024 * j);
+        for (int j = 0; j < 2; ++j) fl[buf][j] = lds16(b, pso + bfl + 1024 * j);
     };
     auto read = [&](int s, int buf) {
         const char* const b = lds + ((s >> 2) & 1) * GRP + (s & 3) * SLAB;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[buf][i] = lds16(b + afr + 1024 * i);
+        for (int i = 0; i < 4; ++i) fa[buf][i] = lds16(b, afr + 1024 * i);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fb[buf][j] = lds16(b + bfr + 1024 * j);
+        for (int j = 0; j < 2; ++j) fb[buf][j] = lds16(b, bfr + 1024 * j);
         if constexpr (S16) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) fl[buf][j] = lds16(b + bfl + 1024 * j);
+            for (int j = 0; j < 2; ++j) fl[buf][j] = lds16(b, bfl + 1024 * j);
         }
     };
     f32x4 acc[4][2], blk[4][2];
@@ -203,9 +195,8 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
-                            blk[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                                __builtin_bit_cast(f16x8, h == 1 ? fal[p & 1][i] : fa[p & 1][i]),
-                                __builtin_bit_cast(f16x8, h == 2 ? fl[p & 1][j] : fb[p & 1][j]), blk[i][j], 0, 0, 0);
+                            blk[i][j] = mfma_f16(h == 1 ? fal[p & 1][i] : fa[p & 1][i], h == 2 ? fl[p & 1][j] : fb[p & 1][j],
+                                                 blk[i][j]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -243,9 +234,7 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
-                            blk[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                                __builtin_bit_cast(f16x8, fa[q & 1][i]), __builtin_bit_cast(f16x8, h ? fl[q & 1][j] : fb[q & 1][j]),
-                                blk[i][j], 0, 0, 0);
+                            blk[i][j] = mfma_f16(fa[q & 1][i], h ? fl[q & 1][j] : fb[q & 1][j], blk[i][j]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -272,9 +261,7 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[q & 1][i]),
-                                                                             __builtin_bit_cast(bf16x8, fb[q & 1][j]),
-                                                                             acc[i][j], 0, 0, 0);
+                        acc[i][j] = mfma_bf16(fa[q & 1][i], fb[q & 1][j], acc[i][j]);
             }
         }
     }
@@ -319,11 +306,11 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
     bool bad = false;
     auto put = [&](long long base, int n, float v) {
         if constexpr (S16) {
-            const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
+            const SplitPair p = split_pair(v);
             bad |= pair_out_of_range(v);
-            unsigned short* o = reinterpret_cast<unsigned short*>(g.out) + base + (n >> 4) * 32 + (n & 15);
-            o[0] = __builtin_bit_cast(unsigned short, h);
-            o[16] = __builtin_bit_cast(unsigned short, l);
+            unsigned short* o = pair_slot(reinterpret_cast<unsigned short*>(g.out) + base, n);
+            o[0] = __builtin_bit_cast(unsigned short, p.h);
+            o[kPairL] = __builtin_bit_cast(unsigned short, p.l);
         } else {
             g.out[base + n] = (bf16_t)v;
         }
@@ -342,13 +329,13 @@ __global__ __launch_bounds__(NT, 1) void k_gemm(GemmArgs g) {
                 for (int e = 0; e < 4; ++e) {
                     if (mb + e >= g.M) continue;
                     float v = acc[i][j][e] * sc + sh;
-                    if (g.act) v = v >= 0.f ? v : LRELU * v;
+                    if (g.act) v = lrelu_select(v);
                     put((long long)(mb + e) * g.ldo + g.out_off, n, v);
                 }
             } else {
                 float v = fmaxf(fmaxf(acc[i][j][0] * sc + sh, acc[i][j][1] * sc + sh),
                                 fmaxf(acc[i][j][2] * sc + sh, acc[i][j][3] * sc + sh));
-                if (g.act) v = v >= 0.f ? v : LRELU * v;
+                if (g.act) v = lrelu_select(v);
                 const int clip = mb >> 4, q = (mb & 15) >> 2;   // pooled pixel q of the 2 x 2 output (HWC)
                 put((long long)clip * g.ldo + g.out_off + q * g.N * (S16 ? 2 : 1), n, v);
             }

@@ -98,8 +98,6 @@ static_assert(FW % FPG == 0, "whole waves of 3 frames");
 constexpr int IWAVES = FW / FPG;             // 11
 constexpr int NMEL = 80;                     // bands (host-checked: the fused kernel runs only for n_mels == 80)
 
-__device__ __forceinline__ void ibarrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // AVSE_ISTFT_STAMP (diagnostic variant builds only, never the library): thread 0 of each block adds the s_memtime
 // cycles of every phase of every item into g_ist_stamps[block][phase]; avse_istft_stamps() copies them out
 #ifdef AVSE_ISTFT_STAMP
@@ -115,11 +113,6 @@ __device__ unsigned long long g_ist_stamps[1024][9];
 #define IST_STAMP_INIT
 #define IST_STAMP(i)
 #endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ist_rsrc(const void* base, long long bytes) {
-    const int nrec = bytes > 0x7fffff00 ? 0x7fffff00 : (int)bytes;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
 
 // RG: the ragged form (avse_istft_ragged).  An item is (u, chunk) of the item table; the utterance's frame counts
 // and the offsets of its mel block, its STFT and its output come from its RaggedUtt row, for the item being computed
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
             const long long mel_u = RG        ? (long long)n_mels * T
                                     : a.spf > 0 ? (long long)a.n_slices * n_mels * a.spf
                                                 : (long long)n_mels * T;
-            const __amdgpu_buffer_rsrc_t rsM = ist_rsrc(a.mel_db + (RG ? ru.mel_off : u * mel_u), mel_u * 4);
+            const __amdgpu_buffer_rsrc_t rsM = make_rsrc_nonneg(a.mel_db + (RG ? ru.mel_off : u * mel_u), mel_u * 4);
 #pragma unroll
             for (int j = 0; j < IT1; ++j) {
                 const int it = min(tid + 64 * IWAVES * j, FW * n_mels - 1);
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
             return;
         }
         const long long stft_u = (long long)a.nb * (RG ? ru.L : a.stft_frames);
-        const __amdgpu_buffer_rsrc_t rsD = ist_rsrc(a.stft + (RG ? ru.in_off : u * stft_u), stft_u * 8);
+        const __amdgpu_buffer_rsrc_t rsD = make_rsrc_nonneg(a.stft + (RG ? ru.in_off : u * stft_u), stft_u * 8);
 #pragma unroll
         for (int j = 0; j < IT3; ++j) {
             if (j != part) continue;
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                 if (it < FW * n_mels && f < nfr) amp[f][m] = __builtin_amdgcn_exp2f(0.16609640474436813f * mv[j]);
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(0)
         // ---- 2. y = (M M^T)^{-1} amp for the chunk's frames ----
         // MFMA form: Y [48 frames (FW used) x 80] = A [48 x 80] x G [80 x 80], G = (M M^T)^{-1} (host, double ->
@@ -303,7 +296,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                 }
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(1)
         // ---- 3. spectrum x unit phase, folded into Z' = conj(E + i O) (k) and E - i O (320 - k) ----
         // (the mixture-STFT loads dk / dm were issued at the start of the item)
@@ -339,7 +332,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                 }
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(2)
         const bool more = item + (int)gridDim.x < n_items;   // the next item's loads, spread over step 4
         if (more) { issue_loads(item + gridDim.x, -1); issue_loads(item + gridDim.x, 0); }
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
 #pragma unroll
                 for (int n2 = 0; n2 < 20; ++n2) v[n2] = zv[16 * n2];
             }
-            ibarrier();
+            lds_barrier();
             IST_STAMP(3)
             if (more) issue_loads(item + gridDim.x, 1);
             if (act) {
@@ -372,7 +365,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                     }
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(4)
         if (more) issue_loads(item + gridDim.x, 2);
         {
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
 #pragma unroll
                 for (int n1 = 0; n1 < 16; ++n1) v[n1] = zv[n1];
             }
-            ibarrier();
+            lds_barrier();
             IST_STAMP(5)
             if (more) issue_loads(item + gridDim.x, 3);
             if (act) {
@@ -402,7 +395,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                     }
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(6)
         // ---- 5. overlap-add + window-sum-square + centre trim (first: the next item's loads) ----
         {
@@ -440,7 +433,7 @@ __global__ __launch_bounds__(64 * IWAVES) AVSE_ISTFT_ATTR void k_istft_fused(Ist
                 out[j] = yv;
             }
         }
-        ibarrier();
+        lds_barrier();
         IST_STAMP(7)
     }
 }
@@ -667,7 +660,7 @@ int launch_istft(const IstftArgs& a, hipStream_t s) {
     if (a.n_utt <= 0 || a.T <= 0) return 0;
     // fused path: 32-bit offsets into one utterance's STFT (nb x frames x 8 B < 2 GiB: ~2 hours at 16 kHz)
     if (a.N == 640 && a.hop == 160 && a.n_mels == NMEL && a.gram_inv && a.bins &&
-        (long long)a.nb * a.stft_frames * 8 < 0x7fffff00LL) {
+        (long long)a.nb * a.stft_frames * 8 < kOOB) {
         if (a.T < 2) return 0;
         const int n_chunks = (a.T - 1 + OF - 1) / OF;
         const long long items = (long long)n_chunks * a.n_utt;

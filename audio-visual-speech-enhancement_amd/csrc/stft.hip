@@ -353,8 +353,7 @@ constexpr int SEG_FS = 360, SEG_MW = MW + 4;
 static_assert(2 * SEG_FS + 321 + SEG_MW <= FPG * 2 * ZS && SEG_FS % 4 == 0, "magnitude frames inside the wave region");
 
 __device__ __forceinline__ void seg_dma(float* sb, const float* __restrict__ sg, int wave, int lane, int pad_mode) {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg), (short)0, SEG_L * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(sg, SEG_L * 4);
     const int base = FPG * wave * 160 - 320;   // sample index of buffer slot 0
     typedef __attribute__((address_space(3))) void* lds_ptr;
     if (wave != 0 && wave != WAVES - 1) {      // (wave-uniform) interior: base .. base + 1023 inside the utterance

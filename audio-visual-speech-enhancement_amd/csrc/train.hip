@@ -33,13 +33,12 @@
 #include <vector>
 
 #include "../../include/avse.h"
-#include "avse_common.h"
+#include "mfma_util.h"
 #include "netplan.h"
 
 namespace avse {
 namespace {
 
-constexpr float LRELU = 0.3f;
 constexpr float BN_MOMENTUM = 0.99f;
 
 __host__ __device__ inline uint32_t drop_hash(uint32_t seed, uint32_t layer, uint32_t idx) {
@@ -268,7 +267,9 @@ struct ActArgs {
     int out_pix, out_c;
 };
 
-__device__ __forceinline__ float bn_lrelu(const ActArgs& a, long long zi, int c, float& yhat) {
+// BatchNorm with the batch statistics, then LeakyReLU in mfma_util.h's lrelu_select form, written out: through the
+// function the compiler inverts the compare.  yhat feeds the backward pass's sign test.
+__device__ __forceinline__ float act_bn(const ActArgs& a, long long zi, int c, float& yhat) {
     yhat = fmaf(a.gamma[c], (a.z[zi] - a.mean[c]) * a.inv[c], a.beta[c]);
     return yhat >= 0.f ? yhat : LRELU * yhat;
 }
@@ -292,10 +293,10 @@ __global__ void k_act_fwd(ActArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const long long zi = (((long long)n * a.Hq + 2 * oy + (e >> 1)) * a.Wq + 2 * ox + (e & 1)) * a.C + c;
-                y = fmaxf(y, bn_lrelu(a, zi, c, yh));
+                y = fmaxf(y, act_bn(a, zi, c, yh));
             }
         } else {
-            y = bn_lrelu(a, i, c, yh);
+            y = act_bn(a, i, c, yh);
         }
         y *= drop_scale(a, i);
         a.out[n * a.out_clip + (long long)(oy * Wo + ox) * a.out_pix + a.out_c + c] = y;
@@ -319,14 +320,14 @@ __global__ void k_act_bwd(ActArgs a, const float* __restrict__ gout, long long g
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 zis[e] = (((long long)n * a.Hq + 2 * oy + (e >> 1)) * a.Wq + 2 * ox + (e & 1)) * a.C + c;
-                const float y = bn_lrelu(a, zis[e], c, yhs[e]);
+                const float y = act_bn(a, zis[e], c, yhs[e]);
                 if (y > best) { best = y; be = e; bh = yhs[e]; }
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) ghat[zis[e]] = (e == be) ? g * (bh >= 0.f ? 1.f : LRELU) : 0.f;
         } else {
             float yh;
-            (void)bn_lrelu(a, i, c, yh);
+            (void)act_bn(a, i, c, yh);
             ghat[i] = g * (yh >= 0.f ? 1.f : LRELU);
         }
     }
