@@ -119,6 +119,13 @@ SIGNATURES = {
                                  _c_void_p, _c_void_p]),
     "avse_stream_reset": (_int, [_c_void_p, _c_void_p]),
     "avse_stream_destroy": (None, [_c_void_p]),
+    # per-stream forms: push_each(s, samples, host sample_off, host n_new, video, host v_new, host flush, vmean, vstd,
+    # out, out_stride, host n_out, mel_db, pred_db, host k_new, stream); reset_each(s, host which, stream);
+    # state(s, host n_samples, host n_video, host flushed)
+    "avse_stream_push_each": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                     _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_stream_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
+    "avse_stream_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

@@ -29,6 +29,12 @@
 //                   one: a slice's floor needs the maxima of all its frames, which other blocks of k_stream_spec write.
 //   k_stream_synth  k_istft640's body (frame640.h synth_frames) on the predicted frames and the ring's phases
 //   k_stream_ola    k_ola's sample (frame640.h ola_sample) over the frame ring for the samples that became final
+//
+// Streams need not move together (avse_stream_push_each): the session keeps its counters per stream, stream_geom.h
+// turns a call's per-stream counts into one row per stream and one item table per kernel (block -> stream, chunk), and
+// k_stream_spec_each / _route_each / _synth_each / _ola_each run the bodies of the four kernels above with the row's
+// counters in place of the call's scalars; the forward runs once on the slices all streams completed.  The lock-step
+// calls run the lock-step kernels while every stream's counters are equal.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,6 +42,7 @@
 
 #include "ctx.h"
 #include "frame640.h"
+#include "stream_geom.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap (as stft.hip)
 #define AVSE_WPE4
@@ -88,128 +95,35 @@ __device__ __forceinline__ float frame_sample(const SpecStreamArgs& a, int b, lo
     return stream_sample(a, b, i);
 }
 
+// The kernel bodies below come from stream_body.inc, which says why they are shared as text.
 __global__ __launch_bounds__(64 * SWAVES) AVSE_WPE4 void k_stream_spec(SpecStreamArgs a) {
-    __shared__ float2 zbuf[SWAVES * FPG * ZS];
-    __shared__ float2 twl[640];
-    __shared__ v2f ut2[161];       // U = -i W640^k / 2 (untangling)
-    __shared__ float2 winl[320];
-    __shared__ float4 melw4[NMEL * MW / 4];
-    __shared__ int mel_st[NMEL];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
-    if ((int)blockIdx.x == a.nblk) {   // the new tail: the last TAIL samples received (zeros before sample 0)
-        for (int j = tid; j < TAIL; j += 64 * SWAVES) {
-            const long long i = a.n_new - TAIL + j;
-            a.tail_out[b * (long long)TAIL + j] = i < 0 ? 0.f : stream_sample(a, b, i);
-        }
-        return;
-    }
-    for (int i = tid; i < 640; i += 64 * SWAVES) twl[i] = a.twiddle[i];
-    for (int k = tid; k < 161; k += 64 * SWAVES) {
-        const float2 w = a.twiddle[k];
-        ut2[k] = v2f{0.5f * w.y, -0.5f * w.x};
-    }
-    for (int i = tid; i < 320; i += 64 * SWAVES) winl[i] = reinterpret_cast<const float2*>(a.window)[i];
-    for (int i = tid; i < NMEL * MW / 4; i += 64 * SWAVES) melw4[i] = reinterpret_cast<const float4*>(a.mel_weight)[i];
-    for (int i = tid; i < NMEL; i += 64 * SWAVES) mel_st[i] = a.mel_start[i];
+    const unsigned blk = blockIdx.x;
+#define STREAM_BODY_SPEC
+#include "stream_body.inc"
+#undef STREAM_BODY_SPEC
+}
 
-    const int g = FPG * wave;                                  // this wave's first frame in the block
-    const int nf = min(SCHUNK, a.nt - SCHUNK * (int)blockIdx.x);
-    const int ng = max(0, min(FPG, nf - g));
-    const long long tw0 = a.t0 + SCHUNK * (long long)blockIdx.x + g;   // the wave's first frame
-    const int f1 = lane >> 4, n1 = lane & 15;
-    float2 x[20];
-#pragma unroll
-    for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
-    if (f1 < ng) {
-        const long long s0 = (tw0 + f1) * 160 - 320;
-        if (s0 >= a.n_old && s0 + 640 <= a.n_new && (a.Lf < 0 || s0 + 640 <= a.Lf)) {   // all in this call's samples
-            const float* p = a.news + b * a.news_stride + (s0 - a.n_old) + 2 * n1;
-#pragma unroll
-            for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(p[32 * n2], p[32 * n2 + 1]);
-        } else {
-#pragma unroll
-            for (int n2 = 0; n2 < 20; ++n2) {
-                const long long i = s0 + 2 * (n1 + 16 * n2);
-                x[n2] = make_float2(frame_sample(a, b, i), frame_sample(a, b, i + 1));
-            }
-        }
-    }
-    __syncthreads();
-    float2* zw = zbuf + wave * FPG * ZS;
-    // ---- steps 1 and 2: the 16 x 20 split of k_spec640, wave-local (each wave owns its three frames) ----
-    v2f v[20];
-    window_frame(v, x, winl, n1);
-    if (f1 < ng) dft20_store(v, twl, zw + f1 * ZS, n1);
-    wave_lds_sync();
-    {
-        const int f = lane / 20, k2 = lane - 20 * (lane / 20);
-        const bool act = f < ng;
-        v2f w[16];
-        v2f* zf = reinterpret_cast<v2f*>(zw + min(f, FPG - 1) * ZS);
-        if (act) dft16_load(w, zf, k2);
-        wave_lds_sync();
-        if (act) dft16_store(w, zf, k2);
-    }
-    wave_lds_sync();
-    // ---- step 3: untangling -> the complex frame into the phase ring, its magnitudes into LDS; item = (f, k) ----
-    {
-        constexpr int IT3 = (FPG * 161 + 63) / 64;   // 8
-        float mk[IT3], mm[IT3];
-#pragma unroll
-        for (int j = 0; j < IT3; ++j) {
-            const int it = lane + 64 * j;
-            if (it >= ng * 161) break;
-            const int f = it / 161, k = it - 161 * f;
-            v2f X, Y;
-            pk_untangle(reinterpret_cast<const v2f*>(zw + f * ZS), k, ut2, X, Y);
-            mk[j] = pk_abs(X);
-            mm[j] = pk_abs(Y);
-            float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
-            o[k] = make_float2(X.x, X.y);
-            if (k != 160) o[320 - k] = make_float2(Y.x, -Y.y);   // X[320 - k] = conj(Y)
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int j = 0; j < IT3; ++j) {
-            const int it = lane + 64 * j;
-            if (it >= ng * 161) break;
-            const int f = it / 161, k = it - 161 * f;
-            float* mf = reinterpret_cast<float*>(zw + f * ZS);
-            mf[k] = mk[j];
-            mf[320 - k] = mm[j];
-        }
-        for (int it = lane; it < FPG * MW; it += 64) {   // bins [321, 321 + MW) are read by the padded band dots
-            const int f = it / MW, j = it - MW * f;
-            reinterpret_cast<float*>(zw + f * ZS)[321 + j] = 0.f;
-        }
-        wave_lds_sync();
-    }
-    // ---- step 4: Slaney mel + dB, item = (m, f) as k_spec640; unclamped, into the frame's slice slot ----
-    float fm0 = -INFINITY, fm1 = -INFINITY, fm2 = -INFINITY;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        const int it = lane + 64 * jj;
-        if (it >= FPG * NMEL) break;
-        const int m = __umul24(it, 43691) >> 17, f = it - 3 * m;   // m = it / 3 (it < 240)
-        if (f >= ng) continue;
-        const float* mf = reinterpret_cast<const float*>(zw + f * ZS) + mel_st[m];
-        const float acc = band_dot_nq(melw4 + m * (MW / 4), reinterpret_cast<const v2f*>(mf), a.nq[jj]);
-        const float db = mel_to_db(acc, a.amin, a.db_floor);
-        const long long t = tw0 + f, sl = t / a.spf;
-        a.mel_ring[(((long long)b * a.RS + (int)(sl % a.RS)) * NMEL + m) * a.spf + (int)(t - sl * a.spf)] = db;
-        fm0 = f == 0 ? fmaxf(fm0, db) : fm0;
-        fm1 = f == 1 ? fmaxf(fm1, db) : fm1;
-        fm2 = f == 2 ? fmaxf(fm2, db) : fm2;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        fm0 = fmaxf(fm0, __shfl_xor(fm0, o));
-        fm1 = fmaxf(fm1, __shfl_xor(fm1, o));
-        fm2 = fmaxf(fm2, __shfl_xor(fm2, o));
-    }
-    if (lane < ng) a.fmax_ring[(long long)b * a.R + (int)((tw0 + lane) % a.R)] = lane == 0 ? fm0 : lane == 1 ? fm1 : fm2;
+// Per-stream form (avse_stream_push_each): block -> item -> (stream, chunk) -> the stream's row (stream_geom.h), all
+// wave-uniform.  The row's counters take the place of the lock-step call's scalars in `a`; on entry a.tail_in / tail_out
+// are tail copies 0 / 1 and a.news the caller's `samples` (row stride 0: the row's sample_off addresses the stream).
+__global__ __launch_bounds__(64 * SWAVES) AVSE_WPE4 void k_stream_spec_each(SpecStreamArgs a, const StreamRow* __restrict__ rows,
+                                                                            const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    const float* t0 = a.tail_in;
+    float* t1 = a.tail_out;
+    a.tail_in = r.tail_in ? t1 : t0;
+    a.tail_out = r.tail_in ? const_cast<float*>(t0) : t1;   // the other copy (written only when the stream was fed)
+    a.news += r.sample_off;
+    a.n_old = r.n_old; a.n_new = r.n_new;
+    a.Lf = r.Lf;
+    a.t0 = r.t0; a.nt = r.nt; a.nblk = r.nblk;
+    const int b = it.b;
+    const unsigned blk = it.chunk;
+#define STREAM_BODY_SPEC
+#include "stream_body.inc"
+#undef STREAM_BODY_SPEC
 }
 
 struct RouteArgs {
@@ -248,45 +162,55 @@ __global__ __launch_bounds__(256) void k_stream_route(RouteArgs a) {
                                  : a.vnew + ((long long)b * a.v_new + (k - a.v_old)) * a.vbytes;
         char* dst = to_net ? a.vstage + ((long long)b * a.k_new + (k - a.k_old)) * a.vbytes
                            : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
-        if (a.vec16) {
-            const long long n = a.vbytes / 16;
-            const uint4* s4 = reinterpret_cast<const uint4*>(src);
-            uint4* d4 = reinterpret_cast<uint4*>(dst);
-            for (long long i = part * 256LL + tid; i < n; i += ROUTE_X * 256LL) d4[i] = s4[i];
-        } else {
-            const long long n = a.vbytes / 4;
-            const unsigned* s1 = reinterpret_cast<const unsigned*>(src);
-            unsigned* d1 = reinterpret_cast<unsigned*>(dst);
-            for (long long i = part * 256LL + tid; i < n; i += ROUTE_X * 256LL) d1[i] = s1[i];
-        }
+#define STREAM_BODY_COPY
+#include "stream_body.inc"
+#undef STREAM_BODY_COPY
         return;
     }
-    // one block per stream: the floor of slice k is (the maximum over every frame up to its last) - top_db.  Wave w
-    // takes the maxima of slices w, w + 4, ..: a lane per frame, then the wave's maximum (a maximum has no order)
-    const int b = blockIdx.x - n_video;
-    for (int kk = tid >> 6; kk < a.k_new; kk += 4) {
-        const long long t0 = (a.k_old + kk) * a.spf;
-        float m = -INFINITY;
-        for (int tt = tid & 63; tt < a.spf; tt += 64) m = fmaxf(m, a.fmax_ring[(long long)b * a.R + (int)((t0 + tt) % a.R)]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if ((tid & 63) == 0) slice_max[kk] = m;
+    const int b = blockIdx.x - n_video;   // one block per stream
+#define STREAM_BODY_CLAMP
+#define STREAM_K_OLD a.k_old
+#define STREAM_K_NEW a.k_new
+#define STREAM_CLIP(kk) ((long long)b * a.k_new + kk)
+#include "stream_body.inc"
+#undef STREAM_K_OLD
+#undef STREAM_K_NEW
+#undef STREAM_CLIP
+#undef STREAM_BODY_CLAMP
+}
+
+// Per-stream form: an item is part chunk % ROUTE_X of the move of the stream's slice k_old + chunk / ROUTE_X (only
+// slices that move are listed), or (chunk == STREAM_CLAMP) its clamp block.  a.vnew is the packed video of the call;
+// the network input, mel_out and vstage are compacted: the stream's slices are clips clip0 .. clip0 + k_new - 1.
+__global__ __launch_bounds__(256) void k_stream_route_each(RouteArgs a, const StreamRow* __restrict__ rows,
+                                                           const StreamItem* __restrict__ items) {
+    __shared__ float slice_max[MAX_SLICES_CAP];
+    const int tid = threadIdx.x;
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    const int b = it.b;
+    if (it.chunk != STREAM_CLAMP) {
+        const int kk = it.chunk / ROUTE_X, part = it.chunk - ROUTE_X * kk;
+        const long long k = r.k_old + kk;
+        const bool from_q = k < r.v_old, to_net = kk < r.k_new;
+        const char* src = from_q ? a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes
+                                 : a.vnew + (r.video_off + (k - r.v_old)) * a.vbytes;
+        char* dst = to_net ? a.vstage + ((long long)r.clip0 + kk) * a.vbytes
+                           : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
+#define STREAM_BODY_COPY
+#include "stream_body.inc"
+#undef STREAM_BODY_COPY
+        return;
     }
-    float cur = a.run_max[b];
-    __syncthreads();   // the slices' maxima are there, and every thread has read the old running maximum
-    const int per = NMEL * a.spf;
-    for (int kk = 0; kk < a.k_new; ++kk) {   // the prefix maximum, in slice order
-        cur = fmaxf(cur, slice_max[kk]);
-        const float floor_db = a.top_db >= 0.f ? cur - a.top_db : -INFINITY;
-        const float* src = a.mel_ring + ((long long)b * a.RS + (int)((a.k_old + kk) % a.RS)) * per;
-        const long long d0 = ((long long)b * a.k_new + kk) * per;
-        for (int i = tid; i < per; i += 256) {
-            const float v = fmaxf(src[i], floor_db);
-            a.net_in[d0 + i] = v;
-            if (a.mel_out) a.mel_out[d0 + i] = v;
-        }
-    }
-    if (tid == 0) a.run_max[b] = cur;
+#define STREAM_BODY_CLAMP
+#define STREAM_K_OLD r.k_old
+#define STREAM_K_NEW r.k_new
+#define STREAM_CLIP(kk) ((long long)r.clip0 + kk)
+#include "stream_body.inc"
+#undef STREAM_K_OLD
+#undef STREAM_K_NEW
+#undef STREAM_CLIP
+#undef STREAM_BODY_CLAMP
 }
 
 struct SynthArgs {
@@ -296,17 +220,35 @@ struct SynthArgs {
     int nt, R;
 };
 
-__global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s) {
-    const int b = blockIdx.y;
-    const int t0 = blockIdx.x * istft640::FPG;
+// One group of FPG frames from t0 of stream b's s.nt predicted frames; clip(sl) is the clip of a.mel_db that holds the
+// stream's slice sl of this call.  (Its callers are distinct instances, Clip being a lambda type: one LDS allocation of
+// synth_frames per kernel.)
+template <class Clip>
+__device__ __forceinline__ void synth_group(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
     istft640::synth_frames(
         a, min(istft640::FPG, s.nt - t0),
         [&](int m, int f) {
             const int t = t0 + f, sl = t / a.spf;
-            return a.mel_db[(((long long)b * a.n_slices + sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
+            return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
         },
         [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; },
         [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 640; });
+}
+
+__global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s) {
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.x * istft640::FPG;
+    synth_group(a, s, b, t0, [&](int sl) { return (long long)b * a.n_slices + sl; });
+}
+
+// Per-stream form: item (stream, group); the stream inverts its k_new slices from frame spf k_old on.
+__global__ __launch_bounds__(64) void k_stream_synth_each(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
+                                                          const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    s.T0 = r.k_old * a.spf;
+    s.nt = r.k_new * a.spf;
+    synth_group(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
 }
 
 struct OlaArgs {
@@ -317,9 +259,8 @@ struct OlaArgs {
     int n_out, R;
 };
 
-__global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a) {
-    const int b = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
+// output sample j of this call of stream b
+__device__ __forceinline__ void ola_out(const OlaArgs& a, const int b, const int j) {
     if (j >= a.n_out) return;
     const long long p = a.e_old + j + 320;   // position in the untrimmed signal
     a.out[b * a.out_stride + j] = istft640::ola_sample(p, a.T, 640, 160, a.window, [&](long long t, int o) {
@@ -327,23 +268,32 @@ __global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a) {
     });
 }
 
-// the host totals after n samples and v video slices
-struct Counts {
-    int64_t frames, slices, emitted;
-};
-Counts stream_totals(int n_fft, int hop, int spf, int64_t n, int64_t v, bool flushed) {
-    Counts c;
-    if (flushed) {
-        c.frames = spf * v;
-        c.slices = v;
-        c.emitted = v > 0 ? (int64_t)hop * (spf * v - 1) : 0;
-        return c;
-    }
-    c.frames = n < n_fft / 2 + 1 ? 0 : (n - n_fft / 2) / hop + 1;   // frame 0 reads x[n_fft / 2] (left reflection)
-    c.slices = std::min(c.frames / spf, v);
-    c.emitted = std::max<int64_t>(0, (int64_t)spf * hop * c.slices - n_fft / 2);
-    return c;
+// Per-stream form: item (stream, block of 256 samples)
+__global__ __launch_bounds__(256) void k_stream_ola_each(OlaArgs a, const StreamRow* __restrict__ rows,
+                                                         const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    a.e_old = r.e_old; a.T = r.T; a.n_out = r.n_out;
+    ola_out(a, it.b, it.chunk * STREAM_OLA_BLOCK + threadIdx.x);
 }
+
+// The streams ids[0 .. gridDim.x) go back to the state after create: both tail copies zero, running maximum -inf.
+__global__ __launch_bounds__(256) void k_stream_reset_each(float* tail, float* run_max, const int* __restrict__ ids, int B) {
+    const int b = ids[blockIdx.x];
+    for (int j = threadIdx.x; j < 2 * TAIL; j += 256) {
+        const int copy = j / TAIL;
+        tail[((long long)copy * B + b) * TAIL + (j - copy * TAIL)] = 0.f;
+    }
+    if (threadIdx.x == 0) run_max[b] = -INFINITY;
+}
+
+__global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a) {
+    ola_out(a, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+}
+
+using Counts = StreamCounts;   // the host totals (stream_geom.h stream_totals)
+static_assert(SCHUNK == STREAM_SCHUNK && ROUTE_X == STREAM_ROUTE_X && istft640::FPG == STREAM_SYNTH_FPG,
+              "stream_geom.h chunks the kernels' work");
 
 }  // namespace
 }  // namespace avse
@@ -363,10 +313,30 @@ struct avse_stream {
     Owned<float> tail, mel_ring, fmax_ring, run_max, net_in, pred, frame_ring;
     Owned<float2> phase_ring;
     Owned<char> vq, vstage;
-    // host counters
+    // host counters, per stream; n / v / parity / flushed mirror them while `uniform` (every stream's are equal), which
+    // is when the lock-step calls run the lock-step kernels
+    std::vector<StreamState> st;
+    bool uniform = true;
     int64_t n = 0, v = 0;
     int parity = 0;           // which tail copy holds the last samples
     bool flushed = false, broken = false;
+    // per-stream calls: the rows of the call being decided, and the pinned staging ring their tables go up from (one
+    // slot per call in turn; `staged[i]` is recorded once the copy out of slot i is queued)
+    static constexpr int SLOTS = 4;
+    std::vector<StreamRow> rows;
+    std::vector<int64_t> arg_n, arg_v, arg_off;   // a lock-step call's arguments, per stream
+    std::vector<uint8_t> arg_flush;
+    StreamItemCounts cap;     // items per table, all streams
+    size_t slot_bytes = 0;
+    Owned<char, true> staging;
+    Owned<char> tables;       // device copy of the current call's tables
+    hipEvent_t staged[SLOTS] = {};
+    bool staged_used[SLOTS] = {};
+    int slot = 0;
+    ~avse_stream() {
+        for (hipEvent_t e : staged)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -377,7 +347,170 @@ int stream_init_state(avse_stream* s, hipStream_t st) {
     s->n = s->v = 0;
     s->parity = 0;
     s->flushed = s->broken = false;
+    std::fill(s->st.begin(), s->st.end(), StreamState{0, 0, 0, 0});
+    s->uniform = true;
     return 0;
+}
+
+// the lock-step mirror -> every stream (after a lock-step step)
+void stream_set_all(avse_stream* s) {
+    std::fill(s->st.begin(), s->st.end(), StreamState{s->n, s->v, (uint8_t)s->flushed, (uint8_t)s->parity});
+    s->uniform = true;
+}
+
+// after a per-stream step: are the streams in lock step again?  (then the mirror holds their counters)
+void stream_refresh_uniform(avse_stream* s) {
+    const StreamState a = s->st[0];
+    bool u = true;
+    for (const StreamState& t : s->st) u = u && t.n == a.n && t.v == a.v && t.flushed == a.flushed && t.parity == a.parity;
+    s->uniform = u;
+    if (u) {
+        s->n = a.n; s->v = a.v;
+        s->parity = a.parity;
+        s->flushed = a.flushed != 0;
+    }
+}
+
+// The next slot of the pinned staging ring, once the copy that last left it has been read: the only wait of a
+// per-stream call, and only when SLOTS calls are still in flight.
+int stream_stage_acquire(avse_stream* s, char** host) {
+    const int i = s->slot;
+    if (s->staged_used[i]) AVSE_HIP_CHECK(hipEventSynchronize(s->staged[i]));
+    *host = s->staging + (size_t)i * s->slot_bytes;
+    return 0;
+}
+int stream_stage_upload(avse_stream* s, size_t bytes, hipStream_t st) {
+    const int i = s->slot;
+    AVSE_HIP_CHECK(hipMemcpyAsync(s->tables, s->staging + (size_t)i * s->slot_bytes, bytes, hipMemcpyHostToDevice, st));
+    AVSE_HIP_CHECK(hipEventRecord(s->staged[i], st));
+    s->staged_used[i] = true;
+    s->slot = (i + 1) % avse_stream::SLOTS;
+    return 0;
+}
+
+// The work of a per-stream push: stream b receives n_new[b] samples and v_new[b] video slices and is closed when
+// flush && flush[b].  host_n_out / host_k_new: per stream, nullable; host_max_out: nullable, the largest n_out.
+int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample_off, const int64_t* n_new, const void* video,
+                     const int64_t* v_new, const uint8_t* flush, const float* vmean, const float* vstd, float* out,
+                     int64_t out_stride, int64_t* host_n_out, int64_t* host_max_out, float* mel_db, float* pred_db,
+                     int64_t* host_k_new, void* stream) {
+    const StreamCfg g{s->n_fft, s->hop, s->spf, s->max_slices};
+    const int B = (int)s->B;
+    StreamRow* rows = s->rows.data();
+    const StreamPlan p = stream_rows(g, s->st.data(), B, sample_off, n_new, v_new, flush, out != nullptr, out_stride, rows);
+    if (p.status != STREAM_OK)
+        return fail(AVSE_ERR_INVALID, "stream " + std::to_string(p.bad) + ": " + stream_message(p.status));
+    int64_t fed = 0;
+    for (int b = 0; b < B; ++b) fed += rows[b].n_new - rows[b].n_old;
+    if ((fed > 0 && (!samples || !sample_off)) || (p.video_total > 0 && !video)) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (p.video_total > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (p.any) {
+        if (int rc = not_capturing(st, "a per-stream push cannot be captured into a graph")) return rc;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (host_n_out) host_n_out[b] = rows[b].n_out;
+        if (host_k_new) host_k_new[b] = rows[b].k_new;
+    }
+    if (host_max_out) *host_max_out = p.max_n_out;
+    if (!p.any) return 0;
+    AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
+    // the tables: rows, then the four item tables, in one copy
+    char* host = nullptr;
+    if (int rc = stream_stage_acquire(s, &host)) return rc;
+    const size_t row_bytes = sizeof(StreamRow) * (size_t)B;
+    std::memcpy(host, rows, row_bytes);
+    StreamItem* h_spec = reinterpret_cast<StreamItem*>(host + row_bytes);
+    StreamItem* h_route = h_spec + p.items.spec;
+    StreamItem* h_synth = h_route + p.items.route;
+    StreamItem* h_ola = h_synth + p.items.synth;
+    stream_fill_items(g, rows, B, h_spec, h_route, h_synth, h_ola);
+    if (int rc = stream_stage_upload(s, row_bytes + sizeof(StreamItem) * (size_t)p.items.total(), st)) return rc;
+    const StreamRow* d_rows = reinterpret_cast<const StreamRow*>(s->tables.p.get());
+    const StreamItem* d_spec = reinterpret_cast<const StreamItem*>(s->tables + row_bytes);
+    const StreamItem* d_route = d_spec + p.items.spec;
+    const StreamItem* d_synth = d_route + p.items.route;
+    const StreamItem* d_ola = d_synth + p.items.synth;
+    // from here on a failure leaves the device state half updated: the session is broken until reset
+    auto run = [&]() -> int {
+        if (p.items.spec > 0) {
+            SpecStreamArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.tail_in = s->tail;                          // copies 0 / 1: the kernel picks by the row's parity
+            a.tail_out = s->tail + (size_t)B * TAIL;
+            a.news = samples; a.news_stride = 0;          // + the row's sample_off
+            a.spf = s->spf; a.R = s->R; a.RS = s->RS;
+            a.twiddle = s->spec.twiddle; a.window = s->spec.window;
+            a.mel_start = s->spec.mel.start; a.mel_weight = s->spec.mel.weight;
+            std::memcpy(a.nq, s->spec.mel.seg_nq, sizeof(a.nq));
+            a.amin = s->amin; a.db_floor = s->db_floor;
+            a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
+            hipLaunchKernelGGL(k_stream_spec_each, dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st, a, d_rows, d_spec);
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.items.route > 0) {
+            RouteArgs r;
+            std::memset(&r, 0, sizeof(r));
+            r.mel_ring = s->mel_ring; r.fmax_ring = s->fmax_ring; r.run_max = s->run_max;
+            r.net_in = s->net_in; r.mel_out = mel_db;
+            r.spf = s->spf; r.R = s->R; r.RS = s->RS; r.top_db = s->top_db;
+            r.vnew = reinterpret_cast<const char*>(video); r.vq = s->vq; r.vstage = s->vstage;
+            r.vbytes = (long long)s->vbytes;
+            r.RV = s->RV; r.B = B;
+            r.vec16 = (reinterpret_cast<uintptr_t>(video) & 15) == 0;
+            hipLaunchKernelGGL(k_stream_route_each, dim3((unsigned)p.items.route), dim3(256), 0, st, r, d_rows, d_route);
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.clips > 0) {
+            if (int rc = avse_forward_video(s->ctx, s->w, s->net_in, s->vstage, s->vdt, vmean, vstd, p.clips, s->pred, stream))
+                return rc;
+            if (pred_db)
+                AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)p.clips * NMEL * s->spf,
+                                              hipMemcpyDeviceToDevice, st));
+            IstftArgs ia;
+            std::memset(&ia, 0, sizeof(ia));
+            ia.mel_db = s->pred; ia.spf = s->spf;
+            ia.n_utt = B; ia.nb = 321; ia.N = 640; ia.hop = s->hop; ia.n_mels = s->n_mels;
+            ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
+            SynthArgs sa;
+            sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
+            sa.T0 = 0; sa.nt = 0; sa.R = s->R;
+            hipLaunchKernelGGL(k_stream_synth_each, dim3((unsigned)p.items.synth), dim3(64), 0, st, ia, sa, d_rows, d_synth);
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.items.ola > 0) {
+            OlaArgs o;
+            o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
+            o.e_old = 0; o.T = 0; o.n_out = 0; o.R = s->R;
+            hipLaunchKernelGGL(k_stream_ola_each, dim3((unsigned)p.items.ola), dim3(256), 0, st, o, d_rows, d_ola);
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        return 0;
+    };
+    if (int rc = run()) {
+        s->broken = true;
+        return rc;
+    }
+    stream_commit(rows, B, s->st.data());
+    stream_refresh_uniform(s);
+    return debug_poll(stream);
+}
+
+// a lock-step call on streams that are not in lock step: the per-stream step with the same counts for every stream
+int stream_step_spread(avse_stream* s, bool flush, const float* samples, int64_t n_new, int64_t sample_stride,
+                       const void* video, int64_t v_new, const float* vmean, const float* vstd, float* out,
+                       int64_t out_stride, int64_t* host_n_out, float* mel_db, float* pred_db, void* stream) {
+    bool open = false;
+    for (int64_t b = 0; b < s->B; ++b) {
+        s->arg_n[b] = n_new;
+        s->arg_v[b] = v_new;
+        s->arg_off[b] = b * sample_stride;
+        s->arg_flush[b] = flush && !s->st[b].flushed;
+        open = open || !s->st[b].flushed;
+    }
+    if (flush && !open) return fail(AVSE_ERR_INVALID, "flush after flush: only avse_stream_reset is legal");
+    return stream_step_each(s, samples, s->arg_off.data(), s->arg_n.data(), video, s->arg_v.data(), s->arg_flush.data(), vmean,
+                            vstd, out, out_stride, nullptr, host_n_out, mel_db, pred_db, nullptr, stream);
 }
 
 // The work of a push (n_new samples, v_new video slices) or of a flush (the remaining frames of the closed signal).
@@ -471,6 +604,7 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
     s->n = n2;
     s->v = v2;
     if (flush) s->flushed = true;
+    stream_set_all(s);
     return debug_poll(stream);
 }
 
@@ -523,6 +657,19 @@ int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, in
         s->phase_ring.alloc(sizeof(float2) * B * s->R * 321) != hipSuccess ||
         s->vq.alloc(B * s->RV * s->vbytes) != hipSuccess || s->vstage.alloc(clips * s->vbytes) != hipSuccess)
         return fail(AVSE_ERR_OOM, "hipMalloc failed (stream session)");
+    // per-stream calls: host rows, and the worst-case tables of one call (stream_geom.h stream_item_caps) on the device
+    // and in each slot of the pinned staging ring, so that no push allocates
+    s->st.assign(B, StreamState{0, 0, 0, 0});
+    s->rows.resize(B);
+    s->arg_n.resize(B); s->arg_v.resize(B); s->arg_off.resize(B); s->arg_flush.resize(B);
+    const StreamItemCounts per_stream = stream_item_caps(StreamCfg{n_fft, hop, frames_per_slice, max_slices});
+    s->cap.spec = per_stream.spec * n_streams; s->cap.route = per_stream.route * n_streams;
+    s->cap.synth = per_stream.synth * n_streams; s->cap.ola = per_stream.ola * n_streams;
+    s->slot_bytes = (sizeof(StreamRow) * B + sizeof(StreamItem) * (size_t)s->cap.total() + 255) & ~(size_t)255;
+    if (s->tables.alloc(s->slot_bytes) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (stream session)");
+    if (s->staging.alloc(s->slot_bytes * avse_stream::SLOTS) != hipSuccess)
+        return fail(AVSE_ERR_OOM, "hipHostMalloc failed (stream session)");
+    for (hipEvent_t& e : s->staged) AVSE_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     // a slot read before its first write holds zeros, never stale memory
     AVSE_HIP_CHECK(hipMemset(s->frame_ring, 0, s->frame_ring.bytes));
     AVSE_HIP_CHECK(hipMemset(s->phase_ring, 0, s->phase_ring.bytes));
@@ -557,6 +704,9 @@ int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_
     if (n_new > 0 && sample_stride < n_new) return fail(AVSE_ERR_INVALID, "sample_stride below n_new");
     if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
     if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
+    if (!s->uniform)
+        return stream_step_spread(s, false, samples, n_new, sample_stride, video, v_new, vmean, vstd, out, out_stride,
+                                  host_n_out, mel_db, pred_db, stream);
     if (s->flushed) return fail(AVSE_ERR_INVALID, "push after flush: only avse_stream_reset is legal");
     if (v_new > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
     if (n_new > (1LL << 40) - s->n || v_new > (1LL << 30) - s->v) return fail(AVSE_ERR_INVALID, "counts too large");
@@ -570,14 +720,65 @@ int avse_stream_flush(avse_stream* s, const float* vmean, const float* vstd, flo
     if (out_stride < 0) return fail(AVSE_ERR_INVALID, "negative counts");
     if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
     if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
+    if (!s->uniform)
+        return stream_step_spread(s, true, nullptr, 0, 0, nullptr, 0, vmean, vstd, out, out_stride, host_n_out, mel_db, pred_db,
+                                  stream);
     if (s->flushed) return fail(AVSE_ERR_INVALID, "flush after flush: only avse_stream_reset is legal");
     return stream_step(s, true, nullptr, 0, 0, nullptr, 0, vmean, vstd, out, out_stride, host_n_out, mel_db, pred_db, stream);
+}
+
+int avse_stream_push_each(avse_stream* s, const float* samples, const int64_t* sample_off, const int64_t* n_new,
+                          const void* video, const int64_t* v_new, const uint8_t* flush, const float* vmean,
+                          const float* vstd, float* out, int64_t out_stride, int64_t* host_n_out, float* mel_db,
+                          float* pred_db, int64_t* host_k_new, void* stream) {
+    if (!s || !n_new || !v_new || !host_n_out) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (out_stride < 0) return fail(AVSE_ERR_INVALID, "negative counts");
+    if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
+    if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
+    return stream_step_each(s, samples, sample_off, n_new, video, v_new, flush, vmean, vstd, out, out_stride, host_n_out,
+                            nullptr, mel_db, pred_db, host_k_new, stream);
 }
 
 int avse_stream_reset(avse_stream* s, void* stream) {
     if (!s) return fail(AVSE_ERR_INVALID, "NULL argument");
     AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
     return stream_init_state(s, (hipStream_t)stream);
+}
+
+int avse_stream_reset_each(avse_stream* s, const uint8_t* which, void* stream) {
+    if (!s || !which) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
+    const int B = (int)s->B;
+    int n = 0;
+    for (int b = 0; b < B; ++b) n += which[b] != 0;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = not_capturing(st, "a per-stream reset cannot be captured into a graph")) return rc;
+    AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
+    char* host = nullptr;
+    if (int rc = stream_stage_acquire(s, &host)) return rc;
+    int* ids = reinterpret_cast<int*>(host);
+    n = 0;
+    for (int b = 0; b < B; ++b)
+        if (which[b]) ids[n++] = b;
+    if (int rc = stream_stage_upload(s, sizeof(int) * (size_t)n, st)) return rc;
+    hipLaunchKernelGGL(k_stream_reset_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(),
+                       reinterpret_cast<const int*>(s->tables.p.get()), B);
+    AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
+    for (int b = 0; b < B; ++b)
+        if (which[b]) s->st[b] = StreamState{0, 0, 0, 0};
+    stream_refresh_uniform(s);
+    return debug_poll(stream);
+}
+
+int avse_stream_state(const avse_stream* s, int64_t* n_samples, int64_t* n_video, uint8_t* flushed) {
+    if (!s) return fail(AVSE_ERR_INVALID, "NULL argument");
+    for (int64_t b = 0; b < s->B; ++b) {
+        if (n_samples) n_samples[b] = s->st[b].n;
+        if (n_video) n_video[b] = s->st[b].v;
+        if (flushed) flushed[b] = s->st[b].flushed;
+    }
+    return 0;
 }
 
 void avse_stream_destroy(avse_stream* s) {

@@ -767,14 +767,28 @@ def stream_counts(n_samples, n_video_slices, flushed=False, session=None):
 
 
 class StreamSession:
-    """avse_stream: the device state of n_streams lock-step streams (stream_create); n / v are the host totals."""
+    """avse_stream: the device state of n_streams streams (stream_create).  ns / vs / fl are the host totals per stream
+    (samples, video slices, flushed), mirroring the library's counters; n / v / flushed are the same as scalars, valid
+    while the streams are in step (the lock-step calls keep them so; stream_push_each may not)."""
 
     def __init__(self, weights, handle, n_streams, spf, video_dtype, max_slices):
         self.weights, self.handle = weights, handle      # the weights (and their context) outlive the session
         self.n_streams, self.spf, self.video_dtype, self.max_slices = n_streams, spf, video_dtype, max_slices
-        self.n = self.v = 0
-        self.flushed = False
+        self.ns, self.vs, self.fl = [0] * n_streams, [0] * n_streams, [False] * n_streams
         self._cdll = _lib.load()
+
+    @property
+    def in_step(self):
+        return len(set(zip(self.ns, self.vs, self.fl))) == 1
+
+    def _common(self, values, name):
+        if not self.in_step:
+            raise RuntimeError(f"StreamSession.{name}: the streams are not in step; read the per-stream lists ns / vs / fl")
+        return values[0]
+
+    n = property(lambda self: self._common(self.ns, "n"))
+    v = property(lambda self: self._common(self.vs, "v"))
+    flushed = property(lambda self: self._common(self.fl, "flushed"))
 
     def __del__(self):
         h, lib = getattr(self, "handle", None), getattr(self, "_cdll", None)
@@ -831,15 +845,25 @@ def _stream_call(sess, flush, samples, video, vnorm_mean, vnorm_std, return_spec
     # what the call will emit, from the host totals (the library keeps no getter for them: n / v mirror its counters).
     # A flush with n > slice * v is refused here by avse_stream_counts, as the library would; a call on a flushed
     # session emits nothing and is left to the library to refuse.
-    _, k0, e0 = stream_counts(sess.n, sess.v, sess.flushed, sess)
-    k1, e1 = k0, e0
-    if not sess.flushed:
-        _, k1, e1 = stream_counts(sess.n + n_new, sess.v + v_new, flush, sess)
-    n_out, k_new = e1 - e0, k1 - k0
+    in_step = sess.in_step
+    if not in_step:
+        # the streams' counters differ (stream_push_each): the library runs the per-stream step with these counts for
+        # every stream, reports the largest count and packs the spectrograms; the results come back per stream
+        todo = [flush and not f for f in sess.fl]
+        ks, es = _stream_expect(sess, [n_new] * B, [v_new] * B, todo)
+        n_out, k_new = max(es), sum(ks)
+        mel_shape = (k_new, 80, sess.spf)
+    else:
+        _, k0, e0 = stream_counts(sess.n, sess.v, sess.flushed, sess)
+        k1, e1 = k0, e0
+        if not sess.flushed:
+            _, k1, e1 = stream_counts(sess.n + n_new, sess.v + v_new, flush, sess)
+        n_out, k_new = e1 - e0, k1 - k0
+        mel_shape = (B, k_new, 80, sess.spf)
     out = torch.empty((B, n_out), dtype=torch.float32, device=dev)
     mel = pred = None
     if return_spectrograms:
-        mel = torch.empty((B, k_new, 80, sess.spf), dtype=torch.float32, device=dev)
+        mel = torch.empty(mel_shape, dtype=torch.float32, device=dev)
         pred = torch.empty_like(mel)
     got = ctypes.c_int64()
     lib = _lib.load()
@@ -854,16 +878,145 @@ def _stream_call(sess, flush, samples, video, vnorm_mean, vnorm_std, return_spec
     _lib.check(rc, "avse_stream_flush" if flush else "avse_stream_push")
     if got.value != n_out:
         raise _lib.AvseError(f"the session emitted {got.value} samples, the host totals give {n_out}")
-    sess.n += n_new
-    sess.v += v_new
-    sess.flushed = sess.flushed or flush
+    for b in range(B):
+        sess.ns[b] += n_new
+        sess.vs[b] += v_new
+        sess.fl[b] = sess.fl[b] or flush
+    if not in_step:
+        return _stream_split(out, mel, pred, ks, es, return_spectrograms)
     return (out, mel, pred) if return_spectrograms else out
+
+
+def _stream_expect(sess, n_new, v_new, flush):
+    """Per stream, what a call with these per-stream counts completes and emits: (slices [B], samples [B]), from the host
+    totals.  A flush with n > slice * v is refused here by avse_stream_counts, as the library would; input for a flushed
+    stream emits nothing and is left to the library to refuse."""
+    ks, es = [], []
+    for b in range(sess.n_streams):
+        _, k0, e0 = stream_counts(sess.ns[b], sess.vs[b], sess.fl[b], sess)
+        k1, e1 = k0, e0
+        if not sess.fl[b]:
+            _, k1, e1 = stream_counts(sess.ns[b] + n_new[b], sess.vs[b] + v_new[b], flush[b], sess)
+        ks.append(k1 - k0)
+        es.append(e1 - e0)
+    return ks, es
+
+
+def _stream_split(out, mel, pred, ks, es, return_spectrograms):
+    """[B, max n_out] and the packed [sum k, 80, spf] spectrograms of a per-stream step -> per-stream lists."""
+    outs = [out[b, :e] for b, e in enumerate(es)]
+    if not return_spectrograms:
+        return outs
+    first = np.concatenate([[0], np.cumsum(ks)]).astype(int)
+    return (outs, [mel[first[b]:first[b + 1]] for b in range(len(ks))],
+            [pred[first[b]:first[b + 1]] for b in range(len(ks))])
+
+
+def _host_i64(values):
+    a = np.ascontiguousarray(values, dtype=np.int64)
+    return a, ctypes.c_void_p(a.ctypes.data)
+
+
+def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=None, vnorm_std=None,
+                     return_spectrograms=False):
+    """avse_stream_push_each: every stream moves by its own amount.  samples: a list of B 1-D float32 device tensors
+    (None or empty for a stream without new samples), video: a list of B [v, 128, 128, F] tensors in the session's dtype
+    (None for a stream without new video), flush: a list of B bools (streams to close as stream_flush does); any of the
+    three may be None as a whole.  The inputs are packed on the device (one torch.cat each).
+    -> a list of B 1-D tensors, stream b's newly final samples; with return_spectrograms also two lists of [k_b, 80, spf]
+    tensors, the slices the network saw and predicted for the k_b slices stream b completed in this call.  Asynchronous
+    on torch's current stream; a stream without input or flush launches no blocks."""
+    w = session.weights
+    dev = torch.device("cuda", w.ctx.device_index)
+    B = session.n_streams
+    samples = [None] * B if samples is None else list(samples)
+    video = [None] * B if video is None else list(video)
+    flush = [False] * B if flush is None else [bool(f) for f in flush]
+    if not (len(samples) == len(video) == len(flush) == B):
+        raise ValueError(f"samples, video and flush must have one entry per stream ({B})")
+    n_new, v_new, s_parts, v_parts = [], [], [], []
+    for b in range(B):
+        x, vid = samples[b], video[b]
+        if x is not None and x.numel():
+            _dev_f32(x, f"samples[{b}]")
+            if x.dim() != 1:
+                raise ValueError(f"samples[{b}] must be 1-D")
+            s_parts.append(x)
+        n_new.append(0 if x is None else int(x.numel()))
+        if vid is not None and vid.shape[0]:
+            if _dev_video(vid, f"video[{b}]", (128, 128, w.F)) != session.video_dtype:
+                raise TypeError(f"video[{b}] is {vid.dtype}, the session was created for the other video dtype")
+            if vid.dim() != 4:
+                raise ValueError(f"video[{b}] must be [v, 128, 128, {w.F}]")
+            v_parts.append(vid)
+        v_new.append(0 if vid is None else int(vid.shape[0]))
+    if (vnorm_mean is None) != (vnorm_std is None):
+        raise ValueError("vnorm_mean and vnorm_std must both be given")
+    if vnorm_mean is not None:
+        _dev_f32(vnorm_mean, "vnorm_mean", (128, 128))
+        _dev_f32(vnorm_std, "vnorm_std", (128, 128))
+    for t in s_parts + v_parts + [vnorm_mean, vnorm_std]:
+        if t is not None and t.device.index != dev.index:
+            raise ValueError(f"the session lives on {dev} but an argument is on {t.device}")
+    ks, es = _stream_expect(session, n_new, v_new, flush)
+    packed = torch.cat(s_parts) if s_parts else None
+    vpacked = torch.cat(v_parts) if v_parts else None
+    off = np.concatenate([[0], np.cumsum(n_new)[:-1]])
+    out = torch.empty((B, max(es)), dtype=torch.float32, device=dev)
+    mel = pred = None
+    if return_spectrograms:
+        mel = torch.empty((sum(ks), 80, session.spf), dtype=torch.float32, device=dev)
+        pred = torch.empty_like(mel)
+    (_off, p_off), (_n, p_n), (_v, p_v) = _host_i64(off), _host_i64(n_new), _host_i64(v_new)
+    fl = np.ascontiguousarray(flush, dtype=np.uint8)
+    got, got_k = np.full(B, -1, np.int64), np.full(B, -1, np.int64)
+    with torch.cuda.device(dev):
+        rc = _lib.load().avse_stream_push_each(
+            session.handle, _lib.ptr(packed), p_off, p_n, _lib.ptr(vpacked), p_v, ctypes.c_void_p(fl.ctypes.data),
+            _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), _lib.ptr(out), int(out.shape[1]), ctypes.c_void_p(got.ctypes.data),
+            _lib.ptr(mel), _lib.ptr(pred), ctypes.c_void_p(got_k.ctypes.data), _lib.stream_handle(dev))
+    _lib.check(rc, "avse_stream_push_each")
+    if got.tolist() != es or got_k.tolist() != ks:
+        raise _lib.AvseError(f"the session emitted {got.tolist()} samples of {got_k.tolist()} slices, the host totals "
+                             f"give {es} of {ks}")
+    for b in range(B):
+        session.ns[b] += n_new[b]
+        session.vs[b] += v_new[b]
+        session.fl[b] = session.fl[b] or flush[b]
+    return _stream_split(out, mel, pred, ks, es, return_spectrograms)
+
+
+def stream_reset_each(session, streams):
+    """avse_stream_reset_each: the listed streams go back to the state after stream_create (their slots are free for new
+    callers), ordered on torch's current stream; the others are untouched."""
+    which = np.zeros(session.n_streams, np.uint8)
+    for b in streams:
+        if not 0 <= int(b) < session.n_streams:
+            raise ValueError(f"no stream {b} in a session of {session.n_streams}")
+        which[int(b)] = 1
+    dev = torch.device("cuda", session.weights.ctx.device_index)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_stream_reset_each(session.handle, ctypes.c_void_p(which.ctypes.data),
+                                                      _lib.stream_handle(dev)), "avse_stream_reset_each")
+    for b in np.flatnonzero(which):
+        session.ns[b], session.vs[b], session.fl[b] = 0, 0, False
+
+
+def stream_state(session):
+    """avse_stream_state: the library's per-stream totals -> (samples [B], video slices [B], flushed [B]) as lists."""
+    B = session.n_streams
+    n, v, f = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.uint8)
+    _lib.check(_lib.load().avse_stream_state(session.handle, ctypes.c_void_p(n.ctypes.data), ctypes.c_void_p(v.ctypes.data),
+                                             ctypes.c_void_p(f.ctypes.data)), "avse_stream_state")
+    return n.tolist(), v.tolist(), [bool(x) for x in f]
 
 
 def stream_push(session, samples=None, video=None, vnorm_mean=None, vnorm_std=None, return_spectrograms=False):
     """avse_stream_push: samples [B, n] float32 (or None), video [B, v, 128, 128, F] in the session's dtype (or None)
     -> the [B, n_out] samples that became final; with return_spectrograms also the [B, k, 80, spf] slices the network saw
-    and predicted for the k slices this call completed.  Asynchronous on torch's current stream."""
+    and predicted for the k slices this call completed.  Asynchronous on torch's current stream.
+    On a session whose streams are not in step (after stream_push_each) every stream still receives these counts, and
+    the results come back per stream as from stream_push_each: lists of B tensors."""
     return _stream_call(session, False, samples, video, vnorm_mean, vnorm_std, return_spectrograms)
 
 
@@ -878,8 +1031,8 @@ def stream_reset(session):
     dev = torch.device("cuda", session.weights.ctx.device_index)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().avse_stream_reset(session.handle, _lib.stream_handle(dev)), "avse_stream_reset")
-    session.n = session.v = 0
-    session.flushed = False
+    B = session.n_streams
+    session.ns, session.vs, session.fl = [0] * B, [0] * B, [False] * B
 
 
 class Trainer:

@@ -160,8 +160,9 @@ class Enhancer:
 
 
 class StreamEnhancer:
-    """Enhancement of audio as it arrives: `n_streams` lock-step streams, e.g. the participants of
-    one call, pushed in chunks of any size.
+    """Enhancement of audio as it arrives: `n_streams` streams pushed in chunks of any size, in lock
+    step (push / flush: e.g. the participants of one call) or each at its own pace (push_each / open / close: the
+    callers of a service).
 
     The reference's predict loop needs the whole utterance (the reflect padding of both ends, the top_db floor from
     the utterance's maximum, the window sum of the finished signal).  A session carries the sample tail, the running
@@ -184,6 +185,7 @@ class StreamEnhancer:
                                          hop_length=g["hop_length"], frames_per_slice=spf, n_mels=data_processor.N_MELS,
                                          fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX,
                                          video_dtype=video_dtype, max_slices=max_slices)
+        self._busy = set()      # slots handed out by open()
 
     def push(self, samples, video=None, vmean=None, vstd=None, return_spectrograms=False):
         """samples [B, n] float32 (int16-scale), video [B, v, 128, 128, F] float32 or uint8 (the session's dtype) or
@@ -197,13 +199,46 @@ class StreamEnhancer:
 
     def reset(self):
         ops.stream_reset(self.session)
+        self._busy = set()
+
+    # ---- independent streams: the slots of one session serve callers that never move together ----
+    def push_each(self, samples=None, video=None, flush=None, vmean=None, vstd=None, return_spectrograms=False):
+        """Every stream by its own amount (ops.stream_push_each): samples / video are lists with one tensor (1-D float32;
+        [v, 128, 128, F]) or None per stream, flush a list of bools -> per-stream lists of what push returns.  A stream
+        without input costs nothing; each stream's output is, bit for bit, that of a session of its own."""
+        return ops.stream_push_each(self.session, samples, video, flush, vmean, vstd, return_spectrograms)
+
+    def reset_streams(self, ids):
+        """The listed streams back to the state after construction; the others keep streaming."""
+        ops.stream_reset_each(self.session, ids)
+
+    def open(self):
+        """-> a free slot (the lowest stream no caller holds) for a caller that joins; close() gives it back."""
+        for b in range(self.session.n_streams):
+            if b not in self._busy:
+                self._busy.add(b)
+                return b
+        raise RuntimeError(f"all {self.session.n_streams} streams of the session are in use")
+
+    def close(self, slot, vmean=None, vstd=None):
+        """A caller hangs up: flushes the slot, resets it and frees it -> its last samples (1-D)."""
+        flush = [b == slot for b in range(self.session.n_streams)]
+        last = self.push_each(flush=flush, vmean=vmean, vstd=vstd)[slot]
+        self.reset_streams([slot])
+        self._busy.discard(slot)
+        return last
 
     @property
     def counts(self):
-        """Host totals: dict(samples, video_slices, frames, slices, emitted)."""
+        """Host totals: dict(samples, video_slices, frames, slices, emitted) while the streams are in step, else the
+        same keys with one list entry per stream."""
         s = self.session
-        f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
-        return dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+        if s.in_step:
+            f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
+            return dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+        rows = [ops.stream_counts(n, v, fl, s) for n, v, fl in zip(s.ns, s.vs, s.fl)]
+        return dict(samples=list(s.ns), video_slices=list(s.vs), frames=[r[0] for r in rows],
+                    slices=[r[1] for r in rows], emitted=[r[2] for r in rows])
 
     @property
     def range_bits(self):

@@ -34,7 +34,8 @@ extern "C" {
  *    exponents (avse_weights_act_exponents, option no_act_scale); later additions under the same version (new symbols
  *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
  *    avse_eval_pairs_sized, avse_eval_pairs_ext, avse_stream_create, avse_stream_counts, avse_stream_push,
- *    avse_stream_flush, avse_stream_reset, avse_stream_destroy */
+ *    avse_stream_flush, avse_stream_reset, avse_stream_destroy, avse_stream_push_each, avse_stream_reset_each,
+ *    avse_stream_state */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -416,9 +417,57 @@ int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_
 int avse_stream_flush(avse_stream* s, const float* vnorm_mean, const float* vnorm_std, float* out, int64_t out_stride,
                       int64_t* host_n_out, float* mel_db /* nullable */, float* pred_db /* nullable */, void* stream);
 
-/* Back to the state after create (no samples, no video, not flushed, not broken), ordered on `stream`. */
+/* Back to the state after create (no samples, no video, not flushed, not broken), ordered on `stream`: every stream. */
 int avse_stream_reset(avse_stream* s, void* stream);
 void avse_stream_destroy(avse_stream* s);
+
+/* ---- independent streams of one session ----
+ * The streams of a session need not move together (callers of a service: packets of different sizes, video late by
+ * different amounts, joining and hanging up at different times).  The session keeps its counters per stream (samples,
+ * video slices, flushed), and every statement in avse_stream_push's comment holds for each stream with that stream's own
+ * totals (n_b, v_b): frame t as soon as its samples are there, slice k at min(frames / spf, v), the causal floor over the
+ * stream's own frames, emitted = max(0, spf H k_done - N/2), the flush rule n <= slice * v.  The network runs once per
+ * call on the slices all streams completed together, and is batch-invariant, so each stream's output is, bit for bit,
+ * that of a session of its own fed the same way.
+ *
+ * Per-stream form of avse_stream_push / avse_stream_flush: stream b receives n_new[b] samples and v_new[b] video
+ * slices (either or both may be 0: an idle stream costs no blocks), and is closed as by avse_stream_flush when
+ * flush && flush[b].
+ *   samples     stream b's n_new[b] samples start at samples + sample_off[b] (floats; as avse_spectrogram_ragged's
+ *               sig_off); both NULL only when every n_new is 0
+ *   video       packed, stream-major: v_new[0] slices of stream 0, then v_new[1] of stream 1, ..; 4-byte aligned
+ *   out         [n_streams][out_stride]: row b receives host_n_out[b] samples
+ *   host_n_out  HOST [n_streams]: the samples appended per stream
+ *   mel_db, pred_db   nullable, packed [sum of host_k_new][n_mels][spf], stream-major
+ *   host_k_new  HOST [n_streams], nullable: the slices each stream completed in this call
+ * Refused with AVSE_ERR_INVALID before any GPU work, the session left exactly as it was, with a message that names the
+ * first offending stream ("stream 3: ..."), when any stream would complete more than max_slices slices, leave more than
+ * max_slices slices of either input queued ahead of the other, be pushed (or flushed again) after its flush, be flushed
+ * with n > slice * v, or emit more than out_stride; negative counts and NULL where not nullable as avse_stream_push.
+ * A failure after launches have begun marks the session broken, as there.
+ * The call allocates nothing: its per-stream rows and block tables (sized at create for the worst case) go up in one
+ * copy from a ring of four pinned staging slots, and the call waits on the host only when the slot it is about to
+ * overwrite has not been read yet, i.e. when four per-stream calls are still queued; otherwise it does not synchronise.
+ * Not capturable into a graph.
+ *
+ * The lock-step calls keep their meaning: while every stream has the same counters they run exactly what they ran
+ * before.  Once the counters differ, avse_stream_push is avse_stream_push_each with the same n_new / v_new for every
+ * stream (samples and video as laid out for avse_stream_push), avse_stream_flush flushes every stream not yet flushed,
+ * and both write the LARGEST per-stream count to *host_n_out (row b of `out` receives stream b's own count, which
+ * avse_stream_state and avse_stream_counts give) and lay mel_db / pred_db out packed as above. */
+int avse_stream_push_each(avse_stream* s,
+        const float* samples, const int64_t* sample_off /* HOST [B] */, const int64_t* n_new /* HOST [B] */,
+        const void* video, const int64_t* v_new /* HOST [B] */, const uint8_t* flush /* HOST [B], nullable */,
+        const float* vnorm_mean, const float* vnorm_std,
+        float* out, int64_t out_stride, int64_t* host_n_out /* HOST [B] */,
+        float* mel_db /* nullable */, float* pred_db /* nullable */, int64_t* host_k_new /* HOST [B], nullable */,
+        void* stream);
+/* Streams with which[b] != 0 go back to the state after create (a caller left, the slot is free for the next one):
+ * counters 0, not flushed, sample tail zero, running maximum -inf.  Ordered on `stream`; the other streams are
+ * untouched.  Uses a staging slot as avse_stream_push_each does.  A broken session needs avse_stream_reset. */
+int avse_stream_reset_each(avse_stream* s, const uint8_t* which /* HOST [B] */, void* stream);
+/* HOST: per-stream totals (samples, video slices, flushed) of the session, [n_streams] each; any output nullable. */
+int avse_stream_state(const avse_stream* s, int64_t* n_samples, int64_t* n_video, uint8_t* flushed);
 
 /* VideoNormalizer.normalize (data_processor.py:208-212), in place on device (float32 only: uint8 video takes the
  * normaliser fused into the forward, vnorm_mean / vnorm_std):
