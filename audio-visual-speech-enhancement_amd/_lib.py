@@ -126,6 +126,8 @@ SIGNATURES = {
                                      _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "avse_stream_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
     "avse_stream_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    # host only: supported(sr, n_fft, hop, spf, n_mels, fmin, fmax) -> 0 or the status stream_create would return
+    "avse_stream_supported": (_int, [_int, _int, _int, _int, _int, _flt, _flt]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

@@ -8,14 +8,15 @@
 //
 // State of a session (all on the device, sized at create; the counters that address it live on the host and are
 // functions of the call arguments alone, so no call reads anything back):
-//   tail        [2][B][640]           the last 640 samples of each stream; the analysis kernel reads one copy and writes
-//                                     the other (the copies swap per push: no block reads what another block writes)
+//   tail        [2][B][N]             the last N = n_fft samples of each stream (640; 1280 / 1920 at 32 / 48 kHz); the
+//                                     analysis kernel reads one copy and writes the other (the copies swap per push:
+//                                     no block reads what another block writes)
 //   mel ring    [B][RS][80][spf]      unclamped mel-dB of slice k in slot k % RS; a partial slice simply waits there
 //   max ring    [B][R]                each frame's maximum over its 80 bands (plain stores), slot t % R
 //   phase ring  [B][R][321] complex   the mixture's STFT of frame t, kept until its slice has been inverted
 //   run max     [B]                   maximum of the unclamped mel-dB of every frame of every slice completed so far
 //   video queue [B][RV] slices        video that arrived ahead of its samples, slot k % RV
-//   frame ring  [B][R][640]           windowed time frames of inverted frames; the last three are the overlap-add tail
+//   frame ring  [B][R][N]             windowed time frames of inverted frames; the last three are the overlap-add tail
 // R = spf (2 max_slices + 1), RS = R / spf, RV = 2 max_slices: a push may complete max_slices slices and leave
 // max_slices queued (avse_stream_push refuses more), so live entries never share a slot.
 //
@@ -35,6 +36,10 @@
 // k_stream_spec_each / _route_each / _synth_each / _ola_each run the bodies of the four kernels above with the row's
 // counters in place of the call's scalars; the forward runs once on the slices all streams completed.  The lock-step
 // calls run the lock-step kernels while every stream's counters are equal.
+//
+// 32 and 48 kHz (n_fft = 640 P, P = 2, 3): k_stream_spec_p<P> / k_stream_synth_p<P> compute each frame as P interleaved
+// 640-point frames (frame_poly.h), k_stream_ola_n / k_stream_reset_n_each take N and hop as arguments, k_stream_route and
+// the forward are shared; the kernels above stay, instruction for instruction, what they are (tools/isa_diff.py).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -42,6 +47,8 @@
 
 #include "ctx.h"
 #include "frame640.h"
+#include "frame_poly.h"
+#include "spec_tables.h"
 #include "stream_geom.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap (as stft.hip)
@@ -124,6 +131,160 @@ __global__ __launch_bounds__(64 * SWAVES) AVSE_WPE4 void k_stream_spec_each(Spec
 #define STREAM_BODY_SPEC
 #include "stream_body.inc"
 #undef STREAM_BODY_SPEC
+}
+
+// ---- 32 and 48 kHz: frames of N = 640 P samples, P phases on the 640-point arithmetic (frame_poly.h) ----
+// The tail holds N samples per stream and a frame starts at sample P (160 t - 320); the rings, the mel tables and
+// everything after the analysis are the 16 kHz session's (the band-limited bins 0 .. 320 are the same 25-Hz bins).
+template <int N>
+__device__ __forceinline__ float stream_sample_n(const SpecStreamArgs& a, int b, long long i) {
+    if (i >= a.n_old) return a.news[b * a.news_stride + (i - a.n_old)];
+    const long long j = i - (a.n_old - N);
+    return a.tail_in[b * (long long)N + (j > 0 ? j : 0)];
+}
+template <int N>
+__device__ __forceinline__ float frame_sample_n(const SpecStreamArgs& a, int b, long long i) {
+    if (i < 0) i = -i;
+    if (a.Lf >= 0 && i >= a.Lf) i = 2 * (a.Lf - 1) - i;
+    if (i >= a.n_new) return 0.f;
+    return stream_sample_n<N>(a, b, i);
+}
+
+// One analysis block of k_stream_spec for P phases: a.twiddle is W_N^k and a.window the Hann window, both [N].  The
+// phases run one after another through the wave's three LDS frame slots (LDS stays at k_stream_spec's size plus the
+// P - 1 further window phases); X[k] and X[320 - k] of the lane's step-3 items accumulate in registers, and the
+// magnitudes, band dots, dB and frame maxima follow the last phase, as in stream_body.inc.
+template <int P>
+__device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const int b, const unsigned blk) {
+    constexpr int N = 640 * P;
+    __shared__ float2 zbuf[SWAVES * FPG * ZS];
+    __shared__ float2 twl[640];        // W640^k = W_N^{P k}
+    __shared__ v2f ut2[161];           // U = -i W640^k / 2 (untangling)
+    __shared__ float2 winl[P * 320];   // phase r of the window as pairs (frame_poly.h window_pair)
+    __shared__ float4 melw4[NMEL * MW / 4];
+    __shared__ int mel_st[NMEL];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if ((int)blk == a.nblk) {   // the new tail: the last N samples received (zeros before sample 0)
+        for (int j = tid; j < N; j += 64 * SWAVES) {
+            const long long i = a.n_new - N + j;
+            a.tail_out[b * (long long)N + j] = i < 0 ? 0.f : stream_sample_n<N>(a, b, i);
+        }
+        return;
+    }
+    for (int i = tid; i < 640; i += 64 * SWAVES) twl[i] = a.twiddle[P * i];
+    for (int k = tid; k < 161; k += 64 * SWAVES) {
+        const float2 w = a.twiddle[P * k];
+        ut2[k] = v2f{0.5f * w.y, -0.5f * w.x};
+    }
+    for (int i = tid; i < P * 320; i += 64 * SWAVES) winl[i] = spec_poly::window_pair<P>(a.window, i / 320, i % 320);
+    for (int i = tid; i < NMEL * MW / 4; i += 64 * SWAVES) melw4[i] = reinterpret_cast<const float4*>(a.mel_weight)[i];
+    for (int i = tid; i < NMEL; i += 64 * SWAVES) mel_st[i] = a.mel_start[i];
+    __syncthreads();
+
+    const int g = FPG * wave;                                  // this wave's first frame in the block
+    const int nf = min(SCHUNK, a.nt - SCHUNK * (int)blk);
+    const int ng = max(0, min(FPG, nf - g));
+    const long long tw0 = a.t0 + SCHUNK * (long long)blk + g;   // the wave's first frame
+    const int f1 = lane >> 4, n1 = lane & 15;
+    const long long s0 = ((tw0 + f1) * 160 - 320) * P;
+    const bool whole = s0 >= a.n_old && s0 + N <= a.n_new && (a.Lf < 0 || s0 + N <= a.Lf);   // all in this call's samples
+    float2* zw = zbuf + wave * FPG * ZS;
+    v2f ax[spec_poly::IT3], ay[spec_poly::IT3];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        float2 x[20];
+#pragma unroll
+        for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
+        if (f1 < ng) {
+            if (whole)
+                spec_poly::load_phase<P>(x, a.news + b * a.news_stride + (s0 - a.n_old), n1, r);
+            else
+                spec_poly::load_phase<P>(x, [&](long long i) { return frame_sample_n<N>(a, b, i); }, s0, n1, r);
+        }
+        // steps 1 and 2 of the 16 x 20 split on the phase's 640 samples, wave-local
+        v2f v[20];
+        window_frame(v, x, winl + r * 320, n1);
+        if (f1 < ng) dft20_store(v, twl, zw + f1 * ZS, n1);
+        wave_lds_sync();
+        {
+            const int f = lane / 20, k2 = lane - 20 * (lane / 20);
+            const bool act = f < ng;
+            v2f w[16];
+            v2f* zf = reinterpret_cast<v2f*>(zw + min(f, FPG - 1) * ZS);
+            if (act) dft16_load(w, zf, k2);
+            wave_lds_sync();
+            if (act) dft16_store(w, zf, k2);
+        }
+        wave_lds_sync();
+        // step 3 of the phase: W_N^{r k} F_r[k] into the accumulators
+        spec_poly::accumulate<P>(ax, ay, zw, ut2, a.twiddle, r, ng, lane);
+        wave_lds_sync();   // the next phase (or the magnitudes below) overwrites the slots
+    }
+    // ---- the complex frame into the phase ring, its magnitudes into LDS; item = (f, k) ----
+#pragma unroll
+    for (int j = 0; j < spec_poly::IT3; ++j) {
+        const int it = lane + 64 * j;
+        if (it >= ng * 161) break;
+        const int f = it / 161, k = it - 161 * f;
+        float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
+        o[k] = make_float2(ax[j].x, ax[j].y);
+        if (k != 160) o[320 - k] = make_float2(ay[j].x, ay[j].y);
+        float* mf = reinterpret_cast<float*>(zw + f * ZS);
+        mf[k] = pk_abs(ax[j]);
+        mf[320 - k] = pk_abs(ay[j]);
+    }
+    for (int it = lane; it < FPG * MW; it += 64) {   // bins [321, 321 + MW) are read by the padded band dots
+        const int f = it / MW, j = it - MW * f;
+        reinterpret_cast<float*>(zw + f * ZS)[321 + j] = 0.f;
+    }
+    wave_lds_sync();
+    // ---- step 4: Slaney mel + dB, item = (m, f); unclamped, into the frame's slice slot ----
+    float fm0 = -INFINITY, fm1 = -INFINITY, fm2 = -INFINITY;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const int it = lane + 64 * jj;
+        if (it >= FPG * NMEL) break;
+        const int m = __umul24(it, 43691) >> 17, f = it - 3 * m;   // m = it / 3 (it < 240)
+        if (f >= ng) continue;
+        const float* mf = reinterpret_cast<const float*>(zw + f * ZS) + mel_st[m];
+        const float acc = band_dot_nq(melw4 + m * (MW / 4), reinterpret_cast<const v2f*>(mf), a.nq[jj]);
+        const float db = mel_to_db(acc, a.amin, a.db_floor);
+        const long long t = tw0 + f, sl = t / a.spf;
+        a.mel_ring[(((long long)b * a.RS + (int)(sl % a.RS)) * NMEL + m) * a.spf + (int)(t - sl * a.spf)] = db;
+        fm0 = f == 0 ? fmaxf(fm0, db) : fm0;
+        fm1 = f == 1 ? fmaxf(fm1, db) : fm1;
+        fm2 = f == 2 ? fmaxf(fm2, db) : fm2;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        fm0 = fmaxf(fm0, __shfl_xor(fm0, o));
+        fm1 = fmaxf(fm1, __shfl_xor(fm1, o));
+        fm2 = fmaxf(fm2, __shfl_xor(fm2, o));
+    }
+    if (lane < ng) a.fmax_ring[(long long)b * a.R + (int)((tw0 + lane) % a.R)] = lane == 0 ? fm0 : lane == 1 ? fm1 : fm2;
+}
+
+template <int P>
+__global__ __launch_bounds__(64 * SWAVES) void k_stream_spec_p(SpecStreamArgs a) {
+    spec_poly_block<P>(a, blockIdx.y, blockIdx.x);
+}
+
+// Per-stream form, as k_stream_spec_each
+template <int P>
+__global__ __launch_bounds__(64 * SWAVES) void k_stream_spec_p_each(SpecStreamArgs a, const StreamRow* __restrict__ rows,
+                                                                    const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    const float* t0 = a.tail_in;
+    float* t1 = a.tail_out;
+    a.tail_in = r.tail_in ? t1 : t0;
+    a.tail_out = r.tail_in ? const_cast<float*>(t0) : t1;
+    a.news += r.sample_off;
+    a.n_old = r.n_old; a.n_new = r.n_new;
+    a.Lf = r.Lf;
+    a.t0 = r.t0; a.nt = r.nt; a.nblk = r.nblk;
+    spec_poly_block<P>(a, it.b, it.chunk);
 }
 
 struct RouteArgs {
@@ -251,6 +412,35 @@ __global__ __launch_bounds__(64) void k_stream_synth_each(IstftArgs a, SynthArgs
     synth_group(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
 }
 
+// 32 / 48 kHz: synth_group on frame_poly.h's synth_frames (a.N = 640 P; the frame ring's slots hold N samples)
+template <int P, class Clip>
+__device__ __forceinline__ void synth_group_p(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
+    istft_poly::synth_frames<P>(
+        a, min(istft640::FPG, s.nt - t0),
+        [&](int m, int f) {
+            const int t = t0 + f, sl = t / a.spf;
+            return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
+        },
+        [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; },
+        [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * (640 * P); });
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void k_stream_synth_p(IstftArgs a, SynthArgs s) {
+    const int b = blockIdx.y;
+    synth_group_p<P>(a, s, b, blockIdx.x * istft640::FPG, [&](int sl) { return (long long)b * a.n_slices + sl; });
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void k_stream_synth_p_each(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
+                                                            const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    s.T0 = r.k_old * a.spf;
+    s.nt = r.k_new * a.spf;
+    synth_group_p<P>(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
+}
+
 struct OlaArgs {
     const float* frame_ring;
     const float* window;
@@ -267,6 +457,45 @@ __device__ __forceinline__ void ola_out(const OlaArgs& a, const int b, const int
         return a.frame_ring[((long long)b * a.R + (int)(t % a.R)) * 640 + o];
     });
 }
+
+// The overlap-add and the reset for a session's own N and hop (32 / 48 kHz): ola_out / k_stream_reset_each with the
+// session's N, hop and N / 2 in place of 640, 160 and 320.
+__device__ __forceinline__ void ola_out_n(const OlaArgs& a, const int N, const int hop, const int b, const int j) {
+    if (j >= a.n_out) return;
+    const long long p = a.e_old + j + N / 2;   // position in the untrimmed signal
+    a.out[b * a.out_stride + j] = istft640::ola_sample(p, a.T, N, hop, a.window, [&](long long t, int o) {
+        return a.frame_ring[((long long)b * a.R + (int)(t % a.R)) * N + o];
+    });
+}
+__global__ __launch_bounds__(256) void k_stream_ola_n(OlaArgs a, int N, int hop) {
+    ola_out_n(a, N, hop, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_stream_ola_n_each(OlaArgs a, int N, int hop, const StreamRow* __restrict__ rows,
+                                                           const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const StreamRow& r = rows[it.b];
+    a.e_old = r.e_old; a.T = r.T; a.n_out = r.n_out;
+    ola_out_n(a, N, hop, it.b, it.chunk * STREAM_OLA_BLOCK + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_stream_reset_n_each(float* tail, float* run_max, const int* __restrict__ ids, int B,
+                                                             int N) {
+    const int b = ids[blockIdx.x];
+    for (int j = threadIdx.x; j < 2 * N; j += 256) {
+        const int copy = j / N;
+        tail[((long long)copy * B + b) * N + (j - copy * N)] = 0.f;
+    }
+    if (threadIdx.x == 0) run_max[b] = -INFINITY;
+}
+
+// the instances (here, ahead of the 16 kHz kernels below, whose place in the code object stays what it was)
+template __global__ void k_stream_spec_p<2>(SpecStreamArgs);
+template __global__ void k_stream_spec_p<3>(SpecStreamArgs);
+template __global__ void k_stream_spec_p_each<2>(SpecStreamArgs, const StreamRow*, const StreamItem*);
+template __global__ void k_stream_spec_p_each<3>(SpecStreamArgs, const StreamRow*, const StreamItem*);
+template __global__ void k_stream_synth_p<2>(IstftArgs, SynthArgs);
+template __global__ void k_stream_synth_p<3>(IstftArgs, SynthArgs);
+template __global__ void k_stream_synth_p_each<2>(IstftArgs, SynthArgs, const StreamRow*, const StreamItem*);
+template __global__ void k_stream_synth_p_each<3>(IstftArgs, SynthArgs, const StreamRow*, const StreamItem*);
 
 // Per-stream form: item (stream, block of 256 samples)
 __global__ __launch_bounds__(256) void k_stream_ola_each(OlaArgs a, const StreamRow* __restrict__ rows,
@@ -291,6 +520,38 @@ __global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a) {
     ola_out(a, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
 }
 
+// ---- host: the kernel of each launch by the session's P = n_fft / 640 (1: the 16 kHz kernels, untouched) ----
+void launch_spec(int P, dim3 grid, hipStream_t st, const SpecStreamArgs& a) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_spec, grid, dim3(64 * SWAVES), 0, st, a);
+    else if (P == 2) hipLaunchKernelGGL(k_stream_spec_p<2>, grid, dim3(64 * SWAVES), 0, st, a);
+    else hipLaunchKernelGGL(k_stream_spec_p<3>, grid, dim3(64 * SWAVES), 0, st, a);
+}
+void launch_spec_each(int P, unsigned n, hipStream_t st, const SpecStreamArgs& a, const StreamRow* rows, const StreamItem* items) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_spec_each, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
+    else if (P == 2) hipLaunchKernelGGL(k_stream_spec_p_each<2>, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
+    else hipLaunchKernelGGL(k_stream_spec_p_each<3>, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
+}
+void launch_synth(int P, dim3 grid, hipStream_t st, const IstftArgs& a, const SynthArgs& s) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_synth, grid, dim3(64), 0, st, a, s);
+    else if (P == 2) hipLaunchKernelGGL(k_stream_synth_p<2>, grid, dim3(64), 0, st, a, s);
+    else hipLaunchKernelGGL(k_stream_synth_p<3>, grid, dim3(64), 0, st, a, s);
+}
+void launch_synth_each(int P, unsigned n, hipStream_t st, const IstftArgs& a, const SynthArgs& s, const StreamRow* rows,
+                       const StreamItem* items) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_synth_each, dim3(n), dim3(64), 0, st, a, s, rows, items);
+    else if (P == 2) hipLaunchKernelGGL(k_stream_synth_p_each<2>, dim3(n), dim3(64), 0, st, a, s, rows, items);
+    else hipLaunchKernelGGL(k_stream_synth_p_each<3>, dim3(n), dim3(64), 0, st, a, s, rows, items);
+}
+void launch_ola(int P, dim3 grid, hipStream_t st, const OlaArgs& o, int N, int hop) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_ola, grid, dim3(256), 0, st, o);
+    else hipLaunchKernelGGL(k_stream_ola_n, grid, dim3(256), 0, st, o, N, hop);
+}
+void launch_ola_each(int P, unsigned n, hipStream_t st, const OlaArgs& o, int N, int hop, const StreamRow* rows,
+                     const StreamItem* items) {
+    if (P == 1) hipLaunchKernelGGL(k_stream_ola_each, dim3(n), dim3(256), 0, st, o, rows, items);
+    else hipLaunchKernelGGL(k_stream_ola_n_each, dim3(n), dim3(256), 0, st, o, N, hop, rows, items);
+}
+
 using Counts = StreamCounts;   // the host totals (stream_geom.h stream_totals)
 static_assert(SCHUNK == STREAM_SCHUNK && ROUTE_X == STREAM_ROUTE_X && istft640::FPG == STREAM_SYNTH_FPG,
               "stream_geom.h chunks the kernels' work");
@@ -305,6 +566,7 @@ struct avse_stream {
     const avse_weights* w = nullptr;
     int64_t B = 0, max_slices = 0;
     int sr = 0, n_fft = 0, hop = 0, spf = 0, n_mels = 0, vdt = 0, F = 0;
+    int P = 1;                // n_fft / 640: the phases of a frame (frame_poly.h)
     float amin = 0, top_db = 0, db_floor = 0;
     int R = 0, RS = 0, RV = 0;
     size_t vbytes = 0;
@@ -437,7 +699,7 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             SpecStreamArgs a;
             std::memset(&a, 0, sizeof(a));
             a.tail_in = s->tail;                          // copies 0 / 1: the kernel picks by the row's parity
-            a.tail_out = s->tail + (size_t)B * TAIL;
+            a.tail_out = s->tail + (size_t)B * s->n_fft;
             a.news = samples; a.news_stride = 0;          // + the row's sample_off
             a.spf = s->spf; a.R = s->R; a.RS = s->RS;
             a.twiddle = s->spec.twiddle; a.window = s->spec.window;
@@ -445,7 +707,7 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             std::memcpy(a.nq, s->spec.mel.seg_nq, sizeof(a.nq));
             a.amin = s->amin; a.db_floor = s->db_floor;
             a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
-            hipLaunchKernelGGL(k_stream_spec_each, dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st, a, d_rows, d_spec);
+            launch_spec_each(s->P, (unsigned)p.items.spec, st, a, d_rows, d_spec);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.items.route > 0) {
@@ -470,19 +732,19 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             IstftArgs ia;
             std::memset(&ia, 0, sizeof(ia));
             ia.mel_db = s->pred; ia.spf = s->spf;
-            ia.n_utt = B; ia.nb = 321; ia.N = 640; ia.hop = s->hop; ia.n_mels = s->n_mels;
+            ia.n_utt = B; ia.nb = s->n_fft / 2 + 1; ia.N = s->n_fft; ia.hop = s->hop; ia.n_mels = s->n_mels;
             ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
             SynthArgs sa;
             sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
             sa.T0 = 0; sa.nt = 0; sa.R = s->R;
-            hipLaunchKernelGGL(k_stream_synth_each, dim3((unsigned)p.items.synth), dim3(64), 0, st, ia, sa, d_rows, d_synth);
+            launch_synth_each(s->P, (unsigned)p.items.synth, st, ia, sa, d_rows, d_synth);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.items.ola > 0) {
             OlaArgs o;
             o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
             o.e_old = 0; o.T = 0; o.n_out = 0; o.R = s->R;
-            hipLaunchKernelGGL(k_stream_ola_each, dim3((unsigned)p.items.ola), dim3(256), 0, st, o, d_rows, d_ola);
+            launch_ola_each(s->P, (unsigned)p.items.ola, st, o, s->n_fft, s->hop, d_rows, d_ola);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         return 0;
@@ -540,8 +802,8 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
         if (n_new > 0 || nt > 0) {
             SpecStreamArgs a;
             std::memset(&a, 0, sizeof(a));
-            a.tail_in = s->tail + (size_t)s->parity * B * TAIL;
-            a.tail_out = s->tail + (size_t)(s->parity ^ 1) * B * TAIL;
+            a.tail_in = s->tail + (size_t)s->parity * B * s->n_fft;
+            a.tail_out = s->tail + (size_t)(s->parity ^ 1) * B * s->n_fft;
             a.news = samples; a.news_stride = sample_stride;
             a.n_old = s->n; a.n_new = n2;
             a.Lf = flush ? slice * v2 : -1;
@@ -553,7 +815,7 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
             a.amin = s->amin; a.db_floor = s->db_floor;
             a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
             const int tail_blk = n_new > 0 ? 1 : 0;
-            hipLaunchKernelGGL(k_stream_spec, dim3(a.nblk + tail_blk, B), dim3(64 * SWAVES), 0, st, a);
+            launch_spec(s->P, dim3(a.nblk + tail_blk, B), st, a);
             AVSE_HIP_CHECK(hipGetLastError());
             if (tail_blk) s->parity ^= 1;
         }
@@ -580,19 +842,20 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
             IstftArgs ia;
             std::memset(&ia, 0, sizeof(ia));
             ia.mel_db = s->pred; ia.spf = s->spf; ia.n_slices = (int)k_new;
-            ia.n_utt = B; ia.T = (int)(k_new * s->spf); ia.nb = 321; ia.N = 640; ia.hop = s->hop; ia.n_mels = s->n_mels;
+            ia.n_utt = B; ia.T = (int)(k_new * s->spf); ia.nb = s->n_fft / 2 + 1; ia.N = s->n_fft; ia.hop = s->hop;
+            ia.n_mels = s->n_mels;
             ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
             SynthArgs sa;
             sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
             sa.T0 = c0.slices * s->spf; sa.nt = ia.T; sa.R = s->R;
-            hipLaunchKernelGGL(k_stream_synth, dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B), dim3(64), 0, st, ia, sa);
+            launch_synth(s->P, dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B), st, ia, sa);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (n_out > 0) {
             OlaArgs o;
             o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
             o.e_old = c0.emitted; o.T = c1.slices * s->spf; o.n_out = (int)n_out; o.R = s->R;
-            hipLaunchKernelGGL(k_stream_ola, dim3((unsigned)((n_out + 255) / 256), B), dim3(256), 0, st, o);
+            launch_ola(s->P, dim3((unsigned)((n_out + 255) / 256), B), st, o, s->n_fft, s->hop);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         return 0;
@@ -612,6 +875,29 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
 
 extern "C" {
 
+int avse_stream_supported(int sr, int n_fft, int hop, int frames_per_slice, int n_mels, float fmin, float fmax) {
+    if (sr <= 0 || n_fft < 2 || hop <= 0 || frames_per_slice < 1 || n_mels < 1) return fail(AVSE_ERR_INVALID, "bad stream geometry");
+    // a geometry streams when slices do not drift against the samples: n_fft even and four hops long (the slice is
+    // then frames_per_slice * hop samples by construction); of those, the 640-point kernels are built, and their
+    // P-phase forms for 2 x 640 at 32 kHz and 3 x 640 at 48 kHz
+    if (n_fft % 2 || n_fft != 4 * hop)
+        return fail(AVSE_ERR_UNSUPPORTED, "streaming needs an even n_fft == 4 * hop (25 fps at 16, 32 or 48 kHz: 640 / 160, "
+                                          "1280 / 320, 1920 / 480)");
+    const bool built = n_fft == 640 || (n_fft == 1280 && sr == 32000) || (n_fft == 1920 && sr == 48000);
+    if (!built || n_mels != NMEL)
+        return fail(AVSE_ERR_UNSUPPORTED, "streaming is built for 25 fps at 16, 32 and 48 kHz (n_fft 640 / hop 160, 1280 / 320 at "
+                                          "sr 32000, 1920 / 480 at sr 48000) and 80 bands");
+    // the bank the kernels will read (build_spec_tables makes the same one): every band within the 24-bin table, and
+    // nothing above bin 320, the last of the 640-point arithmetic (always so at n_fft 640)
+    const MelBands mb = mel_bands(sr, n_fft, n_mels, fmin, fmax);
+    bool low = true;
+    for (int m = 0; m < n_mels; ++m) low = low && mb.start[m] + mb.width[m] - 1 <= 320;
+    if (mb.max_width != MW || !low)
+        return fail(AVSE_ERR_UNSUPPORTED, "streaming needs a Slaney bank whose bands fit 24 bins and lie in bins 0 .. 320 "
+                                          "(fmin 0, fmax 8000 at sr 16000, 32000 or 48000)");
+    return 0;
+}
+
 int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, int sr, int n_fft, int hop,
                        int frames_per_slice, int n_mels, float fmin, float fmax, float amin, float top_db, int video_dtype,
                        int64_t max_slices, avse_stream** out) {
@@ -619,11 +905,7 @@ int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, in
     if (n_streams < 1 || max_slices < 1 || sr <= 0 || n_fft < 2 || hop <= 0 || frames_per_slice < 1 || n_mels < 1 || !(amin > 0.f))
         return fail(AVSE_ERR_INVALID, "bad stream geometry");
     if (video_dtype != AVSE_VIDEO_F32 && video_dtype != AVSE_VIDEO_U8) return fail(AVSE_ERR_INVALID, "unknown video dtype");
-    // a geometry streams when slices do not drift against the samples: n_fft even and four hops long (the slice is
-    // then frames_per_slice * hop samples by construction); of those, the 640-point kernels are built
-    if (n_fft % 2 || n_fft != 4 * hop)
-        return fail(AVSE_ERR_UNSUPPORTED, "streaming needs an even n_fft == 4 * hop (25 fps at 16 kHz: 640 / 160)");
-    if (n_fft != 640 || n_mels != NMEL) return fail(AVSE_ERR_UNSUPPORTED, "streaming is built for n_fft 640, hop 160, 80 bands");
+    if (int rc = avse_stream_supported(sr, n_fft, hop, frames_per_slice, n_mels, fmin, fmax)) return rc;
     if (n_streams > 1024 || max_slices > MAX_SLICES_CAP)
         return fail(AVSE_ERR_UNSUPPORTED, "at most 1024 streams and max_slices 16");
     if (w->device != c->device) return fail(AVSE_ERR_INVALID, "weights and context are on different devices");
@@ -638,22 +920,22 @@ int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, in
     s->sr = sr; s->n_fft = n_fft; s->hop = hop; s->spf = frames_per_slice; s->n_mels = n_mels; s->vdt = video_dtype; s->F = wf;
     s->amin = amin; s->top_db = top_db;
     s->db_floor = (float)(20.0 * std::log10((double)amin));
+    s->P = n_fft / 640;
     if (int rc = build_spec_tables(s->spec, sr, n_fft, n_mels, fmin, fmax)) return rc;
-    if (s->spec.mel.max_width != MW)
-        return fail(AVSE_ERR_UNSUPPORTED, "streaming needs a Slaney bank whose bands fit 24 bins (sr 16000, fmin 0, fmax 8000)");
+    if (s->spec.mel.max_width != MW) return fail(AVSE_ERR_UNSUPPORTED, "the mel tables differ from the bank avse_stream_supported saw");
     if (int rc = build_istft_tables(s->ist, sr, n_fft, n_mels, fmin, fmax)) return rc;
     s->RS = 2 * (int)max_slices + 1;
     s->R = s->RS * s->spf;
     s->RV = 2 * (int)max_slices;
     s->vbytes = (size_t)128 * 128 * wf * (video_dtype == AVSE_VIDEO_U8 ? 1 : 4);
     const size_t B = (size_t)n_streams, clips = B * (size_t)max_slices, per = (size_t)NMEL * s->spf;
-    if (s->tail.alloc(sizeof(float) * 2 * B * TAIL) != hipSuccess ||
+    if (s->tail.alloc(sizeof(float) * 2 * B * n_fft) != hipSuccess ||
         s->mel_ring.alloc(sizeof(float) * B * s->RS * per) != hipSuccess ||
         s->fmax_ring.alloc(sizeof(float) * B * s->R) != hipSuccess ||
         s->run_max.alloc(sizeof(float) * B) != hipSuccess ||
         s->net_in.alloc(sizeof(float) * clips * per) != hipSuccess ||
         s->pred.alloc(sizeof(float) * clips * per) != hipSuccess ||
-        s->frame_ring.alloc(sizeof(float) * B * s->R * 640) != hipSuccess ||
+        s->frame_ring.alloc(sizeof(float) * B * s->R * n_fft) != hipSuccess ||
         s->phase_ring.alloc(sizeof(float2) * B * s->R * 321) != hipSuccess ||
         s->vq.alloc(B * s->RV * s->vbytes) != hipSuccess || s->vstage.alloc(clips * s->vbytes) != hipSuccess)
         return fail(AVSE_ERR_OOM, "hipMalloc failed (stream session)");
@@ -762,8 +1044,12 @@ int avse_stream_reset_each(avse_stream* s, const uint8_t* which, void* stream) {
     for (int b = 0; b < B; ++b)
         if (which[b]) ids[n++] = b;
     if (int rc = stream_stage_upload(s, sizeof(int) * (size_t)n, st)) return rc;
-    hipLaunchKernelGGL(k_stream_reset_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(),
-                       reinterpret_cast<const int*>(s->tables.p.get()), B);
+    const int* ids_d = reinterpret_cast<const int*>(s->tables.p.get());
+    if (s->P == 1)
+        hipLaunchKernelGGL(k_stream_reset_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
+    else
+        hipLaunchKernelGGL(k_stream_reset_n_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d,
+                           B, s->n_fft);
     AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
     for (int b = 0; b < B; ++b)
         if (which[b]) s->st[b] = StreamState{0, 0, 0, 0};

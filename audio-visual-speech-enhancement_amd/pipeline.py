@@ -168,10 +168,12 @@ class StreamEnhancer:
     the utterance's maximum, the window sum of the finished signal).  A session carries the sample tail, the running
     floor, the mixture phase of frames awaiting their prediction and the overlap-add tail between pushes instead;
     include/avse.h avse_stream_push states what each push computes.  Where the unclamped mel-dB range of a stream stays
-    below top_db the concatenated output is the offline Enhancer's, for all 3200 S - 160 samples.
+    below top_db the concatenated output is the offline Enhancer's, for all slice * S - hop samples (3200 S - 160 at
+    16 kHz).
 
-    Only geometries whose slices do not drift against the samples stream (25 fps at 16 kHz); 29.97 / 30 fps raise
-    _lib.AvseError at construction."""
+    Only geometries whose slices do not drift against the samples stream, and of those 25 fps at sample_rate 16000,
+    32000 or 48000 (n_fft = rate / 25; the same weights: ops.stream_supported is the rule); 29.97 / 30 fps and 44.1 kHz
+    raise _lib.AvseError at construction."""
 
     def __init__(self, weights, n_streams, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, max_slices=4,
                  video_dtype=torch.float32):

@@ -35,7 +35,7 @@ extern "C" {
  *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
  *    avse_eval_pairs_sized, avse_eval_pairs_ext, avse_stream_create, avse_stream_counts, avse_stream_push,
  *    avse_stream_flush, avse_stream_reset, avse_stream_destroy, avse_stream_push_each, avse_stream_reset_each,
- *    avse_stream_state */
+ *    avse_stream_state, avse_stream_supported */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -353,9 +353,13 @@ int avse_forward_profile_video(avse_ctx* ctx, const avse_weights* w, const float
  * frames_per_slice * hop samples, and `weights` must have been loaded for frames_per_slice spectrogram frames
  * (AVSE_ERR_INVALID otherwise).  A geometry streams when its slices do not drift against the samples: n_fft even and
  * n_fft == 4 * hop, else AVSE_ERR_UNSUPPORTED (29.97 / 30 fps: n_fft 533, and 24 x 133 = 3192 samples per 3200-sample
- * slice).  Built: n_fft 640 / hop 160 / 80 bands with a Slaney bank whose bands fit 24 bins (sr 16000, fmin 0, fmax
- * 8000: the reference's 25-fps geometry), any frames_per_slice the weights have (20 at 25 fps), up to 1024 streams and
- * max_slices 16; other geometries that pass the condition are AVSE_ERR_UNSUPPORTED too.
+ * slice).  Built: the reference's 25-fps geometries (n_fft = sr / 25, data_processor.py:44) at 16, 32 and 48 kHz, i.e.
+ * n_fft 640 / hop 160, n_fft 1280 / hop 320 at sr 32000 and n_fft 1920 / hop 480 at sr 48000, with 80 bands and a Slaney
+ * bank whose bands fit 24 bins and lie in bins 0 .. 320 (fmin 0, fmax 8000: at every one of these rates the bins are
+ * 25 Hz apart and the bank is the 16 kHz bank, so the longer frames are computed as 2 or 3 interleaved 640-point
+ * frames); any frames_per_slice the weights have (20 at 25 fps), up to 1024 streams and max_slices 16.  Other geometries
+ * that pass the condition are AVSE_ERR_UNSUPPORTED too (44.1 kHz: n_fft 1764; fmax 24000 at 48 kHz);
+ * avse_stream_supported is the rule.
  * max_slices: the most slices one call may complete, and the most either input may run ahead of the other.  All device
  * state and scratch is sized from n_streams and max_slices here (the forward scratch through
  * avse_ctx_reserve_weights(ctx, weights, n_streams * max_slices)); create synchronises, a push or a flush allocates
@@ -365,6 +369,10 @@ int avse_forward_profile_video(avse_ctx* ctx, const avse_weights* w, const float
  * one-stream-at-a-time rule.  With AVSE_F32_SPLIT weights the pushes run the unchecked forward: the range-guard bits
  * accumulate in the context, and avse_range_status / avse_range_snapshot read them as for avse_forward. */
 typedef struct avse_stream avse_stream;
+/* Host-only, no GPU work: 0 when avse_stream_create serves this geometry and bank, else the status it would return for
+ * them (AVSE_ERR_INVALID: non-positive values; AVSE_ERR_UNSUPPORTED: see above) with the reason in avse_last_error.
+ * avse_stream_create calls it; the limits on n_streams / max_slices and the weights' shape are checked there. */
+int avse_stream_supported(int sr, int n_fft, int hop, int frames_per_slice, int n_mels, float fmin, float fmax);
 int avse_stream_create(avse_ctx* ctx, const avse_weights* weights, int64_t n_streams, int sr, int n_fft, int hop,
                        int frames_per_slice, int n_mels, float fmin, float fmax, float amin, float top_db,
                        int video_dtype, int64_t max_slices, avse_stream** out);
@@ -389,12 +397,14 @@ int avse_stream_counts(const avse_stream* s, int64_t n_samples, int64_t n_video_
  *    the offline result;
  *  - output sample i is final once every frame covering it is inverted; it is y[i] of librosa.istft over the frames so
  *    far (frames added in increasing order, each sample over the window sum-square of the frames that cover it), so a
- *    stream has emitted max(0, spf H k_done - N/2) samples: 480 samples (30 ms) of latency beyond the slice.
+ *    stream has emitted max(0, spf H k_done - N/2) samples: N/2 + H samples (30 ms at every built rate: 480 at 16 kHz)
+ *    of latency beyond the slice.
  *   samples   [n_streams][n_new] at row stride sample_stride (>= n_new); NULL when n_new == 0
  *   video     [n_streams][v_new][128][128][F] in the session's video_dtype (4-byte aligned); NULL when v_new == 0
  *   vnorm_*   nullable, as avse_forward
  *   out       [n_streams][out_stride]: row b receives *host_n_out new samples of stream b; NULL only when nothing is emitted.
- *             A push emits at most spf H max_slices samples (3200 max_slices), so an out_stride of that many always serves
+ *             A push emits at most spf H max_slices samples in the session's H (3200 max_slices at 16 kHz, 6400 at 32,
+ *             9600 at 48), so an out_stride of that many always serves
  *   host_n_out  HOST: the samples appended per stream (the same for all)
  *   mel_db    nullable [n_streams][slices completed by this call][n_mels][spf]: what the network saw
  *   pred_db   nullable, same shape: what it predicted
@@ -411,8 +421,9 @@ int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_
  * otherwise); missing samples are zeros, as in preprocess_audio_signal (data_processor.py:39-42), the remaining frames
  * take the right reflection of that signal, the remaining slices run, and the rest of the slice * v - hop samples is
  * emitted (frames 0 .. spf v - 1: the offline call drops frame spf v the same way).  Arguments as avse_stream_push.
- * A flush emits at most spf H max_slices + N/2 - H samples (3200 max_slices + 160: max_slices pending slices plus the
- * tail the pushes held back), more than any push: size `out` for it.
+ * A flush emits at most spf H max_slices + N/2 - H samples in the session's N and H (3200 max_slices + 160 at 16 kHz,
+ * 9600 max_slices + 480 at 48: max_slices pending slices plus the tail the pushes held back), more than any push: size
+ * `out` for it.
  * After a flush only avse_stream_reset is legal. */
 int avse_stream_flush(avse_stream* s, const float* vnorm_mean, const float* vnorm_std, float* out, int64_t out_stride,
                       int64_t* host_n_out, float* mel_db /* nullable */, float* pred_db /* nullable */, void* stream);

@@ -36,6 +36,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--dtype", default="float32_split")
+    ap.add_argument("--sample-rate", type=int, default=16000, help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25)")
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--label", default="")
@@ -56,19 +57,22 @@ def main():
     B = args.streams
     rng = np.random.default_rng(0)
     dw = ops.DeviceWeights(KerasModel.init(seed=0, randomize=True), args.dtype)
-    sig = ops.to_device(rng.normal(0, 3000, (B, 3200 * 8)).round().astype(np.float32))
+    sr = args.sample_rate
+    sl = sr // 5                      # samples per 200-ms slice
+    sig = ops.to_device(rng.normal(0, 3000, (B, sl * 8)).round().astype(np.float32))
     video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, 5)).astype(np.float32))
     mean = ops.to_device(np.full((128, 128), 127.5, np.float32))
     std = ops.to_device(np.full((128, 128), 73.9, np.float32))
-    chunks = [sig[:, 3200 * k:3200 * k + 3200].contiguous() for k in range(8)]
+    chunks = [sig[:, sl * k:sl * k + sl].contiguous() for k in range(8)]
     rows = [[c[b] for b in range(B)] for c in chunks]                  # per-stream 1-D views of the same samples
     vrows = [video[b] for b in range(B)]
     active = B // 2 + 1
     one = [[c[b] if b == active else None for b in range(B)] for c in chunks]
     vone = [video[b] if b == active else None for b in range(B)]
 
-    lock, each, sparse, single = (StreamEnhancer(dw, B), StreamEnhancer(dw, B), StreamEnhancer(dw, B), StreamEnhancer(dw, 1))
-    many = [StreamEnhancer(dw, 1) for _ in range(B)]
+    make = lambda n: StreamEnhancer(dw, n, sample_rate=sr)
+    lock, each, sparse, single = make(B), make(B), make(B), make(1)
+    many = [make(1) for _ in range(B)]
 
     def d_tick(i):
         for b, e in enumerate(many):
@@ -99,13 +103,13 @@ def main():
                 t["host_call_ms"].append(1e3 * (t1 - t0))
                 t["host_sync_ms"].append(1e3 * (t2 - t0))
     n_calls = args.warmup + args.rounds
-    want = 3200 * (n_calls - 1) - 320                                  # every push after the first completed its slice
+    want = sl * (n_calls - 1) - sl // 10                                 # every push after the first completed its slice
     assert lock.counts["emitted"] == want and single.counts["emitted"] == want and many[-1].counts["emitted"] == want
     assert each.counts["emitted"] == want, each.counts                 # (uniform counts: the streams stayed in step)
-    assert sparse.counts["emitted"][active] == want and sum(sparse.counts["samples"]) == 3200 * n_calls
+    assert sparse.counts["emitted"][active] == want and sum(sparse.counts["samples"]) == sl * n_calls
     lines = []
     for name, _ in cases:
-        lines.append(json.dumps(dict(what=name, dtype=args.dtype, streams=B, rounds=args.rounds, warmup=args.warmup,
+        lines.append(json.dumps(dict(what=name, dtype=args.dtype, sample_rate=sr, streams=B, rounds=args.rounds, warmup=args.warmup,
                                      label=args.label, **{k: stats(v) for k, v in times[name].items()})))
         print(lines[-1], flush=True)
     if args.out:

@@ -3,8 +3,9 @@
 yardstick, the closest thing the whole-utterance path can do per 200-ms tick: pipeline.Enhancer on U = B utterances of
 S = 1 slice (one STFT, one forward of B clips, one ISTFT).
 
-Per (dtype, B): `--pushes` timed calls after `--warmup` untimed ones, each a 3,200-sample push with its video slice (every
-push after the first completes one slice per stream).  Per call:
+Per (dtype, B): `--pushes` timed calls after `--warmup` untimed ones, each a 200-ms push (3,200 samples at 16 kHz; with
+--sample-rate 32000 / 48000: 6,400 / 9,600) with its video slice (every push after the first completes one slice per
+stream).  Per call:
   event_ms      HIP events recorded on the stream before and after the call: the device-side time of the tick, launch
                 gaps included
   host_call_ms  host clock around the call alone (the enqueue; Enhancer's float32_split path waits for its range guard
@@ -14,6 +15,7 @@ The device is synchronised between calls, so no call queues behind the one befor
 the median and the 99th percentile of each; --out appends them to a file.
 
   python tools/stream_latency.py --out profiles/stream_latency.jsonl
+  python tools/stream_latency.py --sample-rate 48000 --streams 1,64                        # the 3-phase kernels
   python tools/stream_latency.py --yardstick-only --root <checkout of the parent commit>   # the same script on the parent
 """
 import argparse
@@ -52,6 +54,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", default="1,16,64")
     ap.add_argument("--dtypes", default="float32_split,bfloat16")
+    ap.add_argument("--sample-rate", type=int, default=16000, help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25)")
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -75,28 +78,31 @@ def main():
     rng = np.random.default_rng(0)
     model = KerasModel.init(seed=0, randomize=True)
     n_calls = args.warmup + args.pushes
+    sr = args.sample_rate
+    sl = sr // 5                      # samples per 200-ms slice
+    rate = {} if sr == 16000 else {"sample_rate": sr}      # (a parent tree's Enhancer defaults to 16 kHz as well)
     lines = []
     for dtype in args.dtypes.split(","):
         dw = ops.DeviceWeights(model, dtype)
         for B in (int(b) for b in args.streams.split(",")):
-            sig = ops.to_device(rng.normal(0, 3000, (B, 3200 * 8)).round().astype(np.float32))
+            sig = ops.to_device(rng.normal(0, 3000, (B, sl * 8)).round().astype(np.float32))
             video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, 5)).astype(np.float32))
             mean = ops.to_device(np.full((128, 128), 127.5, np.float32))
             std = ops.to_device(np.full((128, 128), 73.9, np.float32))
-            chunks = [sig[:, 3200 * k:3200 * k + 3200].contiguous() for k in range(8)]
+            chunks = [sig[:, sl * k:sl * k + sl].contiguous() for k in range(8)]
             cases = []
             if not args.yardstick_only:
                 from avse_amd.pipeline import StreamEnhancer
-                enh = StreamEnhancer(dw, B)
+                enh = StreamEnhancer(dw, B, **rate)
                 cases.append(("stream_push", lambda i, enh=enh: enh.push(chunks[i % 8], video, mean, std)))
-            off = Enhancer(dw)
+            off = Enhancer(dw, **rate)
             cases.append(("enhancer_1_slice", lambda i, off=off: off(chunks[i % 8], video, mean, std)))
             for name, fn in cases:
-                r = dict(what=name, dtype=dtype, streams=B, pushes=args.pushes, warmup=args.warmup, label=args.label,
+                r = dict(what=name, dtype=dtype, sample_rate=sr, streams=B, pushes=args.pushes, warmup=args.warmup, label=args.label,
                          **timed(fn, args.warmup, args.pushes, torch))
                 if name == "stream_push":
                     r["emitted_samples"] = enh.counts["emitted"]
-                    assert r["emitted_samples"] == 3200 * (n_calls - 1) - 320, r     # every push completed its slice
+                    assert r["emitted_samples"] == sl * (n_calls - 1) - sl // 10, r   # every push completed its slice
                 lines.append(json.dumps(r))
                 print(lines[-1], flush=True)
     if args.out:
