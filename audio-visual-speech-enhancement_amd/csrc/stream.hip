@@ -31,19 +31,24 @@
 //   k_stream_synth  k_istft640's body (frame640.h synth_frames) on the predicted frames and the ring's phases
 //   k_stream_ola    k_ola's sample (frame640.h ola_sample) over the frame ring for the samples that became final
 //
-// Streams need not move together (avse_stream_push_each): the session keeps its counters per stream, stream_geom.h
-// turns a call's per-stream counts into one row per stream and one item table per kernel (block -> stream, chunk), and
-// k_stream_spec_each / _route_each / _synth_each / _ola_each run the bodies of the four kernels above with the row's
-// counters in place of the call's scalars; the forward runs once on the slices all streams completed.  The lock-step
-// calls run the lock-step kernels while every stream's counters are equal.
-//
-// 32 and 48 kHz (n_fft = 640 P, P = 2, 3): k_stream_spec_p<P> / k_stream_synth_p<P> compute each frame as P interleaved
-// 640-point frames (frame_poly.h), k_stream_ola_n / k_stream_reset_n_each take N and hop as arguments, k_stream_route and
-// the forward are shared; the kernels above stay, instruction for instruction, what they are (tools/isa_diff.py).
+// Each launch is one kernel template, k_stream_spec<P, EACH>, k_stream_route<EACH>, k_stream_synth<P, EACH>,
+// k_stream_ola<P, EACH> (and k_stream_reset<P> for avse_stream_reset_each), with its body written once in the kernel:
+//   EACH  Streams need not move together (avse_stream_push_each): the session keeps its counters per stream,
+//         stream_geom.h turns a call's per-stream counts into one row per stream and one item table per kernel (block ->
+//         stream, chunk), and the EACH instances take the row's counters in place of the call's scalars (`if constexpr
+//         (EACH)` at the top of each kernel; the lock-step instances ignore `rows` and `items`).  The forward runs once
+//         on the slices all streams completed.  The lock-step calls run the lock-step instances while every stream's
+//         counters are equal.
+//   P     n_fft = 640 P: 1 at 16 kHz; at 32 and 48 kHz (P = 2, 3) the analysis and the synthesis compute each frame as P
+//         interleaved 640-point frames (frame_poly.h).  N, the hop and N / 2 are compile-time everywhere;
+//         k_stream_route and the forward do not depend on P.
+// A kernel template, not a function taking the argument struct: the by-value kernel argument never leaves the kernel,
+// so each of its fields is still loaded where it is used ("Independent streams").
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "ctx.h"
 #include "frame640.h"
@@ -52,9 +57,9 @@
 #include "stream_geom.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap (as stft.hip)
-#define AVSE_WPE4
-#else
-#define AVSE_WPE4 __attribute__((amdgpu_waves_per_eu(4)))
+#define AVSE_SPEC_WPE(P)
+#else   // the 16 kHz analysis is capped at 4 waves per SIMD's registers; the P-phase instances are not (1: no cap)
+#define AVSE_SPEC_WPE(P) __attribute__((amdgpu_waves_per_eu((P) == 1 ? 4 : 1)))
 #endif
 
 namespace avse {
@@ -64,12 +69,11 @@ using namespace spec640;
 
 constexpr int SCHUNK = 21;               // frames per analysis block
 constexpr int SWAVES = SCHUNK / FPG;     // 7 waves, 3 frames each
-constexpr int TAIL = 640;                // carried samples per stream (n_fft)
 constexpr int NMEL = 80;
 
 struct SpecStreamArgs {
-    const float* tail_in;     // [B][TAIL]: sample n_old - TAIL + j of each stream
-    float* tail_out;          // [B][TAIL]: sample n_new - TAIL + j
+    const float* tail_in;     // [B][N]: sample n_old - N + j of each stream
+    float* tail_out;          // [B][N]: sample n_new - N + j
     const float* news;        // [B][news_stride]: samples n_old .. n_new - 1
     long long news_stride;
     long long n_old, n_new;   // samples received before / after this call
@@ -77,8 +81,8 @@ struct SpecStreamArgs {
     long long t0;             // frames [t0, t0 + nt) are computed
     int nt, nblk;             // nblk = blocks of SCHUNK frames; block nblk (when launched) writes the tail
     int spf, R, RS;
-    const float2* twiddle;
-    const float* window;
+    const float2* twiddle;    // W_N^k [N]
+    const float* window;      // [N]
     const int* mel_start;
     const float* mel_weight;  // [80][MW]
     int nq[4];
@@ -88,79 +92,59 @@ struct SpecStreamArgs {
     float* fmax_ring;
 };
 
-// sample i (0 <= i < n_new) of stream b: from this call's samples or from the carried tail
-__device__ __forceinline__ float stream_sample(const SpecStreamArgs& a, int b, long long i) {
-    if (i >= a.n_old) return a.news[b * a.news_stride + (i - a.n_old)];
-    const long long j = i - (a.n_old - TAIL);
-    return a.tail_in[b * (long long)TAIL + (j > 0 ? j : 0)];
-}
-// sample i of the centre-padded signal: x[-i] = x[i]; a flush closes the signal at Lf (zeros from n_new, reflected)
-__device__ __forceinline__ float frame_sample(const SpecStreamArgs& a, int b, long long i) {
-    if (i < 0) i = -i;
-    if (a.Lf >= 0 && i >= a.Lf) i = 2 * (a.Lf - 1) - i;
-    if (i >= a.n_new) return 0.f;
-    return stream_sample(a, b, i);
-}
-
-// The kernel bodies below come from stream_body.inc, which says why they are shared as text.
-__global__ __launch_bounds__(64 * SWAVES) AVSE_WPE4 void k_stream_spec(SpecStreamArgs a) {
-    const int b = blockIdx.y;
-    const unsigned blk = blockIdx.x;
-#define STREAM_BODY_SPEC
-#include "stream_body.inc"
-#undef STREAM_BODY_SPEC
-}
-
-// Per-stream form (avse_stream_push_each): block -> item -> (stream, chunk) -> the stream's row (stream_geom.h), all
-// wave-uniform.  The row's counters take the place of the lock-step call's scalars in `a`; on entry a.tail_in / tail_out
-// are tail copies 0 / 1 and a.news the caller's `samples` (row stride 0: the row's sample_off addresses the stream).
-__global__ __launch_bounds__(64 * SWAVES) AVSE_WPE4 void k_stream_spec_each(SpecStreamArgs a, const StreamRow* __restrict__ rows,
-                                                                            const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    const float* t0 = a.tail_in;
-    float* t1 = a.tail_out;
-    a.tail_in = r.tail_in ? t1 : t0;
-    a.tail_out = r.tail_in ? const_cast<float*>(t0) : t1;   // the other copy (written only when the stream was fed)
-    a.news += r.sample_off;
-    a.n_old = r.n_old; a.n_new = r.n_new;
-    a.Lf = r.Lf;
-    a.t0 = r.t0; a.nt = r.nt; a.nblk = r.nblk;
-    const int b = it.b;
-    const unsigned blk = it.chunk;
-#define STREAM_BODY_SPEC
-#include "stream_body.inc"
-#undef STREAM_BODY_SPEC
-}
-
-// ---- 32 and 48 kHz: frames of N = 640 P samples, P phases on the 640-point arithmetic (frame_poly.h) ----
-// The tail holds N samples per stream and a frame starts at sample P (160 t - 320); the rings, the mel tables and
-// everything after the analysis are the 16 kHz session's (the band-limited bins 0 .. 320 are the same 25-Hz bins).
+// sample i (0 <= i < n_new) of stream b: from this call's samples or from the carried tail of N samples
 template <int N>
-__device__ __forceinline__ float stream_sample_n(const SpecStreamArgs& a, int b, long long i) {
+__device__ __forceinline__ float stream_sample(const SpecStreamArgs& a, int b, long long i) {
     if (i >= a.n_old) return a.news[b * a.news_stride + (i - a.n_old)];
     const long long j = i - (a.n_old - N);
     return a.tail_in[b * (long long)N + (j > 0 ? j : 0)];
 }
+// sample i of the centre-padded signal: x[-i] = x[i]; a flush closes the signal at Lf (zeros from n_new, reflected)
 template <int N>
-__device__ __forceinline__ float frame_sample_n(const SpecStreamArgs& a, int b, long long i) {
+__device__ __forceinline__ float frame_sample(const SpecStreamArgs& a, int b, long long i) {
     if (i < 0) i = -i;
     if (a.Lf >= 0 && i >= a.Lf) i = 2 * (a.Lf - 1) - i;
     if (i >= a.n_new) return 0.f;
-    return stream_sample_n<N>(a, b, i);
+    return stream_sample<N>(a, b, i);
 }
 
-// One analysis block of k_stream_spec for P phases: a.twiddle is W_N^k and a.window the Hann window, both [N].  The
-// phases run one after another through the wave's three LDS frame slots (LDS stays at k_stream_spec's size plus the
-// P - 1 further window phases); X[k] and X[320 - k] of the lane's step-3 items accumulate in registers, and the
-// magnitudes, band dots, dB and frame maxima follow the last phase, as in stream_body.inc.
-template <int P>
-__device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const int b, const unsigned blk) {
+// One analysis block: chunk blk of SCHUNK frames of stream b, or (blk == a.nblk) the stream's new tail.  Lock-step:
+// grid [blocks, B].  EACH (avse_stream_push_each): block -> item -> (stream, chunk) -> its row (stream_geom.h),
+// all wave-uniform; the row's counters take the place of the lock-step call's scalars in `a`; on entry a.tail_in /
+// tail_out are tail copies 0 / 1 and a.news the caller's `samples` (row stride 0: the row's sample_off addresses the
+// stream).
+// P == 1 is the packed real FFT of k_spec640.  P > 1 (32 / 48 kHz, frame_poly.h): a.twiddle is W_N^k and a.window the
+// Hann window, both [N], and a frame starts at sample P (160 t - 320); the phases run one after another through the
+// wave's three LDS frame slots (LDS is the P == 1 size plus the P - 1 further window phases), X[k] and X[320 - k] of
+// the lane's step-3 items accumulate in registers, and the magnitudes follow the last phase.  The rings, the mel tables
+// and everything after step 3 are the same (the band-limited bins 0 .. 320 are the same 25-Hz bins).
+template <int P, bool EACH>
+__global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(SpecStreamArgs a, const StreamRow* __restrict__ rows,
+                                                                              const StreamItem* __restrict__ items) {
     constexpr int N = 640 * P;
+    int b;
+    unsigned blk;
+    if constexpr (EACH) {
+        const StreamItem it = items[blockIdx.x];
+        const StreamRow& r = rows[it.b];
+        const float* t0 = a.tail_in;
+        float* t1 = a.tail_out;
+        a.tail_in = r.tail_in ? t1 : t0;
+        a.tail_out = r.tail_in ? const_cast<float*>(t0) : t1;   // the other copy (written only when the stream was fed)
+        a.news += r.sample_off;
+        a.n_old = r.n_old; a.n_new = r.n_new;
+        a.Lf = r.Lf;
+        a.t0 = r.t0; a.nt = r.nt; a.nblk = r.nblk;
+        b = it.b;
+        blk = it.chunk;
+    } else {
+        b = blockIdx.y;
+        blk = blockIdx.x;
+    }
     __shared__ float2 zbuf[SWAVES * FPG * ZS];
     __shared__ float2 twl[640];        // W640^k = W_N^{P k}
     __shared__ v2f ut2[161];           // U = -i W640^k / 2 (untangling)
-    __shared__ float2 winl[P * 320];   // phase r of the window as pairs (frame_poly.h window_pair)
+    __shared__ float2 winl[P * 320];   // phase r of the window as the pairs window_frame reads
     __shared__ float4 melw4[NMEL * MW / 4];
     __shared__ int mel_st[NMEL];
 
@@ -168,7 +152,7 @@ __device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const i
     if ((int)blk == a.nblk) {   // the new tail: the last N samples received (zeros before sample 0)
         for (int j = tid; j < N; j += 64 * SWAVES) {
             const long long i = a.n_new - N + j;
-            a.tail_out[b * (long long)N + j] = i < 0 ? 0.f : stream_sample_n<N>(a, b, i);
+            a.tail_out[b * (long long)N + j] = i < 0 ? 0.f : stream_sample<N>(a, b, i);
         }
         return;
     }
@@ -177,34 +161,44 @@ __device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const i
         const float2 w = a.twiddle[P * k];
         ut2[k] = v2f{0.5f * w.y, -0.5f * w.x};
     }
-    for (int i = tid; i < P * 320; i += 64 * SWAVES) winl[i] = spec_poly::window_pair<P>(a.window, i / 320, i % 320);
+    for (int i = tid; i < P * 320; i += 64 * SWAVES) {
+        if constexpr (P == 1) winl[i] = reinterpret_cast<const float2*>(a.window)[i];
+        else winl[i] = spec_poly::window_pair<P>(a.window, i / 320, i % 320);
+    }
     for (int i = tid; i < NMEL * MW / 4; i += 64 * SWAVES) melw4[i] = reinterpret_cast<const float4*>(a.mel_weight)[i];
     for (int i = tid; i < NMEL; i += 64 * SWAVES) mel_st[i] = a.mel_start[i];
-    __syncthreads();
+    if constexpr (P != 1) __syncthreads();   // (P == 1 loads its samples first)
 
     const int g = FPG * wave;                                  // this wave's first frame in the block
     const int nf = min(SCHUNK, a.nt - SCHUNK * (int)blk);
     const int ng = max(0, min(FPG, nf - g));
     const long long tw0 = a.t0 + SCHUNK * (long long)blk + g;   // the wave's first frame
     const int f1 = lane >> 4, n1 = lane & 15;
-    const long long s0 = ((tw0 + f1) * 160 - 320) * P;
-    const bool whole = s0 >= a.n_old && s0 + N <= a.n_new && (a.Lf < 0 || s0 + N <= a.Lf);   // all in this call's samples
-    float2* zw = zbuf + wave * FPG * ZS;
-    v2f ax[spec_poly::IT3], ay[spec_poly::IT3];
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
+    float2* zw;
+    // ---- steps 1 to 3: the complex frame into the phase ring, its magnitudes into LDS ----
+    if constexpr (P == 1) {
         float2 x[20];
 #pragma unroll
         for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
         if (f1 < ng) {
-            if (whole)
-                spec_poly::load_phase<P>(x, a.news + b * a.news_stride + (s0 - a.n_old), n1, r);
-            else
-                spec_poly::load_phase<P>(x, [&](long long i) { return frame_sample_n<N>(a, b, i); }, s0, n1, r);
+            const long long s0 = (tw0 + f1) * 160 - 320;
+            if (s0 >= a.n_old && s0 + 640 <= a.n_new && (a.Lf < 0 || s0 + 640 <= a.Lf)) {   // all in this call's samples
+                const float* p = a.news + b * a.news_stride + (s0 - a.n_old) + 2 * n1;
+#pragma unroll
+                for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(p[32 * n2], p[32 * n2 + 1]);
+            } else {
+#pragma unroll
+                for (int n2 = 0; n2 < 20; ++n2) {
+                    const long long i = s0 + 2 * (n1 + 16 * n2);
+                    x[n2] = make_float2(frame_sample<N>(a, b, i), frame_sample<N>(a, b, i + 1));
+                }
+            }
         }
-        // steps 1 and 2 of the 16 x 20 split on the phase's 640 samples, wave-local
+        __syncthreads();
+        zw = zbuf + wave * FPG * ZS;
+        // steps 1 and 2: the 16 x 20 split of k_spec640, wave-local (each wave owns its three frames)
         v2f v[20];
-        window_frame(v, x, winl + r * 320, n1);
+        window_frame(v, x, winl, n1);
         if (f1 < ng) dft20_store(v, twl, zw + f1 * ZS, n1);
         wave_lds_sync();
         {
@@ -217,29 +211,86 @@ __device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const i
             if (act) dft16_store(w, zf, k2);
         }
         wave_lds_sync();
-        // step 3 of the phase: W_N^{r k} F_r[k] into the accumulators
-        spec_poly::accumulate<P>(ax, ay, zw, ut2, a.twiddle, r, ng, lane);
-        wave_lds_sync();   // the next phase (or the magnitudes below) overwrites the slots
-    }
-    // ---- the complex frame into the phase ring, its magnitudes into LDS; item = (f, k) ----
+        // step 3: untangling; item = (f, k)
+        constexpr int IT3 = (FPG * 161 + 63) / 64;   // 8
+        float mk[IT3], mm[IT3];
 #pragma unroll
-    for (int j = 0; j < spec_poly::IT3; ++j) {
-        const int it = lane + 64 * j;
-        if (it >= ng * 161) break;
-        const int f = it / 161, k = it - 161 * f;
-        float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
-        o[k] = make_float2(ax[j].x, ax[j].y);
-        if (k != 160) o[320 - k] = make_float2(ay[j].x, ay[j].y);
-        float* mf = reinterpret_cast<float*>(zw + f * ZS);
-        mf[k] = pk_abs(ax[j]);
-        mf[320 - k] = pk_abs(ay[j]);
+        for (int j = 0; j < IT3; ++j) {
+            const int it = lane + 64 * j;
+            if (it >= ng * 161) break;
+            const int f = it / 161, k = it - 161 * f;
+            v2f X, Y;
+            pk_untangle(reinterpret_cast<const v2f*>(zw + f * ZS), k, ut2, X, Y);
+            mk[j] = pk_abs(X);
+            mm[j] = pk_abs(Y);
+            float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
+            o[k] = make_float2(X.x, X.y);
+            if (k != 160) o[320 - k] = make_float2(Y.x, -Y.y);   // X[320 - k] = conj(Y)
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < IT3; ++j) {
+            const int it = lane + 64 * j;
+            if (it >= ng * 161) break;
+            const int f = it / 161, k = it - 161 * f;
+            float* mf = reinterpret_cast<float*>(zw + f * ZS);
+            mf[k] = mk[j];
+            mf[320 - k] = mm[j];
+        }
+    } else {
+        const long long s0 = ((tw0 + f1) * 160 - 320) * P;
+        const bool whole = s0 >= a.n_old && s0 + N <= a.n_new && (a.Lf < 0 || s0 + N <= a.Lf);   // all in this call's samples
+        zw = zbuf + wave * FPG * ZS;
+        v2f ax[spec_poly::IT3], ay[spec_poly::IT3];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            float2 x[20];
+#pragma unroll
+            for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
+            if (f1 < ng) {
+                if (whole)
+                    spec_poly::load_phase<P>(x, a.news + b * a.news_stride + (s0 - a.n_old), n1, r);
+                else
+                    spec_poly::load_phase<P>(x, [&](long long i) { return frame_sample<N>(a, b, i); }, s0, n1, r);
+            }
+            // steps 1 and 2 of the 16 x 20 split on the phase's 640 samples, wave-local
+            v2f v[20];
+            window_frame(v, x, winl + r * 320, n1);
+            if (f1 < ng) dft20_store(v, twl, zw + f1 * ZS, n1);
+            wave_lds_sync();
+            {
+                const int f = lane / 20, k2 = lane - 20 * (lane / 20);
+                const bool act = f < ng;
+                v2f w[16];
+                v2f* zf = reinterpret_cast<v2f*>(zw + min(f, FPG - 1) * ZS);
+                if (act) dft16_load(w, zf, k2);
+                wave_lds_sync();
+                if (act) dft16_store(w, zf, k2);
+            }
+            wave_lds_sync();
+            // step 3 of the phase: W_N^{r k} F_r[k] into the accumulators
+            spec_poly::accumulate<P>(ax, ay, zw, ut2, a.twiddle, r, ng, lane);
+            wave_lds_sync();   // the next phase (or the magnitudes below) overwrites the slots
+        }
+#pragma unroll
+        for (int j = 0; j < spec_poly::IT3; ++j) {   // item = (f, k)
+            const int it = lane + 64 * j;
+            if (it >= ng * 161) break;
+            const int f = it / 161, k = it - 161 * f;
+            float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
+            o[k] = make_float2(ax[j].x, ax[j].y);
+            if (k != 160) o[320 - k] = make_float2(ay[j].x, ay[j].y);
+            float* mf = reinterpret_cast<float*>(zw + f * ZS);
+            mf[k] = pk_abs(ax[j]);
+            mf[320 - k] = pk_abs(ay[j]);
+        }
     }
     for (int it = lane; it < FPG * MW; it += 64) {   // bins [321, 321 + MW) are read by the padded band dots
         const int f = it / MW, j = it - MW * f;
         reinterpret_cast<float*>(zw + f * ZS)[321 + j] = 0.f;
     }
     wave_lds_sync();
-    // ---- step 4: Slaney mel + dB, item = (m, f); unclamped, into the frame's slice slot ----
+    // ---- step 4: Slaney mel + dB, item = (m, f) as k_spec640; unclamped, into the frame's slice slot ----
     float fm0 = -INFINITY, fm1 = -INFINITY, fm2 = -INFINITY;
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -265,28 +316,6 @@ __device__ __forceinline__ void spec_poly_block(const SpecStreamArgs& a, const i
     if (lane < ng) a.fmax_ring[(long long)b * a.R + (int)((tw0 + lane) % a.R)] = lane == 0 ? fm0 : lane == 1 ? fm1 : fm2;
 }
 
-template <int P>
-__global__ __launch_bounds__(64 * SWAVES) void k_stream_spec_p(SpecStreamArgs a) {
-    spec_poly_block<P>(a, blockIdx.y, blockIdx.x);
-}
-
-// Per-stream form, as k_stream_spec_each
-template <int P>
-__global__ __launch_bounds__(64 * SWAVES) void k_stream_spec_p_each(SpecStreamArgs a, const StreamRow* __restrict__ rows,
-                                                                    const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    const float* t0 = a.tail_in;
-    float* t1 = a.tail_out;
-    a.tail_in = r.tail_in ? t1 : t0;
-    a.tail_out = r.tail_in ? const_cast<float*>(t0) : t1;
-    a.news += r.sample_off;
-    a.n_old = r.n_old; a.n_new = r.n_new;
-    a.Lf = r.Lf;
-    a.t0 = r.t0; a.nt = r.nt; a.nblk = r.nblk;
-    spec_poly_block<P>(a, it.b, it.chunk);
-}
-
 struct RouteArgs {
     // the causal clamp of slices [k_old, k_old + k_new)
     const float* mel_ring;
@@ -308,70 +337,94 @@ struct RouteArgs {
 constexpr int ROUTE_X = 8;    // blocks per video slice
 constexpr int MAX_SLICES_CAP = 16;   // avse_stream_create's bound on max_slices
 
-// grid: ROUTE_X blocks per (stream, video slice in flight), then one clamp block per stream when slices completed
-__global__ __launch_bounds__(256) void k_stream_route(RouteArgs a) {
-    __shared__ float slice_max[MAX_SLICES_CAP];
-    const int tid = threadIdx.x;
-    const int n_video = ROUTE_X * a.B * a.nv;
-    if ((int)blockIdx.x < n_video) {
-        const int y = blockIdx.x / ROUTE_X, part = blockIdx.x - ROUTE_X * y;
-        const int b = y / a.nv;
-        const long long k = a.k_old + (y - b * a.nv);
-        const bool from_q = k < a.v_old, to_net = k < a.k_old + a.k_new;
-        if (from_q && !to_net) return;   // stays queued
-        const char* src = from_q ? a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes
-                                 : a.vnew + ((long long)b * a.v_new + (k - a.v_old)) * a.vbytes;
-        char* dst = to_net ? a.vstage + ((long long)b * a.k_new + (k - a.k_old)) * a.vbytes
-                           : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
-#define STREAM_BODY_COPY
-#include "stream_body.inc"
-#undef STREAM_BODY_COPY
-        return;
+// part `part` of ROUTE_X of one video slice's copy (scalars, not RouteArgs: see the header)
+__device__ __forceinline__ void route_copy(const char* src, char* dst, long long vbytes, int vec16, int part, int tid) {
+    if (vec16) {
+        const long long n = vbytes / 16;
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        for (long long i = part * 256LL + tid; i < n; i += ROUTE_X * 256LL) d4[i] = s4[i];
+    } else {
+        const long long n = vbytes / 4;
+        const unsigned* s1 = reinterpret_cast<const unsigned*>(src);
+        unsigned* d1 = reinterpret_cast<unsigned*>(dst);
+        for (long long i = part * 256LL + tid; i < n; i += ROUTE_X * 256LL) d1[i] = s1[i];
     }
-    const int b = blockIdx.x - n_video;   // one block per stream
-#define STREAM_BODY_CLAMP
-#define STREAM_K_OLD a.k_old
-#define STREAM_K_NEW a.k_new
-#define STREAM_CLIP(kk) ((long long)b * a.k_new + kk)
-#include "stream_body.inc"
-#undef STREAM_K_OLD
-#undef STREAM_K_NEW
-#undef STREAM_CLIP
-#undef STREAM_BODY_CLAMP
 }
 
-// Per-stream form: an item is part chunk % ROUTE_X of the move of the stream's slice k_old + chunk / ROUTE_X (only
-// slices that move are listed), or (chunk == STREAM_CLAMP) its clamp block.  a.vnew is the packed video of the call;
+// Lock-step grid: ROUTE_X blocks per (stream, video slice in flight), then one clamp block per stream when slices
+// completed.  EACH: an item is part chunk % ROUTE_X of the move of the stream's slice k_old + chunk / ROUTE_X (only
+// slices that move are listed), or (chunk == STREAM_CLAMP) its clamp block; a.vnew is the packed video of the call, and
 // the network input, mel_out and vstage are compacted: the stream's slices are clips clip0 .. clip0 + k_new - 1.
-__global__ __launch_bounds__(256) void k_stream_route_each(RouteArgs a, const StreamRow* __restrict__ rows,
-                                                           const StreamItem* __restrict__ items) {
+template <bool EACH>
+__global__ __launch_bounds__(256) void k_stream_route(RouteArgs a, const StreamRow* __restrict__ rows,
+                                                      const StreamItem* __restrict__ items) {
     __shared__ float slice_max[MAX_SLICES_CAP];
     const int tid = threadIdx.x;
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    const int b = it.b;
-    if (it.chunk != STREAM_CLAMP) {
-        const int kk = it.chunk / ROUTE_X, part = it.chunk - ROUTE_X * kk;
-        const long long k = r.k_old + kk;
-        const bool from_q = k < r.v_old, to_net = kk < r.k_new;
-        const char* src = from_q ? a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes
-                                 : a.vnew + (r.video_off + (k - r.v_old)) * a.vbytes;
-        char* dst = to_net ? a.vstage + ((long long)r.clip0 + kk) * a.vbytes
-                           : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
-#define STREAM_BODY_COPY
-#include "stream_body.inc"
-#undef STREAM_BODY_COPY
-        return;
+    // The block's item, row and (lock-step) video block count stand here, at function scope, with a dummy for the form
+    // that has none, and not inside the `if constexpr` braces below: a brace scope that declares locals, returns early
+    // and is also left normally compiles to a cleanup switch, and with it to another control flow than these kernels
+    // had as two functions (2,291 instruction lines of the lock-step instance moved).
+    const StreamItem it = EACH ? items[blockIdx.x] : StreamItem{0, 0};
+    const StreamRow* r = EACH ? rows + it.b : nullptr;
+    const int n_video = EACH ? 0 : ROUTE_X * a.B * a.nv;   // lock-step: the grid's video blocks come first
+    if constexpr (EACH) {
+        if (it.chunk != STREAM_CLAMP) {
+            const int b = it.b;
+            const int kk = it.chunk / ROUTE_X, part = it.chunk - ROUTE_X * kk;
+            const long long k = r->k_old + kk;
+            const bool from_q = k < r->v_old, to_net = kk < r->k_new;
+            const char* src = from_q ? a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes
+                                     : a.vnew + (r->video_off + (k - r->v_old)) * a.vbytes;
+            char* dst = to_net ? a.vstage + ((long long)r->clip0 + kk) * a.vbytes
+                               : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
+            route_copy(src, dst, a.vbytes, a.vec16, part, tid);
+            return;
+        }
+    } else {
+        if ((int)blockIdx.x < n_video) {
+            const int y = blockIdx.x / ROUTE_X, part = blockIdx.x - ROUTE_X * y;
+            const int b = y / a.nv;
+            const long long k = a.k_old + (y - b * a.nv);
+            const bool from_q = k < a.v_old, to_net = k < a.k_old + a.k_new;
+            if (from_q && !to_net) return;   // stays queued
+            const char* src = from_q ? a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes
+                                     : a.vnew + ((long long)b * a.v_new + (k - a.v_old)) * a.vbytes;
+            char* dst = to_net ? a.vstage + ((long long)b * a.k_new + (k - a.k_old)) * a.vbytes
+                               : a.vq + ((long long)b * a.RV + (int)(k % a.RV)) * a.vbytes;
+            route_copy(src, dst, a.vbytes, a.vec16, part, tid);
+            return;
+        }
     }
-#define STREAM_BODY_CLAMP
-#define STREAM_K_OLD r.k_old
-#define STREAM_K_NEW r.k_new
-#define STREAM_CLIP(kk) ((long long)r.clip0 + kk)
-#include "stream_body.inc"
-#undef STREAM_K_OLD
-#undef STREAM_K_NEW
-#undef STREAM_CLIP
-#undef STREAM_BODY_CLAMP
+    // the clamp block of stream b: its slices [k_old, k_old + k_new) are clips clip0 .. of the network's input, each
+    // of the three read where it is used (the row's fields are reloaded there, as the call's scalars are; copies made
+    // here, or accessor lambdas capturing `a`, compile to other code)
+    const int b = EACH ? it.b : blockIdx.x - n_video;
+    // the floor of slice k is (the maximum over every frame up to its last) - top_db.  Wave w takes the maxima of
+    // slices w, w + 4, ..: a lane per frame, then the wave's maximum (a maximum has no order)
+    for (int kk = tid >> 6; kk < (EACH ? r->k_new : a.k_new); kk += 4) {
+        const long long t0 = ((EACH ? r->k_old : a.k_old) + kk) * a.spf;
+        float m = -INFINITY;
+        for (int tt = tid & 63; tt < a.spf; tt += 64) m = fmaxf(m, a.fmax_ring[(long long)b * a.R + (int)((t0 + tt) % a.R)]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if ((tid & 63) == 0) slice_max[kk] = m;
+    }
+    float cur = a.run_max[b];
+    __syncthreads();   // the slices' maxima are there, and every thread has read the old running maximum
+    const int per = NMEL * a.spf;
+    for (int kk = 0; kk < (EACH ? r->k_new : a.k_new); ++kk) {   // the prefix maximum, in slice order
+        cur = fmaxf(cur, slice_max[kk]);
+        const float floor_db = a.top_db >= 0.f ? cur - a.top_db : -INFINITY;
+        const float* src = a.mel_ring + ((long long)b * a.RS + (int)(((EACH ? r->k_old : a.k_old) + kk) % a.RS)) * per;
+        const long long d0 = ((EACH ? r->clip0 : (long long)b * a.k_new) + kk) * per;
+        for (int i = tid; i < per; i += 256) {
+            const float v = fmaxf(src[i], floor_db);
+            a.net_in[d0 + i] = v;
+            if (a.mel_out) a.mel_out[d0 + i] = v;
+        }
+    }
+    if (tid == 0) a.run_max[b] = cur;
 }
 
 struct SynthArgs {
@@ -381,64 +434,37 @@ struct SynthArgs {
     int nt, R;
 };
 
-// One group of FPG frames from t0 of stream b's s.nt predicted frames; clip(sl) is the clip of a.mel_db that holds the
-// stream's slice sl of this call.  (Its callers are distinct instances, Clip being a lambda type: one LDS allocation of
-// synth_frames per kernel.)
-template <class Clip>
-__device__ __forceinline__ void synth_group(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
-    istft640::synth_frames(
-        a, min(istft640::FPG, s.nt - t0),
-        [&](int m, int f) {
-            const int t = t0 + f, sl = t / a.spf;
-            return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
-        },
-        [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; },
-        [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 640; });
-}
-
-__global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s) {
-    const int b = blockIdx.y;
-    const int t0 = blockIdx.x * istft640::FPG;
-    synth_group(a, s, b, t0, [&](int sl) { return (long long)b * a.n_slices + sl; });
-}
-
-// Per-stream form: item (stream, group); the stream inverts its k_new slices from frame spf k_old on.
-__global__ __launch_bounds__(64) void k_stream_synth_each(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
-                                                          const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    s.T0 = r.k_old * a.spf;
-    s.nt = r.k_new * a.spf;
-    synth_group(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
-}
-
-// 32 / 48 kHz: synth_group on frame_poly.h's synth_frames (a.N = 640 P; the frame ring's slots hold N samples)
+// One group of FPG frames from t0 of stream b's s.nt predicted frames, into the frame ring's slots of 640 P samples;
+// clip(sl) is the clip of a.mel_db that holds the stream's slice sl of this call.  (Its callers are distinct instances,
+// Clip being a lambda type: one LDS allocation of synth_frames per kernel.)  P > 1: a.N = 640 P, frame_poly.h.
 template <int P, class Clip>
-__device__ __forceinline__ void synth_group_p(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
-    istft_poly::synth_frames<P>(
-        a, min(istft640::FPG, s.nt - t0),
-        [&](int m, int f) {
-            const int t = t0 + f, sl = t / a.spf;
-            return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
-        },
-        [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; },
-        [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * (640 * P); });
+__device__ __forceinline__ void synth_group(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
+    const int ng = min(istft640::FPG, s.nt - t0);
+    auto mel_db = [&](int m, int f) {
+        const int t = t0 + f, sl = t / a.spf;
+        return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
+    };
+    auto stft = [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; };
+    auto frame = [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * (640 * P); };
+    if constexpr (P == 1) istft640::synth_frames(a, ng, mel_db, stft, frame);
+    else istft_poly::synth_frames<P>(a, ng, mel_db, stft, frame);
 }
 
-template <int P>
-__global__ __launch_bounds__(64) void k_stream_synth_p(IstftArgs a, SynthArgs s) {
-    const int b = blockIdx.y;
-    synth_group_p<P>(a, s, b, blockIdx.x * istft640::FPG, [&](int sl) { return (long long)b * a.n_slices + sl; });
-}
-
-template <int P>
-__global__ __launch_bounds__(64) void k_stream_synth_p_each(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
-                                                            const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    s.T0 = r.k_old * a.spf;
-    s.nt = r.k_new * a.spf;
-    synth_group_p<P>(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
+// Lock-step: grid [groups, B].  EACH: item (stream, group); the stream inverts its k_new slices from frame spf k_old on.
+template <int P, bool EACH>
+__global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
+                                                     const StreamItem* __restrict__ items) {
+    if constexpr (EACH) {
+        const StreamItem it = items[blockIdx.x];
+        const StreamRow& r = rows[it.b];
+        s.T0 = r.k_old * a.spf;
+        s.nt = r.k_new * a.spf;
+        synth_group<P>(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
+    } else {
+        const int b = blockIdx.y;
+        const int t0 = blockIdx.x * istft640::FPG;
+        synth_group<P>(a, s, b, t0, [&](int sl) { return (long long)b * a.n_slices + sl; });
+    }
 }
 
 struct OlaArgs {
@@ -449,36 +475,33 @@ struct OlaArgs {
     int n_out, R;
 };
 
-// output sample j of this call of stream b
-__device__ __forceinline__ void ola_out(const OlaArgs& a, const int b, const int j) {
-    if (j >= a.n_out) return;
-    const long long p = a.e_old + j + 320;   // position in the untrimmed signal
-    a.out[b * a.out_stride + j] = istft640::ola_sample(p, a.T, 640, 160, a.window, [&](long long t, int o) {
-        return a.frame_ring[((long long)b * a.R + (int)(t % a.R)) * 640 + o];
-    });
-}
-
-// The overlap-add and the reset for a session's own N and hop (32 / 48 kHz): ola_out / k_stream_reset_each with the
-// session's N, hop and N / 2 in place of 640, 160 and 320.
-__device__ __forceinline__ void ola_out_n(const OlaArgs& a, const int N, const int hop, const int b, const int j) {
+// Output sample j of this call of each stream.  Lock-step: grid [blocks of 256 samples, B].  EACH: item (stream, block).
+template <int P, bool EACH>
+__global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a, const StreamRow* __restrict__ rows,
+                                                    const StreamItem* __restrict__ items) {
+    constexpr int N = 640 * P, hop = 160 * P;
+    int b, j;
+    if constexpr (EACH) {
+        const StreamItem it = items[blockIdx.x];
+        const StreamRow& r = rows[it.b];
+        a.e_old = r.e_old; a.T = r.T; a.n_out = r.n_out;
+        b = it.b;
+        j = it.chunk * STREAM_OLA_BLOCK + threadIdx.x;
+    } else {
+        b = blockIdx.y;
+        j = blockIdx.x * 256 + threadIdx.x;
+    }
     if (j >= a.n_out) return;
     const long long p = a.e_old + j + N / 2;   // position in the untrimmed signal
     a.out[b * a.out_stride + j] = istft640::ola_sample(p, a.T, N, hop, a.window, [&](long long t, int o) {
         return a.frame_ring[((long long)b * a.R + (int)(t % a.R)) * N + o];
     });
 }
-__global__ __launch_bounds__(256) void k_stream_ola_n(OlaArgs a, int N, int hop) {
-    ola_out_n(a, N, hop, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
-}
-__global__ __launch_bounds__(256) void k_stream_ola_n_each(OlaArgs a, int N, int hop, const StreamRow* __restrict__ rows,
-                                                           const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    a.e_old = r.e_old; a.T = r.T; a.n_out = r.n_out;
-    ola_out_n(a, N, hop, it.b, it.chunk * STREAM_OLA_BLOCK + threadIdx.x);
-}
-__global__ __launch_bounds__(256) void k_stream_reset_n_each(float* tail, float* run_max, const int* __restrict__ ids, int B,
-                                                             int N) {
+
+// The streams ids[0 .. gridDim.x) go back to the state after create: both tail copies zero, running maximum -inf.
+template <int P>
+__global__ __launch_bounds__(256) void k_stream_reset(float* tail, float* run_max, const int* __restrict__ ids, int B) {
+    constexpr int N = 640 * P;
     const int b = ids[blockIdx.x];
     for (int j = threadIdx.x; j < 2 * N; j += 256) {
         const int copy = j / N;
@@ -487,69 +510,12 @@ __global__ __launch_bounds__(256) void k_stream_reset_n_each(float* tail, float*
     if (threadIdx.x == 0) run_max[b] = -INFINITY;
 }
 
-// the instances (here, ahead of the 16 kHz kernels below, whose place in the code object stays what it was)
-template __global__ void k_stream_spec_p<2>(SpecStreamArgs);
-template __global__ void k_stream_spec_p<3>(SpecStreamArgs);
-template __global__ void k_stream_spec_p_each<2>(SpecStreamArgs, const StreamRow*, const StreamItem*);
-template __global__ void k_stream_spec_p_each<3>(SpecStreamArgs, const StreamRow*, const StreamItem*);
-template __global__ void k_stream_synth_p<2>(IstftArgs, SynthArgs);
-template __global__ void k_stream_synth_p<3>(IstftArgs, SynthArgs);
-template __global__ void k_stream_synth_p_each<2>(IstftArgs, SynthArgs, const StreamRow*, const StreamItem*);
-template __global__ void k_stream_synth_p_each<3>(IstftArgs, SynthArgs, const StreamRow*, const StreamItem*);
-
-// Per-stream form: item (stream, block of 256 samples)
-__global__ __launch_bounds__(256) void k_stream_ola_each(OlaArgs a, const StreamRow* __restrict__ rows,
-                                                         const StreamItem* __restrict__ items) {
-    const StreamItem it = items[blockIdx.x];
-    const StreamRow& r = rows[it.b];
-    a.e_old = r.e_old; a.T = r.T; a.n_out = r.n_out;
-    ola_out(a, it.b, it.chunk * STREAM_OLA_BLOCK + threadIdx.x);
-}
-
-// The streams ids[0 .. gridDim.x) go back to the state after create: both tail copies zero, running maximum -inf.
-__global__ __launch_bounds__(256) void k_stream_reset_each(float* tail, float* run_max, const int* __restrict__ ids, int B) {
-    const int b = ids[blockIdx.x];
-    for (int j = threadIdx.x; j < 2 * TAIL; j += 256) {
-        const int copy = j / TAIL;
-        tail[((long long)copy * B + b) * TAIL + (j - copy * TAIL)] = 0.f;
-    }
-    if (threadIdx.x == 0) run_max[b] = -INFINITY;
-}
-
-__global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a) {
-    ola_out(a, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
-}
-
-// ---- host: the kernel of each launch by the session's P = n_fft / 640 (1: the 16 kHz kernels, untouched) ----
-void launch_spec(int P, dim3 grid, hipStream_t st, const SpecStreamArgs& a) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_spec, grid, dim3(64 * SWAVES), 0, st, a);
-    else if (P == 2) hipLaunchKernelGGL(k_stream_spec_p<2>, grid, dim3(64 * SWAVES), 0, st, a);
-    else hipLaunchKernelGGL(k_stream_spec_p<3>, grid, dim3(64 * SWAVES), 0, st, a);
-}
-void launch_spec_each(int P, unsigned n, hipStream_t st, const SpecStreamArgs& a, const StreamRow* rows, const StreamItem* items) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_spec_each, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
-    else if (P == 2) hipLaunchKernelGGL(k_stream_spec_p_each<2>, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
-    else hipLaunchKernelGGL(k_stream_spec_p_each<3>, dim3(n), dim3(64 * SWAVES), 0, st, a, rows, items);
-}
-void launch_synth(int P, dim3 grid, hipStream_t st, const IstftArgs& a, const SynthArgs& s) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_synth, grid, dim3(64), 0, st, a, s);
-    else if (P == 2) hipLaunchKernelGGL(k_stream_synth_p<2>, grid, dim3(64), 0, st, a, s);
-    else hipLaunchKernelGGL(k_stream_synth_p<3>, grid, dim3(64), 0, st, a, s);
-}
-void launch_synth_each(int P, unsigned n, hipStream_t st, const IstftArgs& a, const SynthArgs& s, const StreamRow* rows,
-                       const StreamItem* items) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_synth_each, dim3(n), dim3(64), 0, st, a, s, rows, items);
-    else if (P == 2) hipLaunchKernelGGL(k_stream_synth_p_each<2>, dim3(n), dim3(64), 0, st, a, s, rows, items);
-    else hipLaunchKernelGGL(k_stream_synth_p_each<3>, dim3(n), dim3(64), 0, st, a, s, rows, items);
-}
-void launch_ola(int P, dim3 grid, hipStream_t st, const OlaArgs& o, int N, int hop) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_ola, grid, dim3(256), 0, st, o);
-    else hipLaunchKernelGGL(k_stream_ola_n, grid, dim3(256), 0, st, o, N, hop);
-}
-void launch_ola_each(int P, unsigned n, hipStream_t st, const OlaArgs& o, int N, int hop, const StreamRow* rows,
-                     const StreamItem* items) {
-    if (P == 1) hipLaunchKernelGGL(k_stream_ola_each, dim3(n), dim3(256), 0, st, o, rows, items);
-    else hipLaunchKernelGGL(k_stream_ola_n_each, dim3(n), dim3(256), 0, st, o, N, hop, rows, items);
+// ---- host: f(std::integral_constant<int, P>) for the session's P = n_fft / 640, the kernels' template argument ----
+template <class F>
+void with_phases(int P, F f) {
+    if (P == 1) f(std::integral_constant<int, 1>{});
+    else if (P == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
 }
 
 using Counts = StreamCounts;   // the host totals (stream_geom.h stream_totals)
@@ -575,13 +541,11 @@ struct avse_stream {
     Owned<float> tail, mel_ring, fmax_ring, run_max, net_in, pred, frame_ring;
     Owned<float2> phase_ring;
     Owned<char> vq, vstage;
-    // host counters, per stream; n / v / parity / flushed mirror them while `uniform` (every stream's are equal), which
-    // is when the lock-step calls run the lock-step kernels
+    // host counters, per stream; while `uniform` (every stream's are equal) st[0] speaks for all, and the lock-step
+    // calls run the lock-step kernels
     std::vector<StreamState> st;
     bool uniform = true;
-    int64_t n = 0, v = 0;
-    int parity = 0;           // which tail copy holds the last samples
-    bool flushed = false, broken = false;
+    bool broken = false;
     // per-stream calls: the rows of the call being decided, and the pinned staging ring their tables go up from (one
     // slot per call in turn; `staged[i]` is recorded once the copy out of slot i is queued)
     static constexpr int SLOTS = 4;
@@ -603,34 +567,72 @@ struct avse_stream {
 
 namespace {
 
+// every stream to one state: create / reset, and after a lock-step step
+void stream_set_all(avse_stream* s, const StreamState& t) {
+    std::fill(s->st.begin(), s->st.end(), t);
+    s->uniform = true;
+}
+
 int stream_init_state(avse_stream* s, hipStream_t st) {
     AVSE_HIP_CHECK(hipMemsetAsync(s->tail, 0, s->tail.bytes, st));
     AVSE_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)s->run_max.p.get(), (int)0xff800000u, (size_t)s->B, st));   // -inf
-    s->n = s->v = 0;
-    s->parity = 0;
-    s->flushed = s->broken = false;
-    std::fill(s->st.begin(), s->st.end(), StreamState{0, 0, 0, 0});
-    s->uniform = true;
+    s->broken = false;
+    stream_set_all(s, StreamState{0, 0, 0, 0});
     return 0;
 }
 
-// the lock-step mirror -> every stream (after a lock-step step)
-void stream_set_all(avse_stream* s) {
-    std::fill(s->st.begin(), s->st.end(), StreamState{s->n, s->v, (uint8_t)s->flushed, (uint8_t)s->parity});
-    s->uniform = true;
-}
-
-// after a per-stream step: are the streams in lock step again?  (then the mirror holds their counters)
+// after a per-stream step: are the streams in lock step again?
 void stream_refresh_uniform(avse_stream* s) {
     const StreamState a = s->st[0];
     bool u = true;
     for (const StreamState& t : s->st) u = u && t.n == a.n && t.v == a.v && t.flushed == a.flushed && t.parity == a.parity;
     s->uniform = u;
-    if (u) {
-        s->n = a.n; s->v = a.v;
-        s->parity = a.parity;
-        s->flushed = a.flushed != 0;
-    }
+}
+
+// ---- the kernels' argument structs with the session's constants; a step sets the per-call fields ----
+SpecStreamArgs spec_args(const avse_stream* s, const float* samples, int64_t sample_stride) {
+    SpecStreamArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.news = samples; a.news_stride = sample_stride;
+    a.spf = s->spf; a.R = s->R; a.RS = s->RS;
+    a.twiddle = s->spec.twiddle; a.window = s->spec.window;
+    a.mel_start = s->spec.mel.start; a.mel_weight = s->spec.mel.weight;
+    std::memcpy(a.nq, s->spec.mel.seg_nq, sizeof(a.nq));
+    a.amin = s->amin; a.db_floor = s->db_floor;
+    a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
+    return a;
+}
+RouteArgs route_args(const avse_stream* s, const void* video, float* mel_db) {
+    RouteArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.mel_ring = s->mel_ring; r.fmax_ring = s->fmax_ring; r.run_max = s->run_max;
+    r.net_in = s->net_in; r.mel_out = mel_db;
+    r.spf = s->spf; r.R = s->R; r.RS = s->RS; r.top_db = s->top_db;
+    r.vnew = reinterpret_cast<const char*>(video); r.vq = s->vq; r.vstage = s->vstage;
+    r.vbytes = (long long)s->vbytes;
+    r.RV = s->RV; r.B = (int)s->B;
+    r.vec16 = (reinterpret_cast<uintptr_t>(video) & 15) == 0;
+    return r;
+}
+IstftArgs istft_args(const avse_stream* s) {
+    IstftArgs ia;
+    std::memset(&ia, 0, sizeof(ia));
+    ia.mel_db = s->pred; ia.spf = s->spf;
+    ia.n_utt = (int)s->B; ia.nb = s->n_fft / 2 + 1; ia.N = s->n_fft; ia.hop = s->hop; ia.n_mels = s->n_mels;
+    ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
+    return ia;
+}
+SynthArgs synth_args(const avse_stream* s, int64_t T0, int nt) {
+    SynthArgs sa;
+    sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
+    sa.T0 = T0; sa.nt = nt; sa.R = s->R;
+    return sa;
+}
+OlaArgs ola_args(const avse_stream* s, float* out, int64_t out_stride, int64_t e_old, int64_t T, int n_out) {
+    OlaArgs o;
+    o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
+    o.e_old = e_old; o.T = T; o.n_out = n_out; o.R = s->R;
+    return o;
 }
 
 // The next slot of the pinned staging ring, once the copy that last left it has been read: the only wait of a
@@ -696,31 +698,18 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
     // from here on a failure leaves the device state half updated: the session is broken until reset
     auto run = [&]() -> int {
         if (p.items.spec > 0) {
-            SpecStreamArgs a;
-            std::memset(&a, 0, sizeof(a));
+            SpecStreamArgs a = spec_args(s, samples, 0);  // row stride 0: + the row's sample_off
             a.tail_in = s->tail;                          // copies 0 / 1: the kernel picks by the row's parity
             a.tail_out = s->tail + (size_t)B * s->n_fft;
-            a.news = samples; a.news_stride = 0;          // + the row's sample_off
-            a.spf = s->spf; a.R = s->R; a.RS = s->RS;
-            a.twiddle = s->spec.twiddle; a.window = s->spec.window;
-            a.mel_start = s->spec.mel.start; a.mel_weight = s->spec.mel.weight;
-            std::memcpy(a.nq, s->spec.mel.seg_nq, sizeof(a.nq));
-            a.amin = s->amin; a.db_floor = s->db_floor;
-            a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
-            launch_spec_each(s->P, (unsigned)p.items.spec, st, a, d_rows, d_spec);
+            with_phases(s->P, [&](auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<P, true>), dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st,
+                                   a, d_rows, d_spec);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.items.route > 0) {
-            RouteArgs r;
-            std::memset(&r, 0, sizeof(r));
-            r.mel_ring = s->mel_ring; r.fmax_ring = s->fmax_ring; r.run_max = s->run_max;
-            r.net_in = s->net_in; r.mel_out = mel_db;
-            r.spf = s->spf; r.R = s->R; r.RS = s->RS; r.top_db = s->top_db;
-            r.vnew = reinterpret_cast<const char*>(video); r.vq = s->vq; r.vstage = s->vstage;
-            r.vbytes = (long long)s->vbytes;
-            r.RV = s->RV; r.B = B;
-            r.vec16 = (reinterpret_cast<uintptr_t>(video) & 15) == 0;
-            hipLaunchKernelGGL(k_stream_route_each, dim3((unsigned)p.items.route), dim3(256), 0, st, r, d_rows, d_route);
+            hipLaunchKernelGGL(k_stream_route<true>, dim3((unsigned)p.items.route), dim3(256), 0, st,
+                               route_args(s, video, mel_db), d_rows, d_route);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.clips > 0) {
@@ -729,22 +718,17 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             if (pred_db)
                 AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)p.clips * NMEL * s->spf,
                                               hipMemcpyDeviceToDevice, st));
-            IstftArgs ia;
-            std::memset(&ia, 0, sizeof(ia));
-            ia.mel_db = s->pred; ia.spf = s->spf;
-            ia.n_utt = B; ia.nb = s->n_fft / 2 + 1; ia.N = s->n_fft; ia.hop = s->hop; ia.n_mels = s->n_mels;
-            ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
-            SynthArgs sa;
-            sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
-            sa.T0 = 0; sa.nt = 0; sa.R = s->R;
-            launch_synth_each(s->P, (unsigned)p.items.synth, st, ia, sa, d_rows, d_synth);
+            with_phases(s->P, [&](auto P) {   // T0, nt: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<P, true>), dim3((unsigned)p.items.synth), dim3(64), 0, st,
+                                   istft_args(s), synth_args(s, 0, 0), d_rows, d_synth);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.items.ola > 0) {
-            OlaArgs o;
-            o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
-            o.e_old = 0; o.T = 0; o.n_out = 0; o.R = s->R;
-            launch_ola_each(s->P, (unsigned)p.items.ola, st, o, s->n_fft, s->hop, d_rows, d_ola);
+            with_phases(s->P, [&](auto P) {   // e_old, T, n_out: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<P, true>), dim3((unsigned)p.items.ola), dim3(256), 0, st,
+                                   ola_args(s, out, out_stride, 0, 0, 0), d_rows, d_ola);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         return 0;
@@ -779,8 +763,9 @@ int stream_step_spread(avse_stream* s, bool flush, const float* samples, int64_t
 int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new, int64_t sample_stride, const void* video,
                 int64_t v_new, const float* vmean, const float* vstd, float* out, int64_t out_stride, int64_t* host_n_out,
                 float* mel_db, float* pred_db, void* stream) {
-    const Counts c0 = stream_totals(s->n_fft, s->hop, s->spf, s->n, s->v, false);
-    const int64_t n2 = s->n + n_new, v2 = s->v + v_new;
+    const StreamState cur = s->st[0];   // every stream's: the caller saw `uniform`
+    const Counts c0 = stream_totals(s->n_fft, s->hop, s->spf, cur.n, cur.v, false);
+    const int64_t n2 = cur.n + n_new, v2 = cur.v + v_new;
     const Counts c1 = stream_totals(s->n_fft, s->hop, s->spf, n2, v2, flush);
     const int64_t slice = (int64_t)s->spf * s->hop;
     if (flush && n2 > slice * v2) return fail(AVSE_ERR_INVALID, "flush: more samples than the video slices cover (n > slice * v)");
@@ -796,41 +781,33 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
     hipStream_t st = (hipStream_t)stream;
     AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
     const int B = (int)s->B;
+    const int tail_blk = n_new > 0 ? 1 : 0;   // the tail copies swap when samples arrive
+    const StreamRow* no_rows = nullptr;       // the lock-step kernels read the call's scalars
+    const StreamItem* no_items = nullptr;
     // from here on a failure leaves the device state half updated: the session is broken until reset
     auto run = [&]() -> int {
         const int64_t nt = c1.frames - c0.frames;
         if (n_new > 0 || nt > 0) {
-            SpecStreamArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.tail_in = s->tail + (size_t)s->parity * B * s->n_fft;
-            a.tail_out = s->tail + (size_t)(s->parity ^ 1) * B * s->n_fft;
-            a.news = samples; a.news_stride = sample_stride;
-            a.n_old = s->n; a.n_new = n2;
+            SpecStreamArgs a = spec_args(s, samples, sample_stride);
+            a.tail_in = s->tail + (size_t)cur.parity * B * s->n_fft;
+            a.tail_out = s->tail + (size_t)(cur.parity ^ 1) * B * s->n_fft;
+            a.n_old = cur.n; a.n_new = n2;
             a.Lf = flush ? slice * v2 : -1;
             a.t0 = c0.frames; a.nt = (int)nt; a.nblk = (int)((nt + SCHUNK - 1) / SCHUNK);
-            a.spf = s->spf; a.R = s->R; a.RS = s->RS;
-            a.twiddle = s->spec.twiddle; a.window = s->spec.window;
-            a.mel_start = s->spec.mel.start; a.mel_weight = s->spec.mel.weight;
-            std::memcpy(a.nq, s->spec.mel.seg_nq, sizeof(a.nq));
-            a.amin = s->amin; a.db_floor = s->db_floor;
-            a.mel_ring = s->mel_ring; a.phase_ring = s->phase_ring; a.fmax_ring = s->fmax_ring;
-            const int tail_blk = n_new > 0 ? 1 : 0;
-            launch_spec(s->P, dim3(a.nblk + tail_blk, B), st, a);
+            with_phases(s->P, [&](auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<P, false>), dim3(a.nblk + tail_blk, B), dim3(64 * SWAVES), 0, st,
+                                   a, no_rows, no_items);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
-            if (tail_blk) s->parity ^= 1;
         }
         const int64_t nv = v2 - c0.slices;   // video slices not yet consumed, this call's included
         if (k_new > 0 || v_new > 0) {
-            RouteArgs r;
-            std::memset(&r, 0, sizeof(r));
-            r.mel_ring = s->mel_ring; r.fmax_ring = s->fmax_ring; r.run_max = s->run_max;
-            r.net_in = s->net_in; r.mel_out = mel_db;
-            r.k_old = c0.slices; r.k_new = (int)k_new; r.spf = s->spf; r.R = s->R; r.RS = s->RS; r.top_db = s->top_db;
-            r.vnew = reinterpret_cast<const char*>(video); r.vq = s->vq; r.vstage = s->vstage;
-            r.vbytes = (long long)s->vbytes; r.v_old = s->v; r.v_new = v_new;
-            r.nv = (int)nv; r.RV = s->RV; r.B = B;
-            r.vec16 = (reinterpret_cast<uintptr_t>(video) & 15) == 0;
-            hipLaunchKernelGGL(k_stream_route, dim3((unsigned)(ROUTE_X * B * nv + (k_new > 0 ? B : 0))), dim3(256), 0, st, r);
+            RouteArgs r = route_args(s, video, mel_db);
+            r.k_old = c0.slices; r.k_new = (int)k_new;
+            r.v_old = cur.v; r.v_new = v_new;
+            r.nv = (int)nv;
+            hipLaunchKernelGGL(k_stream_route<false>, dim3((unsigned)(ROUTE_X * B * nv + (k_new > 0 ? B : 0))), dim3(256), 0, st,
+                               r, no_rows, no_items);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (k_new > 0) {
@@ -839,23 +816,20 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
             if (pred_db)
                 AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)B * k_new * NMEL * s->spf,
                                               hipMemcpyDeviceToDevice, st));
-            IstftArgs ia;
-            std::memset(&ia, 0, sizeof(ia));
-            ia.mel_db = s->pred; ia.spf = s->spf; ia.n_slices = (int)k_new;
-            ia.n_utt = B; ia.T = (int)(k_new * s->spf); ia.nb = s->n_fft / 2 + 1; ia.N = s->n_fft; ia.hop = s->hop;
-            ia.n_mels = s->n_mels;
-            ia.pinvT = s->ist.pinvT; ia.twiddle = s->ist.twiddle; ia.window = s->ist.window;
-            SynthArgs sa;
-            sa.phase_ring = s->phase_ring; sa.frame_ring = s->frame_ring;
-            sa.T0 = c0.slices * s->spf; sa.nt = ia.T; sa.R = s->R;
-            launch_synth(s->P, dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B), st, ia, sa);
+            IstftArgs ia = istft_args(s);
+            ia.n_slices = (int)k_new;
+            ia.T = (int)(k_new * s->spf);
+            with_phases(s->P, [&](auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<P, false>), dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B),
+                                   dim3(64), 0, st, ia, synth_args(s, c0.slices * s->spf, ia.T), no_rows, no_items);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (n_out > 0) {
-            OlaArgs o;
-            o.frame_ring = s->frame_ring; o.window = s->ist.window; o.out = out; o.out_stride = out_stride;
-            o.e_old = c0.emitted; o.T = c1.slices * s->spf; o.n_out = (int)n_out; o.R = s->R;
-            launch_ola(s->P, dim3((unsigned)((n_out + 255) / 256), B), st, o, s->n_fft, s->hop);
+            with_phases(s->P, [&](auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<P, false>), dim3((unsigned)((n_out + 255) / 256), B), dim3(256), 0,
+                                   st, ola_args(s, out, out_stride, c0.emitted, c1.slices * s->spf, (int)n_out), no_rows, no_items);
+            });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         return 0;
@@ -864,10 +838,7 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
         s->broken = true;
         return rc;
     }
-    s->n = n2;
-    s->v = v2;
-    if (flush) s->flushed = true;
-    stream_set_all(s);
+    stream_set_all(s, StreamState{n2, v2, (uint8_t)flush, (uint8_t)(cur.parity ^ tail_blk)});
     return debug_poll(stream);
 }
 
@@ -989,9 +960,9 @@ int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_
     if (!s->uniform)
         return stream_step_spread(s, false, samples, n_new, sample_stride, video, v_new, vmean, vstd, out, out_stride,
                                   host_n_out, mel_db, pred_db, stream);
-    if (s->flushed) return fail(AVSE_ERR_INVALID, "push after flush: only avse_stream_reset is legal");
+    if (s->st[0].flushed) return fail(AVSE_ERR_INVALID, "push after flush: only avse_stream_reset is legal");
     if (v_new > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
-    if (n_new > (1LL << 40) - s->n || v_new > (1LL << 30) - s->v) return fail(AVSE_ERR_INVALID, "counts too large");
+    if (n_new > (1LL << 40) - s->st[0].n || v_new > (1LL << 30) - s->st[0].v) return fail(AVSE_ERR_INVALID, "counts too large");
     return stream_step(s, false, samples, n_new, sample_stride, video, v_new, vmean, vstd, out, out_stride, host_n_out, mel_db,
                        pred_db, stream);
 }
@@ -1005,7 +976,7 @@ int avse_stream_flush(avse_stream* s, const float* vmean, const float* vstd, flo
     if (!s->uniform)
         return stream_step_spread(s, true, nullptr, 0, 0, nullptr, 0, vmean, vstd, out, out_stride, host_n_out, mel_db, pred_db,
                                   stream);
-    if (s->flushed) return fail(AVSE_ERR_INVALID, "flush after flush: only avse_stream_reset is legal");
+    if (s->st[0].flushed) return fail(AVSE_ERR_INVALID, "flush after flush: only avse_stream_reset is legal");
     return stream_step(s, true, nullptr, 0, 0, nullptr, 0, vmean, vstd, out, out_stride, host_n_out, mel_db, pred_db, stream);
 }
 
@@ -1045,11 +1016,9 @@ int avse_stream_reset_each(avse_stream* s, const uint8_t* which, void* stream) {
         if (which[b]) ids[n++] = b;
     if (int rc = stream_stage_upload(s, sizeof(int) * (size_t)n, st)) return rc;
     const int* ids_d = reinterpret_cast<const int*>(s->tables.p.get());
-    if (s->P == 1)
-        hipLaunchKernelGGL(k_stream_reset_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
-    else
-        hipLaunchKernelGGL(k_stream_reset_n_each, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d,
-                           B, s->n_fft);
+    with_phases(s->P, [&](auto P) {
+        hipLaunchKernelGGL(k_stream_reset<P>, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
+    });
     AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
     for (int b = 0; b < B; ++b)
         if (which[b]) s->st[b] = StreamState{0, 0, 0, 0};

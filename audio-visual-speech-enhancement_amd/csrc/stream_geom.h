@@ -1,7 +1,7 @@
 // Host-only geometry of a streaming session (no HIP header): the totals of one stream (stream_totals, shared by the
 // lock-step and the per-stream calls), and for a per-stream push (include/avse.h avse_stream_push_each) the refusal
 // decision, one row per stream and one item table per kernel, block -> (stream, chunk).  StreamRow / StreamItem are
-// also the device-side layouts (stream.hip uploads them and the k_stream_*_each kernels read them).  Nothing here
+// also the device-side layouts (stream.hip uploads them and the EACH instances of its kernels read them).  Nothing here
 // allocates: the caller owns every array (the session sizes them at create from stream_item_caps).
 #pragma once
 #include <algorithm>

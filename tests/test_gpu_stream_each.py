@@ -291,3 +291,51 @@ def test_refusals_name_the_stream_and_leave_no_trace(gpu):
         outs[b].append(got[b])
         assert same_bits(torch.cat(outs[b]).cpu().numpy(), alone(dtype, b, SLICES[0], SLICES[1])["out"]), b
     assert enh.range_bits == 0
+
+
+# ---- 8. the video's alignment ----------------------------------------------------------------------------------
+def test_video_off_a_16_byte_boundary_gives_the_aligned_bits(gpu):
+    """tests/test_gpu_streaming.py's test of this name through avse_stream_push_each (straight on the C-ABI: ops packs
+    the streams' video into a fresh, aligned tensor): both streams of a B = 2 session take the same two slices from a
+    packed video 4 bytes past a 16-byte boundary and from an aligned one, and are flushed."""
+    from avse_amd import _lib, ops
+    from avse_amd.pipeline import StreamEnhancer
+    from test_gpu_streaming import offset_video
+    B = 2
+    x, video, mean, std, _ = inputs()
+    md, sd = ops.to_device(mean), ops.to_device(std)
+    xd, vd = ops.to_device(x[:B, :6400]), ops.to_device(video[:B, :2])
+    lib = _lib.load()
+    enh = StreamEnhancer(weights("float32"), B)
+    h, st = enh.session.handle, _lib.stream_handle(xd.device)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+
+    def c_push(samples, vids, n_new, v_new, flush):
+        n, v, fl = np.full(B, n_new, np.int64), np.full(B, v_new, np.int64), np.full(B, flush, np.uint8)
+        off = np.arange(B, dtype=np.int64) * n_new
+        out = torch.zeros((B, 3400), dtype=torch.float32, device=xd.device)
+        mel, pred = (torch.zeros((B, 80, 20), dtype=torch.float32, device=xd.device) for _ in range(2))
+        n_out, k_new = np.full(B, -7, np.int64), np.full(B, -7, np.int64)
+        rc = lib.avse_stream_push_each(h, _lib.ptr(samples), ptr(off), ptr(n), _lib.ptr(vids), ptr(v), ptr(fl), _lib.ptr(md),
+                                       _lib.ptr(sd), _lib.ptr(out), 3400, ptr(n_out), _lib.ptr(mel), _lib.ptr(pred),
+                                       ptr(k_new), st)
+        assert rc == 0, lib.avse_last_error()
+        assert n_out[0] == n_out[1] and k_new[0] == k_new[1]
+        return out[:, :n_out[0]], mel[:B * k_new[0]], pred[:B * k_new[0]]
+
+    runs = []
+    for floats in (1, 0):
+        enh.reset()
+        got = []
+        for k in range(2):
+            vid = offset_video(vd[:, k].contiguous(), floats)       # packed: stream 0's slice, then stream 1's
+            got.append(c_push(xd[:, 3200 * k:3200 * k + 3200].contiguous(), vid, 3200, 1, 0))
+        got.append(c_push(None, None, 0, 0, 1))
+        assert [g[0].shape[1] for g in got] == [0, 2880, 3360] and [g[1].shape[0] for g in got] == [0, B, B]
+        runs.append([torch.cat([g[0] for g in got], dim=1).cpu().numpy()] +
+                    [torch.cat([g[i] for g in got]).cpu().numpy() for i in (1, 2)])
+    for key, off, aligned in zip(KEYS, *runs):
+        assert np.isfinite(off).all() and same_bits(off, aligned), key
+    # and they are the lock-step session's
+    ref = run_stream(StreamEnhancer(weights("float32"), B), x[:B, :6400], video[:B, :2], [3200, 3200], [1, 1])
+    assert same_bits(runs[0][0], ref["out"])

@@ -1,7 +1,7 @@
 """Streaming at 32 and 48 kHz ("32 and 48 kHz"): frames of N = 640 P samples (P = 2, 3) computed as
-P interleaved 640-point frames (csrc/frame_poly.h; k_stream_spec_p / k_stream_synth_p / k_stream_ola_n) against the
-float64 oracle pipeline at that rate, against the offline device path (a direct DFT at these rates), and against
-themselves under every cut of the input.
+P interleaved 640-point frames (csrc/frame_poly.h; the P = 2, 3 instances of k_stream_spec / k_stream_synth /
+k_stream_ola) against the float64 oracle pipeline at that rate, against the offline device path (a direct DFT at these
+rates), and against themselves under every cut of the input.
 
 Shapes are those of tests/test_gpu_streaming.py scaled by P: B <= 3 streams of S = 4 slices, L = 12800 P samples, that
 file's video, normaliser and model.  The gates are that file's: DB_MAX / DB_RMS for the mel-dB the network sees, its

@@ -340,3 +340,41 @@ def test_refusals_leave_the_session_as_it_was(gpu):
     clean = run_stream(StreamEnhancer(dw, 1), x[:1], video[:1], [3200] * 4, video_at=[1] * 4)
     assert same_bits(torch.cat(outs, dim=1).cpu().numpy(), clean["out"])
     assert enh.range_bits == 0
+
+
+# ---- 7. the video's alignment -----------------------------------------------------------------------------------
+def offset_video(vd, floats):
+    """vd's values in a contiguous view `floats` floats into a fresh buffer: the data pointer is 4 * floats bytes past
+    the buffer's (16-byte aligned) start."""
+    buf = torch.empty(vd.numel() + 4, dtype=vd.dtype, device=vd.device)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[floats:floats + vd.numel()].view(vd.shape)
+    view.copy_(vd)
+    assert view.is_contiguous() and view.data_ptr() % 16 == (4 * floats) % 16
+    return view
+
+
+def test_video_off_a_16_byte_boundary_gives_the_aligned_bits(gpu):
+    """k_stream_route moves a call's video slices 16 bytes per lane when the video pointer is 16-byte aligned and 4 bytes
+    per lane otherwise.  The same two slices go to a B = 2 session from tensors 4 bytes past a 16-byte boundary and
+    from aligned ones: push 1 queues slice 0 (19 frames: no slice is complete), push 2 stages it from the queue and
+    queues slice 1, the flush stages that one.  Everything the session returns must be the same bits."""
+    from avse_amd import ops
+    from avse_amd.pipeline import StreamEnhancer
+    B = 2
+    x, video, mean, std, _ = inputs()
+    md, sd = ops.to_device(mean), ops.to_device(std)
+    xd, vd = ops.to_device(x[:B, :6400]), ops.to_device(video[:B, :2])
+    enh = StreamEnhancer(weights("float32"), B)
+    runs = []
+    for floats in (1, 0):
+        enh.reset()
+        got = []
+        for k in range(2):
+            vid = offset_video(vd[:, k:k + 1].contiguous(), floats)
+            got.append(enh.push(xd[:, 3200 * k:3200 * k + 3200].contiguous(), vid, md, sd, return_spectrograms=True))
+        got.append(enh.flush(md, sd, return_spectrograms=True))
+        runs.append([torch.cat([g[i] for g in got], dim=1).cpu().numpy() for i in range(3)])
+    assert runs[0][0].shape == (B, 6240) and runs[0][1].shape == runs[0][2].shape == (B, 2, 80, 20)
+    for key, off, aligned in zip(("out", "mel", "pred"), *runs):
+        assert np.isfinite(off).all() and same_bits(off, aligned), key

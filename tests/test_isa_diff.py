@@ -92,6 +92,57 @@ def test_compare_same_under_relocation_and_cuid():
     assert [(s, same) for s, same, _ in rows] == [("_Z5k_oneILi0EEvPf", True), ("_Z5k_twoPf", True)]
 
 
+def _renamed(disasm, notes):
+    """k_two as an instance k_two<1> of a template with one more argument: another name (in its notes and in its own
+    branch target too), another kernarg layout, the object's trailing padding under it."""
+    new = "_Z5k_twoILi1EEvPfPKi"
+    disasm = disasm.replace("v_mov_b32_e32 v2, 0  ", "s_cbranch_scc1 2      ").replace("7E040280", "BF850002 <_Z5k_twoPf+0x10>")
+    notes = notes.replace("    .name:           _Z5k_twoPf\n", "    .name:           _Z5k_twoPf\n    .sgpr_count:     9\n")
+    d2 = disasm.replace("_Z5k_twoPf", new) + "\t...\n"
+    n2 = notes.replace("_Z5k_twoPf", new).replace("  - .agpr_count:     0\n    .name:           " + new,
+                                                   "  - .agpr_count:     0\n    .args:\n      - .offset:         8\n"
+                                                   "    .name:           " + new)
+    return disasm, notes, d2, n2, new
+
+
+def test_compare_renamed_pair():
+    mod = _load()
+    d1, n1, d2, n2, new = _renamed(DISASM, NOTES)
+    a, b = mod.kernels_of_text(d1, n1), mod.kernels_of_text(d2, n2)
+    assert any("_Z5k_twoPf+0x10" in l for l in a["_Z5k_twoPf"][0]) and any(".offset" in l for l in b[new][1])
+    # unmapped: the kernel is missing on either side
+    assert {s: same for s, same, _ in mod.compare(a, b)} == {"_Z5k_oneILi0EEvPf": True, "_Z5k_twoPf": False, new: False}
+    # mapped by symbol or by a substring: name, own branch target, kernarg layout and trailing padding do not count
+    for old_pat, new_pat in (("_Z5k_twoPf", new), ("k_twoPf", "k_twoILi1E")):
+        rows = mod.compare(a, b, [(old_pat, new_pat)])
+        assert [(s, same) for s, same, _ in rows] == [(f"_Z5k_twoPf -> {new}", True), ("_Z5k_oneILi0EEvPf", True)]
+    # an instruction or a register count of the mapped pair still does
+    rows = mod.compare(a, mod.kernels_of_text(d2.replace("s_cbranch_scc1 2", "s_cbranch_scc0 2"), n2), [("k_twoPf", "k_twoILi1E")])
+    assert [same for _, same, _ in rows] == [False, True] and any("instructions" in l for l in rows[0][2])
+    rows = mod.compare(a, mod.kernels_of_text(d2, n2.replace(".sgpr_count:     9", ".sgpr_count:     10")), [("k_twoPf", "k_twoILi1E")])
+    assert [same for _, same, _ in rows] == [False, True] and any("resources" in l for l in rows[0][2])
+    # one old kernel may stand in several pairs; a pattern that names no symbol, or several, pairs nothing
+    rows = mod.compare(a, b, [("k_twoPf", "k_twoILi1E"), ("k_twoPf", "k_oneILi0E")])
+    assert [(s, same) for s, same, _ in rows] == [(f"_Z5k_twoPf -> {new}", True), ("_Z5k_twoPf -> _Z5k_oneILi0EEvPf", False),
+                                                  ("_Z5k_oneILi0EEvPf", False)]
+    assert mod.resolve("k_", a) is None and mod.resolve("k_three", a) is None and mod.resolve("k_one", a) == "_Z5k_oneILi0EEvPf"
+    assert {s: same for s, same, _ in mod.compare(a, b, [("k_", new)])} == {"_Z5k_oneILi0EEvPf": True, "_Z5k_twoPf": False, new: False}
+
+
+def test_read_map(tmp_path):
+    mod = _load()
+    path = tmp_path / "renames.txt"
+    path.write_text("# old new\nk_twoPf   k_twoILi1E   # the instance\n\nk_a k_b\n")
+    assert mod.read_map(str(path)) == [("k_twoPf", "k_twoILi1E"), ("k_a", "k_b")]
+    path.write_text("k_twoPf\n")
+    try:
+        mod.read_map(str(path))
+    except ValueError as e:
+        assert "OLD NEW" in str(e)
+    else:
+        raise AssertionError("a line with one word was accepted")
+
+
 def test_compare_pins_a_difference_on_its_kernel():
     mod = _load()
     base = mod.kernels_of_text(DISASM, NOTES)

@@ -8,9 +8,17 @@ lines naming the per-source __hip_cuid_<hash> symbol are dropped; what is left i
 Prints `same` or `DIFF` per symbol and exits 1 on any difference (2: a directory holds no objects).  It judges
 nothing beyond equality.
 
+A kernel that was renamed is paired by hand: --map OLD=NEW (repeatable) or --map-file FILE (lines `OLD NEW`, `#`
+comments), each side a symbol or a substring that names exactly one symbol of an object of its side; one symbol may
+stand in several pairs (a kernel that became two instances).  A mapped pair is compared by its instructions (its own
+name in branch targets aside) and, of the notes, by the register, LDS, scratch and spill fields only: the name, the
+symbol and the kernarg layout differ by design.
+
     python tools/isa_diff.py <parent checkout>/csrc/build <this checkout>/csrc/build
     python tools/isa_diff.py <parent checkout>/csrc/build_debug <this checkout>/csrc/build_debug     (make DEBUG=1)
+    python tools/isa_diff.py --map k_stream_specENS=k_stream_specILi1ELb0E --map-file renames.txt A B
 """
+import argparse
 import difflib
 import os
 import re
@@ -25,6 +33,9 @@ ADDRESS = re.compile(r"//\s*[0-9A-Fa-f]+:")          # "// 000000001700: C00E050
 CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
 KERNEL_ENTRY = re.compile(r"^  - \.")                 # first key of one amdhsa.kernels entry
 KERNEL_NAME = re.compile(r"^\s+\.name:\s+(\S+)")
+# the note fields a renamed kernel is still held to
+RESOURCE = re.compile(r"^\s+\.(agpr_count|sgpr_count|vgpr_count|sgpr_spill_count|vgpr_spill_count|"
+                      r"group_segment_fixed_size|private_segment_fixed_size|uses_dynamic_stack):")
 
 
 def normalise(text):
@@ -96,27 +107,77 @@ def kernels(obj, tmp):
                            run(f"{LLVM}/llvm-readelf", "--notes", co))
 
 
-def compare(ka, kb):
-    """[(symbol, same, detail lines)] over the union of two kernels() results."""
-    rows = []
-    for s in sorted(set(ka) | set(kb)):
-        if s not in ka or s not in kb:
-            rows.append((s, False, ["only in " + ("A" if s in ka else "B")]))
+def _detail(pairs):
+    detail = []
+    for what, x, y in pairs:
+        if x != y:
+            d = [l for l in difflib.unified_diff(x, y, "A", "B", lineterm="", n=0) if not l.startswith(("---", "+++"))]
+            detail += [f"{what}: {sum(l[0] in '+-' for l in d)} lines differ"] + d[:12]
+    return detail
+
+
+def resolve(pattern, symbols):
+    """The one symbol `pattern` names (itself, or as a substring), or None when it names none or several."""
+    if pattern in symbols:
+        return pattern
+    hits = [s for s in symbols if pattern in s]
+    return hits[0] if len(hits) == 1 else None
+
+
+def compare(ka, kb, renames=()):
+    """[(symbol or "old -> new", same, detail lines)]: the pairs of `renames` ((old, new) patterns, see resolve) that
+    both sides hold, then the union of the symbols of two kernels() results that stand in no such pair."""
+    rows, paired_a, paired_b = [], set(), set()
+    for old, new in renames:
+        sa, sb = resolve(old, ka), resolve(new, kb)
+        if sa is None or sb is None:
             continue
-        detail = []
-        for what, x, y in (("instructions", ka[s][0], kb[s][0]), ("notes", ka[s][1], kb[s][1])):
-            if x != y:
-                d = [l for l in difflib.unified_diff(x, y, "A", "B", lineterm="", n=0) if not l.startswith(("---", "+++"))]
-                detail += [f"{what}: {sum(l[0] in '+-' for l in d)} lines differ"] + d[:12]
+        paired_a.add(sa)
+        paired_b.add(sb)
+        # (a closing "...": the section's trailing padding, which the disassembler prints under the object's last kernel)
+        own = lambda sym, lines: [l.replace(sym, "<self>") for l in (lines[:-1] if lines[-1:] == ["..."] else lines)]
+        res = lambda lines: [l.strip() for l in lines if RESOURCE.match(l)]
+        detail = _detail((("instructions", own(sa, ka[sa][0]), own(sb, kb[sb][0])),
+                          ("resources", res(ka[sa][1]), res(kb[sb][1]))))
+        rows.append((f"{sa} -> {sb}", not detail, detail))
+    in_a, in_b = set(ka) - paired_a, set(kb) - paired_b
+    for s in sorted(in_a | in_b):
+        if s not in in_a or s not in in_b:
+            rows.append((s, False, ["only in " + ("A" if s in in_a else "B")]))
+            continue
+        detail = _detail((("instructions", ka[s][0], kb[s][0]), ("notes", ka[s][1], kb[s][1])))
         rows.append((s, not detail, detail))
     return rows
 
 
+def read_map(path):
+    """[(old, new)] of a rename file: one `OLD NEW` per line, blank lines and `#` comments skipped."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            words = line.split("#")[0].split()
+            if len(words) == 2:
+                out.append((words[0], words[1]))
+            elif words:
+                raise ValueError(f"{path}: expected `OLD NEW`, got {line.rstrip()!r}")
+    return out
+
+
 def main(argv):
-    if len(argv) != 3:
-        print(__doc__)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW", help="pair a renamed kernel (repeatable)")
+    ap.add_argument("--map-file", action="append", default=[], metavar="FILE", help="lines `OLD NEW`")
+    ap.add_argument("a")
+    ap.add_argument("b")
+    args = ap.parse_args(argv[1:])
+    a, b = args.a, args.b
+    renames = [tuple(m.split("=", 1)) for m in args.map if "=" in m]
+    if len(renames) != len(args.map):
+        print("--map takes OLD=NEW")
         return 2
-    a, b = argv[1], argv[2]
+    for path in args.map_file:
+        renames += read_map(path)
+    used = set()
     names = sorted(set(f for f in os.listdir(a) if f.endswith(".o")) & set(f for f in os.listdir(b) if f.endswith(".o")))
     if not names:
         print("no object file present in both directories")
@@ -124,12 +185,18 @@ def main(argv):
     ndiff = nsym = 0
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         for name in names:
-            for sym, same, detail in compare(kernels(os.path.join(a, name), ta), kernels(os.path.join(b, name), tb)):
+            ka, kb = kernels(os.path.join(a, name), ta), kernels(os.path.join(b, name), tb)
+            used |= {r for r in renames if resolve(r[0], ka) is not None and resolve(r[1], kb) is not None}
+            for sym, same, detail in compare(ka, kb, renames):
                 nsym += 1
                 ndiff += not same
                 print(f"{'same' if same else 'DIFF'}  {name}  {sym}")
                 for line in detail:
                     print("        " + line)
+    for old, new in renames:
+        if (old, new) not in used:
+            ndiff += 1
+            print(f"DIFF  --map {old}={new}: names no pair of symbols (none, or several, on a side)")
     print(f"{nsym} kernel symbols in {len(names)} objects: {ndiff} differ")
     return 1 if ndiff else 0
 
