@@ -42,14 +42,15 @@ __device__ __forceinline__ void dft5(float2& x0, float2& x1, float2& x2, float2&
 }
 
 // 20-point forward DFT of v[n2] (n2 = 5a + b, k2 = c + 4d) in registers; result Y[c + 4d] in v[5c + d].
-// tw = W640^k table (W20^{bc} = W640^{32 bc}).
+// tw = W640^k table (W20^{bc} = W640^{32 bc}); TS: the table's step per W20 (40 for a W800^k table, frame800.h).
+template <int TS = 32>
 __device__ __forceinline__ void dft20(float2 (&v)[20], const float2* __restrict__ tw) {
 #pragma unroll
     for (int b = 0; b < 5; ++b) dft4(v[b], v[5 + b], v[10 + b], v[15 + b]);
 #pragma unroll
     for (int b = 1; b < 5; ++b)
 #pragma unroll
-        for (int c = 1; c < 4; ++c) v[5 * c + b] = cmul(v[5 * c + b], tw[32 * b * c]);
+        for (int c = 1; c < 4; ++c) v[5 * c + b] = cmul(v[5 * c + b], tw[TS * b * c]);
 #pragma unroll
     for (int c = 0; c < 4; ++c) dft5(v[5 * c], v[5 * c + 1], v[5 * c + 2], v[5 * c + 3], v[5 * c + 4]);
 }

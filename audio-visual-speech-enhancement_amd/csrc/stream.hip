@@ -31,8 +31,9 @@
 //   k_stream_synth  k_istft640's body (frame640.h synth_frames) on the predicted frames and the ring's phases
 //   k_stream_ola    k_ola's sample (frame640.h ola_sample) over the frame ring for the samples that became final
 //
-// Each launch is one kernel template, k_stream_spec<P, EACH>, k_stream_route<EACH>, k_stream_synth<P, EACH>,
-// k_stream_ola<P, EACH> (and k_stream_reset<P> for avse_stream_reset_each), with its body written once in the kernel:
+// Each launch is one kernel template, k_stream_spec<BASE, P, EACH>, k_stream_route<EACH>, k_stream_synth<BASE, P, EACH>,
+// k_stream_ola<BASE, P, EACH> (and k_stream_reset<BASE, P> for avse_stream_reset_each), with its body written once in
+// the kernel:
 //   EACH  Streams need not move together (avse_stream_push_each): the session keeps its counters per stream,
 //         stream_geom.h turns a call's per-stream counts into one row per stream and one item table per kernel (block ->
 //         stream, chunk), and the EACH instances take the row's counters in place of the call's scalars (`if constexpr
@@ -42,6 +43,9 @@
 //   P     n_fft = 640 P: 1 at 16 kHz; at 32 and 48 kHz (P = 2, 3) the analysis and the synthesis compute each frame as P
 //         interleaved 640-point frames (frame_poly.h).  N, the hop and N / 2 are compile-time everywhere;
 //         k_stream_route and the forward do not depend on P.
+//   BASE  the frame arithmetic, n_fft = BASE P: 640 (frame640.h, frame_poly.h: 25-fps video at 16 / 32 / 48 kHz, P = 1,
+//         2, 3) or 800 (frame800.h: 30-fps video at 24 / 48 kHz, P = 1, 2; bins 0 .. 266 of a 20 x 20 split).  The
+//         rings, the mel tables, k_stream_route, the forward and the host geometry do not depend on it.
 // A kernel template, not a function taking the argument struct: the by-value kernel argument never leaves the kernel,
 // so each of its fields is still loaded where it is used ("Independent streams").
 #include <algorithm>
@@ -52,14 +56,16 @@
 
 #include "ctx.h"
 #include "frame640.h"
+#include "frame800.h"
 #include "frame_poly.h"
 #include "spec_tables.h"
 #include "stream_geom.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap (as stft.hip)
-#define AVSE_SPEC_WPE(P)
-#else   // the 16 kHz analysis is capped at 4 waves per SIMD's registers; the P-phase instances are not (1: no cap)
-#define AVSE_SPEC_WPE(P) __attribute__((amdgpu_waves_per_eu((P) == 1 ? 4 : 1)))
+#define AVSE_SPEC_WPE(BASE, P)
+#else   // the 16 kHz analysis is capped at 4 waves per SIMD's registers; the P-phase and the 800-point instances are not
+        // (1: no cap)
+#define AVSE_SPEC_WPE(BASE, P) __attribute__((amdgpu_waves_per_eu((BASE) == 640 && (P) == 1 ? 4 : 1)))
 #endif
 
 namespace avse {
@@ -118,10 +124,17 @@ __device__ __forceinline__ float frame_sample(const SpecStreamArgs& a, int b, lo
 // wave's three LDS frame slots (LDS is the P == 1 size plus the P - 1 further window phases), X[k] and X[320 - k] of
 // the lane's step-3 items accumulate in registers, and the magnitudes follow the last phase.  The rings, the mel tables
 // and everything after step 3 are the same (the band-limited bins 0 .. 320 are the same 25-Hz bins).
-template <int P, bool EACH>
-__global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(SpecStreamArgs a, const StreamRow* __restrict__ rows,
-                                                                              const StreamItem* __restrict__ items) {
-    constexpr int N = 640 * P;
+//
+// BASE == 800 (30-fps video, frame800.h): N = 800 P, a frame starts at sample P (200 t - 400), lanes (frame, n1 < 20) run
+// the 20 x 20 split (lanes 60 .. 63 idle in steps 1 and 2), step 3 takes the pairs (k, 400 - k), k <= 200, into the
+// accumulators for P = 1 too, and only bins 0 .. 266 (the 30-Hz bins under 8 kHz) reach the phase ring and the mel step.
+template <int BASE, int P, bool EACH>
+__global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(BASE, P) void k_stream_spec(SpecStreamArgs a, const StreamRow* __restrict__ rows,
+                                                                                    const StreamItem* __restrict__ items) {
+    static_assert(BASE == 640 || BASE == 800, "the frame arithmetic of frame640.h or frame800.h");
+    constexpr int N = BASE * P;
+    constexpr int ZS = BASE == 640 ? spec640::ZS : spec800::ZS;      // LDS slot of a frame
+    constexpr int KPAD = BASE == 640 ? 321 : spec800::KTOP + 1;      // first bin past the band-limited spectrum
     int b;
     unsigned blk;
     if constexpr (EACH) {
@@ -142,9 +155,9 @@ __global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(Sp
         blk = blockIdx.x;
     }
     __shared__ float2 zbuf[SWAVES * FPG * ZS];
-    __shared__ float2 twl[640];        // W640^k = W_N^{P k}
-    __shared__ v2f ut2[161];           // U = -i W640^k / 2 (untangling)
-    __shared__ float2 winl[P * 320];   // phase r of the window as the pairs window_frame reads
+    __shared__ float2 twl[BASE];       // W640^k = W_N^{P k} (W800^k)
+    __shared__ v2f ut2[BASE / 4 + 1];  // U = -i W640^k / 2 (untangling)
+    __shared__ float2 winl[P * (BASE / 2)];   // phase r of the window as the pairs window_frame reads
     __shared__ float4 melw4[NMEL * MW / 4];
     __shared__ int mel_st[NMEL];
 
@@ -156,18 +169,18 @@ __global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(Sp
         }
         return;
     }
-    for (int i = tid; i < 640; i += 64 * SWAVES) twl[i] = a.twiddle[P * i];
-    for (int k = tid; k < 161; k += 64 * SWAVES) {
+    for (int i = tid; i < BASE; i += 64 * SWAVES) twl[i] = a.twiddle[P * i];
+    for (int k = tid; k < BASE / 4 + 1; k += 64 * SWAVES) {
         const float2 w = a.twiddle[P * k];
         ut2[k] = v2f{0.5f * w.y, -0.5f * w.x};
     }
-    for (int i = tid; i < P * 320; i += 64 * SWAVES) {
+    for (int i = tid; i < P * (BASE / 2); i += 64 * SWAVES) {
         if constexpr (P == 1) winl[i] = reinterpret_cast<const float2*>(a.window)[i];
-        else winl[i] = spec_poly::window_pair<P>(a.window, i / 320, i % 320);
+        else winl[i] = spec_poly::window_pair<P>(a.window, i / (BASE / 2), i % (BASE / 2));
     }
     for (int i = tid; i < NMEL * MW / 4; i += 64 * SWAVES) melw4[i] = reinterpret_cast<const float4*>(a.mel_weight)[i];
     for (int i = tid; i < NMEL; i += 64 * SWAVES) mel_st[i] = a.mel_start[i];
-    if constexpr (P != 1) __syncthreads();   // (P == 1 loads its samples first)
+    if constexpr (P != 1 || BASE != 640) __syncthreads();   // (the 16 kHz instance loads its samples first)
 
     const int g = FPG * wave;                                  // this wave's first frame in the block
     const int nf = min(SCHUNK, a.nt - SCHUNK * (int)blk);
@@ -176,7 +189,55 @@ __global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(Sp
     const int f1 = lane >> 4, n1 = lane & 15;
     float2* zw;
     // ---- steps 1 to 3: the complex frame into the phase ring, its magnitudes into LDS ----
-    if constexpr (P == 1) {
+    if constexpr (BASE == 800) {
+        const int f8 = lane / 20, n8 = lane - 20 * (lane / 20);   // (frame, n1) in step 1, (frame, k2) in step 2
+        const bool act = f8 < ng;                                   // (lanes 60 .. 63: f8 == 3 == FPG, never active)
+        const long long s0 = ((tw0 + f8) * 200 - 400) * P;
+        const bool whole = s0 >= a.n_old && s0 + N <= a.n_new && (a.Lf < 0 || s0 + N <= a.Lf);   // all in this call's samples
+        zw = zbuf + wave * FPG * ZS;
+        v2f ax[spec800::IT3], ay[spec800::IT3];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            float2 x[20];
+#pragma unroll
+            for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
+            if (act) {
+                if (whole)
+                    spec800::load_phase<P>(x, a.news + b * a.news_stride + (s0 - a.n_old), n8, r);
+                else
+                    spec800::load_phase<P>(x, [&](long long i) { return frame_sample<N>(a, b, i); }, s0, n8, r);
+            }
+            // steps 1 and 2 of the 20 x 20 split on the phase's 800 samples, wave-local
+            v2f v[20];
+            spec800::window_frame(v, x, winl + r * 400, n8);
+            if (act) spec800::dft20_store(v, twl, zw + f8 * ZS, n8);
+            wave_lds_sync();
+            {
+                v2f* zf = reinterpret_cast<v2f*>(zw + min(f8, FPG - 1) * ZS);
+                if (act) spec800::row_load(v, zf, n8);
+                wave_lds_sync();
+                if (act) spec800::row_store(v, zf, n8);
+            }
+            wave_lds_sync();
+            // step 3 of the phase: W_N^{r k} F_r[k] into the accumulators
+            spec800::accumulate<P>(ax, ay, zw, ut2, a.twiddle, r, ng, lane);
+            wave_lds_sync();   // the next phase (or the magnitudes below) overwrites the slots
+        }
+#pragma unroll
+        for (int j = 0; j < spec800::IT3; ++j) {   // item = (f, k <= 200): bins k and 400 - k, the latter up to bin 266
+            const int it = lane + 64 * j;
+            if (it >= ng * 201) break;
+            const int f = it / 201, k = it - 201 * f;
+            float2* o = a.phase_ring + ((long long)b * a.R + (int)((tw0 + f) % a.R)) * 321;
+            float* mf = reinterpret_cast<float*>(zw + f * ZS);
+            o[k] = make_float2(ax[j].x, ax[j].y);
+            mf[k] = pk_abs(ax[j]);
+            if (k != 200 && 400 - k < KPAD) {
+                o[400 - k] = make_float2(ay[j].x, ay[j].y);
+                mf[400 - k] = pk_abs(ay[j]);
+            }
+        }
+    } else if constexpr (P == 1) {
         float2 x[20];
 #pragma unroll
         for (int n2 = 0; n2 < 20; ++n2) x[n2] = make_float2(0.f, 0.f);
@@ -287,7 +348,7 @@ __global__ __launch_bounds__(64 * SWAVES) AVSE_SPEC_WPE(P) void k_stream_spec(Sp
     }
     for (int it = lane; it < FPG * MW; it += 64) {   // bins [321, 321 + MW) are read by the padded band dots
         const int f = it / MW, j = it - MW * f;
-        reinterpret_cast<float*>(zw + f * ZS)[321 + j] = 0.f;
+        reinterpret_cast<float*>(zw + f * ZS)[KPAD + j] = 0.f;
     }
     wave_lds_sync();
     // ---- step 4: Slaney mel + dB, item = (m, f) as k_spec640; unclamped, into the frame's slice slot ----
@@ -437,7 +498,8 @@ struct SynthArgs {
 // One group of FPG frames from t0 of stream b's s.nt predicted frames, into the frame ring's slots of 640 P samples;
 // clip(sl) is the clip of a.mel_db that holds the stream's slice sl of this call.  (Its callers are distinct instances,
 // Clip being a lambda type: one LDS allocation of synth_frames per kernel.)  P > 1: a.N = 640 P, frame_poly.h.
-template <int P, class Clip>
+// BASE == 800: a.N = 800 P, frame800.h (P = 1 and 2 alike); the ring's rows stay 321 wide, bins 0 .. 266 are read.
+template <int BASE, int P, class Clip>
 __device__ __forceinline__ void synth_group(const IstftArgs& a, const SynthArgs& s, const int b, const int t0, Clip clip) {
     const int ng = min(istft640::FPG, s.nt - t0);
     auto mel_db = [&](int m, int f) {
@@ -445,13 +507,14 @@ __device__ __forceinline__ void synth_group(const IstftArgs& a, const SynthArgs&
         return a.mel_db[(clip(sl) * a.n_mels + m) * (long long)a.spf + (t - sl * a.spf)];
     };
     auto stft = [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * 321 + k]; };
-    auto frame = [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * (640 * P); };
-    if constexpr (P == 1) istft640::synth_frames(a, ng, mel_db, stft, frame);
+    auto frame = [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((s.T0 + t0 + f) % s.R)) * (BASE * P); };
+    if constexpr (BASE == 800) istft800::synth_frames<P>(a, ng, mel_db, stft, frame);
+    else if constexpr (P == 1) istft640::synth_frames(a, ng, mel_db, stft, frame);
     else istft_poly::synth_frames<P>(a, ng, mel_db, stft, frame);
 }
 
 // Lock-step: grid [groups, B].  EACH: item (stream, group); the stream inverts its k_new slices from frame spf k_old on.
-template <int P, bool EACH>
+template <int BASE, int P, bool EACH>
 __global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s, const StreamRow* __restrict__ rows,
                                                      const StreamItem* __restrict__ items) {
     if constexpr (EACH) {
@@ -459,11 +522,11 @@ __global__ __launch_bounds__(64) void k_stream_synth(IstftArgs a, SynthArgs s, c
         const StreamRow& r = rows[it.b];
         s.T0 = r.k_old * a.spf;
         s.nt = r.k_new * a.spf;
-        synth_group<P>(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
+        synth_group<BASE, P>(a, s, it.b, it.chunk * istft640::FPG, [&](int sl) { return (long long)r.clip0 + sl; });
     } else {
         const int b = blockIdx.y;
         const int t0 = blockIdx.x * istft640::FPG;
-        synth_group<P>(a, s, b, t0, [&](int sl) { return (long long)b * a.n_slices + sl; });
+        synth_group<BASE, P>(a, s, b, t0, [&](int sl) { return (long long)b * a.n_slices + sl; });
     }
 }
 
@@ -476,10 +539,10 @@ struct OlaArgs {
 };
 
 // Output sample j of this call of each stream.  Lock-step: grid [blocks of 256 samples, B].  EACH: item (stream, block).
-template <int P, bool EACH>
+template <int BASE, int P, bool EACH>
 __global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a, const StreamRow* __restrict__ rows,
                                                     const StreamItem* __restrict__ items) {
-    constexpr int N = 640 * P, hop = 160 * P;
+    constexpr int N = BASE * P, hop = BASE / 4 * P;
     int b, j;
     if constexpr (EACH) {
         const StreamItem it = items[blockIdx.x];
@@ -499,9 +562,9 @@ __global__ __launch_bounds__(256) void k_stream_ola(OlaArgs a, const StreamRow* 
 }
 
 // The streams ids[0 .. gridDim.x) go back to the state after create: both tail copies zero, running maximum -inf.
-template <int P>
+template <int BASE, int P>
 __global__ __launch_bounds__(256) void k_stream_reset(float* tail, float* run_max, const int* __restrict__ ids, int B) {
-    constexpr int N = 640 * P;
+    constexpr int N = BASE * P;
     const int b = ids[blockIdx.x];
     for (int j = threadIdx.x; j < 2 * N; j += 256) {
         const int copy = j / N;
@@ -510,12 +573,26 @@ __global__ __launch_bounds__(256) void k_stream_reset(float* tail, float* run_ma
     if (threadIdx.x == 0) run_max[b] = -INFINITY;
 }
 
-// ---- host: f(std::integral_constant<int, P>) for the session's P = n_fft / 640, the kernels' template argument ----
+// the frame arithmetic a geometry runs on: n_fft = base * P.  0: none is built (avse_stream_supported's rule:
+// 640 P at 16 / 32 / 48 kHz for 25-fps video, 800 P at 24 / 48 kHz for 30-fps video; a frame length belongs to its rate)
+int stream_base(int sr, int n_fft) {
+    if (n_fft == 640 || (n_fft == 1280 && sr == 32000) || (n_fft == 1920 && sr == 48000)) return 640;
+    if ((n_fft == 800 && sr == 24000) || (n_fft == 1600 && sr == 48000)) return 800;
+    return 0;
+}
+
+// ---- host: f(integral_constant<int, BASE>, integral_constant<int, P>) for the session's n_fft = BASE * P, the
+// kernels' template arguments ----
 template <class F>
-void with_phases(int P, F f) {
-    if (P == 1) f(std::integral_constant<int, 1>{});
-    else if (P == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
+void with_phases(int base, int P, F f) {
+    using B640 = std::integral_constant<int, 640>;
+    using B800 = std::integral_constant<int, 800>;
+    if (base == 800) {
+        if (P == 1) f(B800{}, std::integral_constant<int, 1>{});
+        else f(B800{}, std::integral_constant<int, 2>{});
+    } else if (P == 1) f(B640{}, std::integral_constant<int, 1>{});
+    else if (P == 2) f(B640{}, std::integral_constant<int, 2>{});
+    else f(B640{}, std::integral_constant<int, 3>{});
 }
 
 using Counts = StreamCounts;   // the host totals (stream_geom.h stream_totals)
@@ -532,7 +609,8 @@ struct avse_stream {
     const avse_weights* w = nullptr;
     int64_t B = 0, max_slices = 0;
     int sr = 0, n_fft = 0, hop = 0, spf = 0, n_mels = 0, vdt = 0, F = 0;
-    int P = 1;                // n_fft / 640: the phases of a frame (frame_poly.h)
+    int base = 640;           // the frame arithmetic: 640 (frame640.h / frame_poly.h) or 800 (frame800.h)
+    int P = 1;                // n_fft / base: the phases of a frame
     float amin = 0, top_db = 0, db_floor = 0;
     int R = 0, RS = 0, RV = 0;
     size_t vbytes = 0;
@@ -701,8 +779,8 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             SpecStreamArgs a = spec_args(s, samples, 0);  // row stride 0: + the row's sample_off
             a.tail_in = s->tail;                          // copies 0 / 1: the kernel picks by the row's parity
             a.tail_out = s->tail + (size_t)B * s->n_fft;
-            with_phases(s->P, [&](auto P) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<P, true>), dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st,
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<BASE, P, true>), dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st,
                                    a, d_rows, d_spec);
             });
             AVSE_HIP_CHECK(hipGetLastError());
@@ -718,15 +796,15 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             if (pred_db)
                 AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)p.clips * NMEL * s->spf,
                                               hipMemcpyDeviceToDevice, st));
-            with_phases(s->P, [&](auto P) {   // T0, nt: the rows'
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<P, true>), dim3((unsigned)p.items.synth), dim3(64), 0, st,
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {   // T0, nt: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<BASE, P, true>), dim3((unsigned)p.items.synth), dim3(64), 0, st,
                                    istft_args(s), synth_args(s, 0, 0), d_rows, d_synth);
             });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.items.ola > 0) {
-            with_phases(s->P, [&](auto P) {   // e_old, T, n_out: the rows'
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<P, true>), dim3((unsigned)p.items.ola), dim3(256), 0, st,
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {   // e_old, T, n_out: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<BASE, P, true>), dim3((unsigned)p.items.ola), dim3(256), 0, st,
                                    ola_args(s, out, out_stride, 0, 0, 0), d_rows, d_ola);
             });
             AVSE_HIP_CHECK(hipGetLastError());
@@ -794,8 +872,8 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
             a.n_old = cur.n; a.n_new = n2;
             a.Lf = flush ? slice * v2 : -1;
             a.t0 = c0.frames; a.nt = (int)nt; a.nblk = (int)((nt + SCHUNK - 1) / SCHUNK);
-            with_phases(s->P, [&](auto P) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<P, false>), dim3(a.nblk + tail_blk, B), dim3(64 * SWAVES), 0, st,
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<BASE, P, false>), dim3(a.nblk + tail_blk, B), dim3(64 * SWAVES), 0, st,
                                    a, no_rows, no_items);
             });
             AVSE_HIP_CHECK(hipGetLastError());
@@ -819,15 +897,15 @@ int stream_step(avse_stream* s, bool flush, const float* samples, int64_t n_new,
             IstftArgs ia = istft_args(s);
             ia.n_slices = (int)k_new;
             ia.T = (int)(k_new * s->spf);
-            with_phases(s->P, [&](auto P) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<P, false>), dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B),
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_synth<BASE, P, false>), dim3((ia.T + istft640::FPG - 1) / istft640::FPG, B),
                                    dim3(64), 0, st, ia, synth_args(s, c0.slices * s->spf, ia.T), no_rows, no_items);
             });
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (n_out > 0) {
-            with_phases(s->P, [&](auto P) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<P, false>), dim3((unsigned)((n_out + 255) / 256), B), dim3(256), 0,
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<BASE, P, false>), dim3((unsigned)((n_out + 255) / 256), B), dim3(256), 0,
                                    st, ola_args(s, out, out_stride, c0.emitted, c1.slices * s->spf, (int)n_out), no_rows, no_items);
             });
             AVSE_HIP_CHECK(hipGetLastError());
@@ -849,23 +927,30 @@ extern "C" {
 int avse_stream_supported(int sr, int n_fft, int hop, int frames_per_slice, int n_mels, float fmin, float fmax) {
     if (sr <= 0 || n_fft < 2 || hop <= 0 || frames_per_slice < 1 || n_mels < 1) return fail(AVSE_ERR_INVALID, "bad stream geometry");
     // a geometry streams when slices do not drift against the samples: n_fft even and four hops long (the slice is
-    // then frames_per_slice * hop samples by construction); of those, the 640-point kernels are built, and their
-    // P-phase forms for 2 x 640 at 32 kHz and 3 x 640 at 48 kHz
+    // then frames_per_slice * hop samples by construction); of those, the 640-point kernels are built, their P-phase
+    // forms for 2 x 640 at 32 kHz and 3 x 640 at 48 kHz, and the 800-point kernels of 30-fps video at 24 kHz and, in
+    // two phases, at 48 kHz
     if (n_fft % 2 || n_fft != 4 * hop)
         return fail(AVSE_ERR_UNSUPPORTED, "streaming needs an even n_fft == 4 * hop (25 fps at 16, 32 or 48 kHz: 640 / 160, "
-                                          "1280 / 320, 1920 / 480)");
-    const bool built = n_fft == 640 || (n_fft == 1280 && sr == 32000) || (n_fft == 1920 && sr == 48000);
-    if (!built || n_mels != NMEL)
+                                          "1280 / 320, 1920 / 480; 30 fps at 24 or 48 kHz: 800 / 200, 1600 / 400)");
+    const int base = stream_base(sr, n_fft);
+    if (!base || n_mels != NMEL)
         return fail(AVSE_ERR_UNSUPPORTED, "streaming is built for 25 fps at 16, 32 and 48 kHz (n_fft 640 / hop 160, 1280 / 320 at "
-                                          "sr 32000, 1920 / 480 at sr 48000) and 80 bands");
+                                          "sr 32000, 1920 / 480 at sr 48000), for 30 fps at 24 and 48 kHz (800 / 200 at sr 24000, "
+                                          "1600 / 400 at sr 48000), and 80 bands");
     // the bank the kernels will read (build_spec_tables makes the same one): every band within the 24-bin table, and
-    // nothing above bin 320, the last of the 640-point arithmetic (always so at n_fft 640)
+    // nothing above the last bin of the frame arithmetic: 320 of the 640-point one (always so at n_fft 640), 266 of the
+    // 800-point one (the 30-Hz bins under 8 kHz)
+    const int top = base == 640 ? 320 : spec800::KTOP;
     const MelBands mb = mel_bands(sr, n_fft, n_mels, fmin, fmax);
     bool low = true;
-    for (int m = 0; m < n_mels; ++m) low = low && mb.start[m] + mb.width[m] - 1 <= 320;
+    for (int m = 0; m < n_mels; ++m) low = low && mb.start[m] + mb.width[m] - 1 <= top;
     if (mb.max_width != MW || !low)
-        return fail(AVSE_ERR_UNSUPPORTED, "streaming needs a Slaney bank whose bands fit 24 bins and lie in bins 0 .. 320 "
-                                          "(fmin 0, fmax 8000 at sr 16000, 32000 or 48000)");
+        return fail(AVSE_ERR_UNSUPPORTED, base == 640
+                        ? "streaming needs a Slaney bank whose bands fit 24 bins and lie in bins 0 .. 320 "
+                          "(fmin 0, fmax 8000 at sr 16000, 32000 or 48000)"
+                        : "streaming needs a Slaney bank whose bands fit 24 bins and lie in bins 0 .. 266 "
+                          "(fmin 0, fmax 8000 at sr 24000 or 48000 with 30-fps video)");
     return 0;
 }
 
@@ -891,7 +976,8 @@ int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, in
     s->sr = sr; s->n_fft = n_fft; s->hop = hop; s->spf = frames_per_slice; s->n_mels = n_mels; s->vdt = video_dtype; s->F = wf;
     s->amin = amin; s->top_db = top_db;
     s->db_floor = (float)(20.0 * std::log10((double)amin));
-    s->P = n_fft / 640;
+    s->base = stream_base(sr, n_fft);
+    s->P = n_fft / s->base;
     if (int rc = build_spec_tables(s->spec, sr, n_fft, n_mels, fmin, fmax)) return rc;
     if (s->spec.mel.max_width != MW) return fail(AVSE_ERR_UNSUPPORTED, "the mel tables differ from the bank avse_stream_supported saw");
     if (int rc = build_istft_tables(s->ist, sr, n_fft, n_mels, fmin, fmax)) return rc;
@@ -1016,8 +1102,8 @@ int avse_stream_reset_each(avse_stream* s, const uint8_t* which, void* stream) {
         if (which[b]) ids[n++] = b;
     if (int rc = stream_stage_upload(s, sizeof(int) * (size_t)n, st)) return rc;
     const int* ids_d = reinterpret_cast<const int*>(s->tables.p.get());
-    with_phases(s->P, [&](auto P) {
-        hipLaunchKernelGGL(k_stream_reset<P>, dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
+    with_phases(s->base, s->P, [&](auto BASE, auto P) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_reset<BASE, P>), dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
     });
     AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
     for (int b = 0; b < B; ++b)

@@ -769,7 +769,8 @@ def stream_counts(n_samples, n_video_slices, flushed=False, session=None):
 def stream_supported(sample_rate=16000, n_fft=640, hop_length=160, frames_per_slice=20, n_mels=80, fmin=0.0, fmax=8000.0,
                      return_message=False):
     """avse_stream_supported (host only, no GPU): 0 when stream_create serves this geometry and mel bank (25 fps at 16,
-    32 and 48 kHz: n_fft 640 / 1280 / 1920 = 4 hops, 80 bands under 8 kHz), else the status it would raise with (3:
+    32 and 48 kHz: n_fft 640 / 1280 / 1920 = 4 hops; 30 fps at 24 and 48 kHz: n_fft 800 / 1600 = 4 hops; 80 bands under
+    8 kHz), else the status it would raise with (3:
     unsupported, 1: invalid).  return_message: -> (status, the library's reason; "" for status 0)."""
     lib = _lib.load()
     rc = int(lib.avse_stream_supported(int(sample_rate), int(n_fft), int(hop_length), int(frames_per_slice), int(n_mels),
@@ -813,9 +814,10 @@ class StreamSession:
 def stream_create(weights, n_streams, sample_rate=16000, n_fft=640, hop_length=160, frames_per_slice=20, n_mels=80,
                   fmin=0.0, fmax=8000.0, amin=1e-5, top_db=80.0, video_dtype=torch.float32, max_slices=4):
     """avse_stream_create on the weights' context -> StreamSession.  video_dtype: torch.float32 or torch.uint8, the
-    element type every push's video will have.  Geometries the streaming kernels do not serve (29.97 / 30 fps, 44.1 kHz:
-    stream_supported says which do: 640 / 160 at 16 kHz, 1280 / 320 at 32 kHz, 1920 / 480 at 48 kHz) raise _lib.AvseError
-    (status 3)."""
+    element type every push's video will have.  Geometries the streaming kernels do not serve (29.97 fps, 30 fps at
+    16 kHz, 44.1 kHz: stream_supported says which do: 640 / 160 at 16 kHz, 1280 / 320 at 32 kHz, 1920 / 480 at 48 kHz for
+    25-fps video, 800 / 200 at 24 kHz and 1600 / 400 at 48 kHz for 30-fps video, with frames_per_slice 24 and the
+    [80, 24] x 6-frame weights) raise _lib.AvseError (status 3)."""
     if not isinstance(weights, DeviceWeights):
         raise TypeError("weights must be DeviceWeights")
     if int(n_streams) < 1 or int(max_slices) < 1:

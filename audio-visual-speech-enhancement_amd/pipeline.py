@@ -172,8 +172,9 @@ class StreamEnhancer:
     16 kHz).
 
     Only geometries whose slices do not drift against the samples stream, and of those 25 fps at sample_rate 16000,
-    32000 or 48000 (n_fft = rate / 25; the same weights: ops.stream_supported is the rule); 29.97 / 30 fps and 44.1 kHz
-    raise _lib.AvseError at construction."""
+    32000 or 48000 (n_fft = rate / 25; the same weights) and 30 fps at sample_rate 24000 or 48000 (n_fft = rate / 30,
+    weights of the [80, 24] x 6-frame network); ops.stream_supported is the rule.  29.97 fps, 30 fps at 16 kHz (n_fft
+    533) and 44.1 kHz raise _lib.AvseError at construction."""
 
     def __init__(self, weights, n_streams, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, max_slices=4,
                  video_dtype=torch.float32):

@@ -352,13 +352,18 @@ int avse_forward_profile_video(avse_ctx* ctx, const avse_weights* w, const float
  * Geometry and dB parameters are avse_spectrogram's / avse_istft's, video_dtype avse_forward_video's; a slice is
  * frames_per_slice * hop samples, and `weights` must have been loaded for frames_per_slice spectrogram frames
  * (AVSE_ERR_INVALID otherwise).  A geometry streams when its slices do not drift against the samples: n_fft even and
- * n_fft == 4 * hop, else AVSE_ERR_UNSUPPORTED (29.97 / 30 fps: n_fft 533, and 24 x 133 = 3192 samples per 3200-sample
- * slice).  Built: the reference's 25-fps geometries (n_fft = sr / 25, data_processor.py:44) at 16, 32 and 48 kHz, i.e.
- * n_fft 640 / hop 160, n_fft 1280 / hop 320 at sr 32000 and n_fft 1920 / hop 480 at sr 48000, with 80 bands and a Slaney
- * bank whose bands fit 24 bins and lie in bins 0 .. 320 (fmin 0, fmax 8000: at every one of these rates the bins are
- * 25 Hz apart and the bank is the 16 kHz bank, so the longer frames are computed as 2 or 3 interleaved 640-point
- * frames); any frames_per_slice the weights have (20 at 25 fps), up to 1024 streams and max_slices 16.  Other geometries
- * that pass the condition are AVSE_ERR_UNSUPPORTED too (44.1 kHz: n_fft 1764; fmax 24000 at 48 kHz);
+ * n_fft == 4 * hop, else AVSE_ERR_UNSUPPORTED (29.97 fps at every rate, and 30 fps at 16 kHz: n_fft 533, and
+ * 24 x 133 = 3192 samples per 3200-sample slice; int(48000 / 29.97) = 1601 is odd).  Built: the reference's 25-fps
+ * geometries (n_fft = sr / 25, data_processor.py:44) at 16, 32 and 48 kHz, i.e. n_fft 640 / hop 160, n_fft 1280 / hop 320
+ * at sr 32000 and n_fft 1920 / hop 480 at sr 48000, with 80 bands and a Slaney bank whose bands fit 24 bins and lie in
+ * bins 0 .. 320 (fmin 0, fmax 8000: at every one of these rates the bins are 25 Hz apart and the bank is the 16 kHz
+ * bank, so the longer frames are computed as 2 or 3 interleaved 640-point frames); and its 30-fps geometries
+ * (n_fft = sr / 30) at 24 and 48 kHz, i.e. n_fft 800 / hop 200 at sr 24000 and n_fft 1600 / hop 400 at sr 48000, with
+ * 80 bands and a bank that lies in bins 0 .. 266 (fmin 0, fmax 8000: the bins are 30 Hz apart at both rates and the
+ * banks are equal, so the 1600-sample frame is two interleaved 800-point frames); a frame length belongs to its rate
+ * (800 / 200 at 16 kHz is refused).  Any frames_per_slice the weights have (20 at 25 fps, 24 at 30 fps, where the
+ * weights are those of the [80, 24] x 6-frame network), up to 1024 streams and max_slices 16.  Other geometries that
+ * pass the condition are AVSE_ERR_UNSUPPORTED too (44.1 kHz: n_fft 1764; fmax 24000 at 48 kHz);
  * avse_stream_supported is the rule.
  * max_slices: the most slices one call may complete, and the most either input may run ahead of the other.  All device
  * state and scratch is sized from n_streams and max_slices here (the forward scratch through

@@ -36,7 +36,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--dtype", default="float32_split")
-    ap.add_argument("--sample-rate", type=int, default=16000, help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25)")
+    ap.add_argument("--sample-rate", type=int, default=16000,
+                    help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25); with --fps 30: 24000 or 48000 (n_fft = rate / 30)")
+    ap.add_argument("--fps", type=float, default=25.0, help="video frame rate: 25, or 30 (the [80, 24] x 6-frame network)")
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--label", default="")
@@ -56,11 +58,14 @@ def main():
 
     B = args.streams
     rng = np.random.default_rng(0)
-    dw = ops.DeviceWeights(KerasModel.init(seed=0, randomize=True), args.dtype)
+    if args.fps not in (25.0, 30.0) or args.sample_rate not in ((16000, 32000, 48000) if args.fps == 25.0 else (24000, 48000)):
+        sys.exit("stream_each_latency: --fps 25 takes --sample-rate 16000, 32000 or 48000; --fps 30 takes 24000 or 48000")
+    T, F = (20, 5) if args.fps == 25.0 else (24, 6)
+    dw = ops.DeviceWeights(KerasModel.init(seed=0, randomize=True, audio_shape=(80, T), video_shape=(128, 128, F)), args.dtype)
     sr = args.sample_rate
     sl = sr // 5                      # samples per 200-ms slice
     sig = ops.to_device(rng.normal(0, 3000, (B, sl * 8)).round().astype(np.float32))
-    video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, 5)).astype(np.float32))
+    video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, F)).astype(np.float32))
     mean = ops.to_device(np.full((128, 128), 127.5, np.float32))
     std = ops.to_device(np.full((128, 128), 73.9, np.float32))
     chunks = [sig[:, sl * k:sl * k + sl].contiguous() for k in range(8)]
@@ -70,7 +75,7 @@ def main():
     one = [[c[b] if b == active else None for b in range(B)] for c in chunks]
     vone = [video[b] if b == active else None for b in range(B)]
 
-    make = lambda n: StreamEnhancer(dw, n, sample_rate=sr)
+    make = lambda n: StreamEnhancer(dw, n, video_frame_rate=args.fps, sample_rate=sr)
     lock, each, sparse, single = make(B), make(B), make(B), make(1)
     many = [make(1) for _ in range(B)]
 
@@ -103,13 +108,13 @@ def main():
                 t["host_call_ms"].append(1e3 * (t1 - t0))
                 t["host_sync_ms"].append(1e3 * (t2 - t0))
     n_calls = args.warmup + args.rounds
-    want = sl * (n_calls - 1) - sl // 10                                 # every push after the first completed its slice
+    want = sl * (n_calls - 1) - 2 * (sl // T)                                # every push after the first completed its slice
     assert lock.counts["emitted"] == want and single.counts["emitted"] == want and many[-1].counts["emitted"] == want
     assert each.counts["emitted"] == want, each.counts                 # (uniform counts: the streams stayed in step)
     assert sparse.counts["emitted"][active] == want and sum(sparse.counts["samples"]) == sl * n_calls
     lines = []
     for name, _ in cases:
-        lines.append(json.dumps(dict(what=name, dtype=args.dtype, sample_rate=sr, streams=B, rounds=args.rounds, warmup=args.warmup,
+        lines.append(json.dumps(dict(what=name, dtype=args.dtype, sample_rate=sr, fps=args.fps, streams=B, rounds=args.rounds, warmup=args.warmup,
                                      label=args.label, **{k: stats(v) for k, v in times[name].items()})))
         print(lines[-1], flush=True)
     if args.out:

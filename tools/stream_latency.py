@@ -16,6 +16,7 @@ the median and the 99th percentile of each; --out appends them to a file.
 
   python tools/stream_latency.py --out profiles/stream_latency.jsonl
   python tools/stream_latency.py --sample-rate 48000 --streams 1,64                        # the 3-phase kernels
+  python tools/stream_latency.py --fps 30 --sample-rate 24000 --streams 1,64               # 30-fps video: the 800-point kernels
   python tools/stream_latency.py --yardstick-only --root <checkout of the parent commit>   # the same script on the parent
 """
 import argparse
@@ -54,7 +55,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", default="1,16,64")
     ap.add_argument("--dtypes", default="float32_split,bfloat16")
-    ap.add_argument("--sample-rate", type=int, default=16000, help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25)")
+    ap.add_argument("--sample-rate", type=int, default=16000,
+                    help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25); with --fps 30: 24000 or 48000 (n_fft = rate / 30)")
+    ap.add_argument("--fps", type=float, default=25.0, help="video frame rate: 25, or 30 (the [80, 24] x 6-frame network)")
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -76,17 +79,23 @@ def main():
         sys.exit("stream_latency: no ROCm GPU visible to torch; nothing is measured without one")
 
     rng = np.random.default_rng(0)
-    model = KerasModel.init(seed=0, randomize=True)
+    if args.fps not in (25.0, 30.0) or args.sample_rate not in ((16000, 32000, 48000) if args.fps == 25.0 else (24000, 48000)):
+        sys.exit("stream_latency: --fps 25 takes --sample-rate 16000, 32000 or 48000; --fps 30 takes 24000 or 48000")
+    T, F = (20, 5) if args.fps == 25.0 else (24, 6)
+    model = KerasModel.init(seed=0, randomize=True) if args.fps == 25.0 else \
+        KerasModel.init(seed=0, randomize=True, audio_shape=(80, T), video_shape=(128, 128, F))
     n_calls = args.warmup + args.pushes
     sr = args.sample_rate
     sl = sr // 5                      # samples per 200-ms slice
     rate = {} if sr == 16000 else {"sample_rate": sr}      # (a parent tree's Enhancer defaults to 16 kHz as well)
+    if args.fps != 25.0:
+        rate["video_frame_rate"] = args.fps
     lines = []
     for dtype in args.dtypes.split(","):
         dw = ops.DeviceWeights(model, dtype)
         for B in (int(b) for b in args.streams.split(",")):
             sig = ops.to_device(rng.normal(0, 3000, (B, sl * 8)).round().astype(np.float32))
-            video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, 5)).astype(np.float32))
+            video = ops.to_device(rng.integers(0, 256, (B, 1, 128, 128, F)).astype(np.float32))
             mean = ops.to_device(np.full((128, 128), 127.5, np.float32))
             std = ops.to_device(np.full((128, 128), 73.9, np.float32))
             chunks = [sig[:, sl * k:sl * k + sl].contiguous() for k in range(8)]
@@ -98,11 +107,11 @@ def main():
             off = Enhancer(dw, **rate)
             cases.append(("enhancer_1_slice", lambda i, off=off: off(chunks[i % 8], video, mean, std)))
             for name, fn in cases:
-                r = dict(what=name, dtype=dtype, sample_rate=sr, streams=B, pushes=args.pushes, warmup=args.warmup, label=args.label,
+                r = dict(what=name, dtype=dtype, sample_rate=sr, fps=args.fps, streams=B, pushes=args.pushes, warmup=args.warmup, label=args.label,
                          **timed(fn, args.warmup, args.pushes, torch))
                 if name == "stream_push":
                     r["emitted_samples"] = enh.counts["emitted"]
-                    assert r["emitted_samples"] == sl * (n_calls - 1) - sl // 10, r   # every push completed its slice
+                    assert r["emitted_samples"] == sl * (n_calls - 1) - 2 * (sl // T), r   # every push completed its slice
                 lines.append(json.dumps(r))
                 print(lines[-1], flush=True)
     if args.out:
