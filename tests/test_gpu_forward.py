@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import synth_video
+from forward_local_ref import buf_shapes
 from oracle import keras_ref as K
 from oracle import librosa_ref as R
 
@@ -34,6 +35,7 @@ BUF_SHAPES = {"video_in": (128, 128, 8), "audio_in": (80, 20, 8), "a_conv1": (40
               "enc_dense": (1312,), "dec_dense1": (1312,), "dec_dense2": (5, 5, 128), "d_deconv1": (10, 5, 128),
               "d_deconv2": (20, 5, 128), "d_deconv3": (40, 10, 128), "d_deconv4": (40, 10, 64),
               "d_deconv5": (80, 20, 64)}
+assert BUF_SHAPES == buf_shapes(20, 5)      # the 25-fps instance of the arena's per-clip shapes
 
 
 # AVSE_F32_SPLIT: buffers in the split pair layout (every layer output that feeds another conv / dense layer; the fp32
@@ -59,7 +61,9 @@ def rel_rms(a, b):
 
 def scratch(dw, N, clips=None, names=None):
     """Read libavse's intermediate activations (avse_debug_scratch) as float32 numpy arrays — only the listed
-    clips (every buffer is clip-major) and buffers, so a 512-clip batch does not copy gigabytes."""
+    clips (every buffer is clip-major) and buffers, so a 512-clip batch does not copy gigabytes.  The arena is laid out
+    for the shape of the last forward, which must be dw's: the per-clip shapes follow its (T, F)."""
+    shapes = buf_shapes(dw.T, dw.F)
     from avse_amd import _lib
     base = ctypes.c_void_p()
     offs = (ctypes.c_int64 * 20)()
@@ -74,7 +78,7 @@ def scratch(dw, N, clips=None, names=None):
     for i, name in enumerate(BUF_NAMES):
         if names is not None and name not in names:
             continue
-        per = int(np.prod(BUF_SHAPES[name]))
+        per = int(np.prod(shapes[name]))
         t = torch.empty(len(clips) * per, dtype=dt, device="cuda")
         for j, c in enumerate(clips):
             rc = hip.hipMemcpy(ctypes.c_void_p(t.data_ptr() + j * per * es),
@@ -82,13 +86,13 @@ def scratch(dw, N, clips=None, names=None):
             assert rc == 0
         if dw.dtype == _lib.AVSE_F32_SPLIT and name in SPLIT_PAIR_BUFS:
             # split-pair layout (include/avse.h AVSE_F32_SPLIT): per pixel and 16 channels [h(16) | l(16)] f16
-            shp = BUF_SHAPES[name]
+            shp = shapes[name]
             hl = t.view(torch.float16).float().cpu().numpy().reshape((len(clips),) + shp[:-1] + (shp[-1] // 16, 2, 16))
             # the pairs hold x 2^e of the producing layer (avse_weights_act_exponents; concat: a_conv5 = v_conv6)
             e = dw.act_exponents()["a_conv5" if name == "concat" else name]
             out[name] = np.ldexp((hl[..., 0, :].astype(np.float64) + hl[..., 1, :]).reshape((len(clips),) + shp), -e)
         else:
-            out[name] = t.float().cpu().numpy().reshape((len(clips),) + BUF_SHAPES[name])
+            out[name] = t.float().cpu().numpy().reshape((len(clips),) + shapes[name])
     return out
 
 

@@ -319,7 +319,7 @@ def test_split_valu_aconv1_matches_kconv_and_oracle(gpu, N, T):
     model = db_scale(KerasModel.init(seed=71, randomize=True, audio_shape=(80, T)))
     rng = np.random.default_rng(171)
     mel = rng.normal(-40, 15, (N, 80, T)).astype(np.float32)
-    names = ["a_conv1", "a_conv2"] if T == 20 else []   # (the scratch reader knows the 25 fps shapes)
+    names = ["a_conv1", "a_conv2"]
     clips = spread_clips(N, k=6)
     dw = ops.DeviceWeights(model, SPLIT)
     got = ops.forward(dw, ops.to_device(mel), None, checked=True).cpu().numpy()

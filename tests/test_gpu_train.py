@@ -84,11 +84,17 @@ def check_gradients(g, ref_g, tol=1e-2):
 # N = 16 with max_batch = 16 is the reference's fit batch (network.py:203) and the shape bench.py's train leg times
 # (wg_splits, rows_per_split, k_wgrad_nat splits and the column-reduction blocks all change with N); N = 1: the dense
 # layers' BatchNormalization over a single sample (variance 0)
-@pytest.mark.parametrize("N,rate,max_batch", [(4, 0.25, 8), (3, 0.0, 8), (16, 0.25, 16), (1, 0.0, 16)])
-def test_gradients_match_oracle(gpu, N, rate, max_batch):
+# "signed": the model with every BatchNormalization gamma negated on channels 1::3 (a trained checkpoint may hold
+# negative gammas; KerasModel.init draws them positive), N = 3
+@pytest.mark.parametrize("N,rate,max_batch", [(4, 0.25, 8), (3, 0.0, 8), (16, 0.25, 16), (1, 0.0, 16),
+                                              pytest.param(3, 0.25, 8, id="signed-3-0.25-8")])
+def test_gradients_match_oracle(gpu, request, N, rate, max_batch):
     from avse_amd import ops
     from avse_amd.model import KerasModel
     model = KerasModel.init(seed=21, randomize=True)
+    if request.node.callspec.id.startswith("signed"):
+        from forward_local_ref import negated_gammas
+        negated_gammas(model)
     rng = np.random.default_rng(5 + N)
     mel, video, target = batch(rng, N)
     tr = ops.Trainer(model, max_batch=max_batch, device=gpu)

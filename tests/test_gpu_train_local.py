@@ -25,7 +25,10 @@ another float32 summation order over up to 262k rows and a forward whose x diffe
 reads of separate grads-only steps, so the first test asserts that such steps are bit-identical.
 
 Cases (train_local_ref.CASES): N = 3 (ragged row counts everywhere, short train_split grids), N = 2 of the
-(80, 24) / (128, 128, 6) plan without dropout, N = 16 with max_batch 16 (the reference's fit batch).
+(80, 24) / (128, 128, 6) plan without dropout, N = 16 with max_batch 16 (the reference's fit batch), and n3s: N = 3
+with every gamma negated on channels 1::3, as a trained checkpoint may hold (measured, largest over its 20 layers:
+ghat 3.8e-8, dgamma 3.2e-6, dbeta 1.9e-7, dz 1.2e-5 at dec_dense1 against a gate of 3.3e-4, dW 3.0e-6, dbias 3.3e-8,
+gin 2.3e-7, ambiguous share <= 2.9e-3; all pass).
 
 Measured on an MI355X (profiles/train_local_checks.txt has every layer and its gate), largest relative RMS over the
 layers of a case, device | float32 stand-in; all 3 x 20 layers pass, two grads-only steps are bit-equal, no defect:

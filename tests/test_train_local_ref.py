@@ -16,7 +16,7 @@ import train_local_ref as R
 from oracle import keras_train_ref as KT
 
 
-@pytest.fixture(scope="module", params=["n3", "n2"])
+@pytest.fixture(scope="module", params=["n3", "n2", "n3s"])
 def case(request):
     c = R.CASES[request.param]
     model, mel, video, target = R.case_inputs(request.param)
@@ -50,6 +50,27 @@ def test_chaining_reproduces_autograd(case):
         e = R.bias_error(i, dbias, dz, want[n + "/bias"])      # pre-BN biases: ~0 against ~0, on the scale of sum |dz|
         assert e <= 1e-10, (n + "/bias", e)
     print(f"{name}: worst relative RMS against float64 autograd {worst:.1e}")
+
+
+def test_signed_case_keeps_the_ambiguous_share_under_the_cap(case):
+    """n3s (gammas negated on channels 1::3): the float64 reference alone — its own g_out, no float32 anywhere — keeps
+    every layer's ambiguous share under the 1 % cap, so on the device the cap still measures the kernel; and the case
+    does hold negative gammas on every BatchNormalization."""
+    name, _, _, ref, _, _ = case
+    gin, worst = {}, 0.0
+    for i in reversed(range(len(R.NAMES))):
+        L = ref.layers[i]
+        if L.bn:
+            assert bool((L.gamma < 0).any()) == (name == "n3s") and not (L.gamma == 0).any(), R.NAMES[i]
+            ghat, amb = ref.act_bwd(i, ref.g_out_of(i, gin.__getitem__))
+            share = float(amb.mean())
+            worst = max(worst, share)
+            assert share <= R.AMBIGUOUS_SHARE, (name, R.NAMES[i], share)
+            dz = ref.bn_bwd(i, ghat)[2]
+        else:
+            dz = ref.dLdy
+        gin[i] = ref.input_grad(i, dz)
+    print(f"{name}: largest ambiguous share of the float64 reference {worst:.2e}")
 
 
 def test_standin_calibration(case):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from forward_local_ref import negated_gammas
 from oracle import keras_ref as K
 from oracle import keras_train_ref as KT
 
@@ -43,12 +44,16 @@ NO_DGRAD = (NAMES.index("a_conv1"), NAMES.index("v_conv1"))     # the first laye
 ENC_DENSE = NAMES.index("enc_dense")
 
 
-# The cases of tests/test_gpu_train_local.py (the first two also run on the CPU, tests/test_train_local_ref.py):
+# The cases of tests/test_gpu_train_local.py (n3, n2 and n3s also run on the CPU, tests/test_train_local_ref.py):
 #   n3   every row count a ragged multiple for rows_per_split and colred_grid; 3 clips give train_split its short grids
 #   n2   the other plan ((80, 24) / (128, 128, 6)), with the row-run v_conv1 shapes, no dropout
 #   n16  the reference's fit batch: wg_splits, k_wgrad_nat's 2048-row cap and the column-reduction grids change here
+#   n3s  n3 with every BatchNormalization gamma negated on channels 1::3 (forward_local_ref.negated_gammas), as a
+#        trained checkpoint may hold: the forward's sign handling, dgamma and dz with gamma < 0.  No zero gammas: a
+#        constant channel ties every pool window, and the ambiguous share would measure the input, not the kernel
 CASES = {
     "n3": dict(N=3, rate=0.25, T=20, F=5, max_batch=8, model_seed=21, data_seed=8, drop_seed=1234),
+    "n3s": dict(N=3, rate=0.25, T=20, F=5, max_batch=8, model_seed=21, data_seed=8, drop_seed=1234, signed=True),
     "n2": dict(N=2, rate=0.0, T=24, F=6, max_batch=8, model_seed=21, data_seed=7, drop_seed=1234),
     "n16": dict(N=16, rate=0.25, T=20, F=5, max_batch=16, model_seed=21, data_seed=21, drop_seed=1234),
 }
@@ -59,6 +64,8 @@ def case_inputs(case):
     from avse_amd.model import KerasModel
     c = CASES[case]
     model = KerasModel.init(seed=c["model_seed"], randomize=True, audio_shape=(80, c["T"]), video_shape=(128, 128, c["F"]))
+    if c.get("signed"):
+        negated_gammas(model)
     rng = np.random.default_rng(c["data_seed"])
     mel = rng.normal(-40, 12, (c["N"], 80, c["T"])).astype(np.float32)
     video = rng.normal(0, 1, (c["N"], 128, 128, c["F"])).astype(np.float32)      # normalised crops
