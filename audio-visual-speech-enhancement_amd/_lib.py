@@ -128,6 +128,20 @@ SIGNATURES = {
     "avse_stream_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     # host only: supported(sr, n_fft, hop, spf, n_mels, fmin, fmax) -> 0 or the status stream_create would return
     "avse_stream_supported": (_int, [_int, _int, _int, _int, _int, _flt, _flt]),
+    # resampling: supported(sr_in, sr_out); counts(sr_in, sr_out, n_in, flushed, host n_out); ragged(ctx, sig, host
+    # sig_off, host n_samples, n_utt, sr_in, sr_out, out, host out_off, stream); resampler create(ctx, n_streams, sr_in,
+    # sr_out, out); push_each(r, samples, host sample_off, host n_new, host flush, out, out_stride, host n_out, stream);
+    # reset_each(r, host which, stream); state(r, host n_in, host n_out, host flushed)
+    "avse_resample_supported": (_int, [_int, _int]),
+    "avse_resample_counts": (_int, [_int, _int, _i64, _int, ctypes.POINTER(_i64)]),
+    "avse_resample_ragged": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _c_void_p, _c_void_p,
+                                    _c_void_p]),
+    "avse_resampler_create": (_int, [_c_void_p, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),
+    "avse_resampler_push_each": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                        _c_void_p]),
+    "avse_resampler_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
+    "avse_resampler_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_resampler_destroy": (None, [_c_void_p]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

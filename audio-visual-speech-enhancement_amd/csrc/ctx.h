@@ -96,6 +96,12 @@ struct EvalTables {
     int up = 1, down = 1, H = 0, win = 0;
 };
 
+// device copy of one resampling ratio's taps by phase (resample.hip avse_resample_ragged)
+struct ResampleTables {
+    int up = 0, down = 0;
+    Owned<double> ptaps;     // [up][2 H / up + 1]
+};
+
 // The tables of one geometry on the current device, kept when `t` already holds them (capi.hip): the context's own
 // (replaced when a call names another geometry) and a streaming session's, which lives as long as the session.
 int build_spec_tables(SpecTables& t, int sr, int n_fft, int n_mels, double fmin, double fmax);
@@ -128,6 +134,8 @@ struct avse_ctx {
     avse::IstftTables istft;
     avse::EvalTables eval[4];   // the last four (sample rate, resampling path) of avse_eval_pairs*, replaced in turn
     int eval_next = 0;
+    avse::ResampleTables resample[4];   // the last four ratios of avse_resample_ragged, replaced in turn
+    int resample_next = 0;
     avse::Owned<float> frames;      // ISTFT frame scratch
     avse::Owned<unsigned> umax;     // spectrogram: one word per utterance
     avse::Owned<float> mse_partial;

@@ -933,15 +933,9 @@ def _host_i64(values):
     return a, ctypes.c_void_p(a.ctypes.data)
 
 
-def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=None, vnorm_std=None,
-                     return_spectrograms=False):
-    """avse_stream_push_each: every stream moves by its own amount.  samples: a list of B 1-D float32 device tensors
-    (None or empty for a stream without new samples), video: a list of B [v, 128, 128, F] tensors in the session's dtype
-    (None for a stream without new video), flush: a list of B bools (streams to close as stream_flush does); any of the
-    three may be None as a whole.  The inputs are packed on the device (one torch.cat each).
-    -> a list of B 1-D tensors, stream b's newly final samples; with return_spectrograms also two lists of [k_b, 80, spf]
-    tensors, the slices the network saw and predicted for the k_b slices stream b completed in this call.  Asynchronous
-    on torch's current stream; a stream without input or flush launches no blocks."""
+def _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std):
+    """stream_push_each's arguments, checked and packed on the device (one torch.cat each)
+    -> (packed samples, offsets [B], n_new [B], packed video, v_new [B], flush [B])."""
     w = session.weights
     dev = torch.device("cuda", w.ctx.device_index)
     B = session.n_streams
@@ -974,10 +968,34 @@ def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=N
     for t in s_parts + v_parts + [vnorm_mean, vnorm_std]:
         if t is not None and t.device.index != dev.index:
             raise ValueError(f"the session lives on {dev} but an argument is on {t.device}")
-    ks, es = _stream_expect(session, n_new, v_new, flush)
     packed = torch.cat(s_parts) if s_parts else None
     vpacked = torch.cat(v_parts) if v_parts else None
     off = np.concatenate([[0], np.cumsum(n_new)[:-1]])
+    return packed, off, n_new, vpacked, v_new, flush
+
+
+def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=None, vnorm_std=None,
+                     return_spectrograms=False):
+    """avse_stream_push_each: every stream moves by its own amount.  samples: a list of B 1-D float32 device tensors
+    (None or empty for a stream without new samples), video: a list of B [v, 128, 128, F] tensors in the session's dtype
+    (None for a stream without new video), flush: a list of B bools (streams to close as stream_flush does); any of the
+    three may be None as a whole.  The inputs are packed on the device (one torch.cat each).
+    -> a list of B 1-D tensors, stream b's newly final samples; with return_spectrograms also two lists of [k_b, 80, spf]
+    tensors, the slices the network saw and predicted for the k_b slices stream b completed in this call.  Asynchronous
+    on torch's current stream; a stream without input or flush launches no blocks."""
+    packed, off, n_new, vpacked, v_new, flush = _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std)
+    out, mel, pred, ks, es = _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnorm_mean, vnorm_std,
+                                                 return_spectrograms)
+    return _stream_split(out, mel, pred, ks, es, return_spectrograms)
+
+
+def _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnorm_mean, vnorm_std, return_spectrograms):
+    """The call of stream_push_each on checked, packed arguments: stream b's n_new[b] samples start at element off[b] of
+    the float32 buffer `packed` (any layout: tight, or the rows of a [B, stride] buffer), its v_new[b] video slices lie
+    stream-major in `vpacked`.  -> (out [B, max n_out], mel, pred, slices per stream, samples per stream)."""
+    dev = torch.device("cuda", session.weights.ctx.device_index)
+    B = session.n_streams
+    ks, es = _stream_expect(session, n_new, v_new, flush)
     out = torch.empty((B, max(es)), dtype=torch.float32, device=dev)
     mel = pred = None
     if return_spectrograms:
@@ -999,7 +1017,7 @@ def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=N
         session.ns[b] += n_new[b]
         session.vs[b] += v_new[b]
         session.fl[b] = session.fl[b] or flush[b]
-    return _stream_split(out, mel, pred, ks, es, return_spectrograms)
+    return out, mel, pred, ks, es
 
 
 def stream_reset_each(session, streams):
@@ -1049,6 +1067,186 @@ def stream_reset(session):
         _lib.check(_lib.load().avse_stream_reset(session.handle, _lib.stream_handle(dev)), "avse_stream_reset")
     B = session.n_streams
     session.ns, session.vs, session.fl = [0] * B, [0] * B, [False] * B
+
+
+def resample_supported(sr_in, sr_out, return_message=False):
+    """avse_resample_supported (host only, no GPU): 0 when sr_in -> sr_out is served (max(up, down) <= 640 after
+    reduction), else the status resample / resampler_create would raise with (3: unsupported, 1: invalid).
+    return_message: -> (status, the library's reason; "" for status 0)."""
+    lib = _lib.load()
+    rc = int(lib.avse_resample_supported(int(sr_in), int(sr_out)))
+    if not return_message:
+        return rc
+    return rc, (lib.avse_last_error().decode(errors="replace") if rc else "")
+
+
+def resample_counts(sr_in, sr_out, n_in, flushed=False):
+    """avse_resample_counts (host only, no GPU): the outputs that are final after n_in inputs,
+    max(0, ceil((n_in up - H) / down)), or all ceil(n_in up / down) of a flushed stream."""
+    out = ctypes.c_int64()
+    _lib.check(_lib.load().avse_resample_counts(int(sr_in), int(sr_out), int(n_in), int(bool(flushed)), ctypes.byref(out)),
+               "avse_resample_counts")
+    return out.value
+
+
+def resample(signals, sr_in, sr_out):
+    """scipy.signal.resample_poly(x, up, down) with its defaults in one avse_resample_ragged call: signals is a [U, n]
+    float32 device tensor (-> [U, ceil(n up / down)]) or a list of 1-D float32 device tensors (-> a list of 1-D tensors,
+    views of one buffer).  float64 taps and sums, rounded once to float32; equal rates copy the bits."""
+    batch = isinstance(signals, torch.Tensor)
+    if batch:
+        _dev_f32(signals, "signals")
+        if signals.dim() != 2:
+            raise ValueError(f"signals must be [U, n] or a list of 1-D tensors, got shape {tuple(signals.shape)}")
+        U, n = int(signals.shape[0]), int(signals.shape[1])
+        buf, dev = signals, signals.device
+        lens = np.full(U, n, np.int64)
+        off = np.arange(U, dtype=np.int64) * n
+    else:
+        signals = list(signals)
+        if not signals:
+            raise ValueError("resample needs at least one signal")
+        for k, t in enumerate(signals):
+            _dev_f32(t, f"signals[{k}]")
+            if t.dim() != 1:
+                raise ValueError(f"signals[{k}] must be 1-D, got shape {tuple(t.shape)}")
+        U, dev = len(signals), signals[0].device
+        lens = np.array([t.numel() for t in signals], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        buf = torch.cat(signals)
+    n_out = np.array([resample_counts(sr_in, sr_out, int(n), True) for n in lens], dtype=np.int64)
+    out_off = np.concatenate([[0], np.cumsum(n_out)[:-1]]).astype(np.int64)
+    out = torch.empty(max(int(n_out.sum()), 1), dtype=torch.float32, device=dev)
+    if U:
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_resample_ragged(
+                ctx.handle, _lib.ptr(buf), off.ctypes.data, lens.ctypes.data, U, int(sr_in), int(sr_out), _lib.ptr(out),
+                out_off.ctypes.data, _lib.stream_handle(dev)), "avse_resample_ragged")
+    if batch:
+        return out[:int(n_out.sum())].view(U, int(n_out[0]) if U else 0)
+    return [out[int(o):int(o) + int(m)] for o, m in zip(out_off, n_out)]
+
+
+class Resampler:
+    """avse_resampler: the device state of n_streams streams at one rate pair (resampler_create).  ns / outs / fl are the
+    host totals per stream (inputs received, outputs emitted, flushed), mirroring the library's counters."""
+
+    def __init__(self, ctx, handle, n_streams, sr_in, sr_out):
+        self.ctx, self.handle = ctx, handle      # the context outlives the resampler
+        self.n_streams, self.sr_in, self.sr_out = n_streams, sr_in, sr_out
+        self.ns, self.outs, self.fl = [0] * n_streams, [0] * n_streams, [False] * n_streams
+        self._cdll = _lib.load()
+
+    def expect(self, n_new, flush):
+        """Per stream, the outputs a call with these counts emits, from the host totals (input for a flushed stream
+        emits nothing and is left to the library to refuse)."""
+        es = []
+        for b in range(self.n_streams):
+            e = 0
+            if not self.fl[b]:
+                e = resample_counts(self.sr_in, self.sr_out, self.ns[b] + n_new[b], flush[b]) - self.outs[b]
+            es.append(e)
+        return es
+
+    def __del__(self):
+        h, lib = getattr(self, "handle", None), getattr(self, "_cdll", None)
+        if h is not None and h.value and lib is not None:
+            lib.avse_resampler_destroy(h)
+            self.handle = None
+
+
+def resampler_create(n_streams, sr_in, sr_out, device=None):
+    """avse_resampler_create on the device's context -> Resampler.  A rate pair resample_supported refuses raises
+    _lib.AvseError (status 3)."""
+    if int(n_streams) < 1:
+        raise ValueError("n_streams must be positive")
+    ctx = _lib.context(device)
+    h = ctypes.c_void_p()
+    with torch.cuda.device(ctx.device_index):
+        _lib.check(_lib.load().avse_resampler_create(ctx.handle, int(n_streams), int(sr_in), int(sr_out), ctypes.byref(h)),
+                   "avse_resampler_create")
+    return Resampler(ctx, h, int(n_streams), int(sr_in), int(sr_out))
+
+
+def _resampler_push_packed(r, packed, off, n_new, flush, out_stride=None):
+    """The call of resampler_push_each on checked, packed arguments (stream b's n_new[b] samples start at element off[b] of
+    `packed`) -> (out [B, out_stride or the largest count], outputs per stream)."""
+    dev = torch.device("cuda", r.ctx.device_index)
+    B = r.n_streams
+    es = r.expect(n_new, flush)
+    stride = max(es) if out_stride is None else int(out_stride)
+    out = torch.empty((B, stride), dtype=torch.float32, device=dev)
+    (_off, p_off), (_n, p_n) = _host_i64(off), _host_i64(n_new)
+    fl = np.ascontiguousarray(flush, dtype=np.uint8)
+    got = np.full(B, -1, np.int64)
+    with torch.cuda.device(dev):
+        rc = _lib.load().avse_resampler_push_each(r.handle, _lib.ptr(packed), p_off, p_n, ctypes.c_void_p(fl.ctypes.data),
+                                                  _lib.ptr(out), stride, ctypes.c_void_p(got.ctypes.data),
+                                                  _lib.stream_handle(dev))
+    _lib.check(rc, "avse_resampler_push_each")
+    if got.tolist() != es:
+        raise _lib.AvseError(f"the resampler emitted {got.tolist()} samples, the host totals give {es}")
+    for b in range(B):
+        r.ns[b] += n_new[b]
+        r.outs[b] += es[b]
+        r.fl[b] = r.fl[b] or flush[b]
+    return out, es
+
+
+def resampler_push_each(resampler, samples=None, flush=None, out_stride=None):
+    """avse_resampler_push_each: samples is a list of B 1-D float32 device tensors (None or empty for an idle stream),
+    flush a list of B bools (streams to close: their remaining outputs come out, with zeros past the end as the one-shot
+    call has them) -> a list of B 1-D tensors, the outputs that became final.  The concatenation of a stream's outputs is,
+    bit for bit, resample() of its whole signal, however it was cut.  out_stride: the row length of the output buffer
+    (default: the largest count); one too small is refused by the library with the state unchanged.  Asynchronous on
+    torch's current stream."""
+    dev = torch.device("cuda", resampler.ctx.device_index)
+    B = resampler.n_streams
+    samples = [None] * B if samples is None else list(samples)
+    flush = [False] * B if flush is None else [bool(f) for f in flush]
+    if not (len(samples) == len(flush) == B):
+        raise ValueError(f"samples and flush must have one entry per stream ({B})")
+    n_new, parts = [], []
+    for b, x in enumerate(samples):
+        if x is not None and x.numel():
+            _dev_f32(x, f"samples[{b}]")
+            if x.dim() != 1:
+                raise ValueError(f"samples[{b}] must be 1-D")
+            if x.device.index != dev.index:
+                raise ValueError(f"the resampler lives on {dev} but samples[{b}] is on {x.device}")
+            parts.append(x)
+        n_new.append(0 if x is None else int(x.numel()))
+    packed = torch.cat(parts) if parts else None
+    off = np.concatenate([[0], np.cumsum(n_new)[:-1]])
+    out, es = _resampler_push_packed(resampler, packed, off, n_new, flush, out_stride)
+    return [out[b, :e] for b, e in enumerate(es)]
+
+
+def resampler_reset_each(resampler, streams=None):
+    """avse_resampler_reset_each: the listed streams (None: all) go back to the state after resampler_create."""
+    B = resampler.n_streams
+    which = np.ones(B, np.uint8) if streams is None else np.zeros(B, np.uint8)
+    for b in ([] if streams is None else streams):
+        if not 0 <= int(b) < B:
+            raise ValueError(f"no stream {b} in a resampler of {B}")
+        which[int(b)] = 1
+    dev = torch.device("cuda", resampler.ctx.device_index)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_resampler_reset_each(resampler.handle, ctypes.c_void_p(which.ctypes.data),
+                                                         _lib.stream_handle(dev)), "avse_resampler_reset_each")
+    for b in np.flatnonzero(which):
+        resampler.ns[b], resampler.outs[b], resampler.fl[b] = 0, 0, False
+
+
+def resampler_state(resampler):
+    """avse_resampler_state: the library's per-stream totals -> (inputs [B], outputs [B], flushed [B]) as lists."""
+    B = resampler.n_streams
+    n, m, f = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.uint8)
+    _lib.check(_lib.load().avse_resampler_state(resampler.handle, ctypes.c_void_p(n.ctypes.data),
+                                                ctypes.c_void_p(m.ctypes.data), ctypes.c_void_p(f.ctypes.data)),
+               "avse_resampler_state")
+    return n.tolist(), m.tolist(), [bool(x) for x in f]
 
 
 class Trainer:

@@ -174,10 +174,23 @@ class StreamEnhancer:
     Only geometries whose slices do not drift against the samples stream, and of those 25 fps at sample_rate 16000,
     32000 or 48000 (n_fft = rate / 25; the same weights) and 30 fps at sample_rate 24000 or 48000 (n_fft = rate / 30,
     weights of the [80, 24] x 6-frame network); ops.stream_supported is the rule.  29.97 fps, 30 fps at 16 kHz (n_fft
-    533) and 44.1 kHz raise _lib.AvseError at construction."""
+    533) and 44.1 kHz raise _lib.AvseError at construction.
+
+    Any other rate goes through `input_rate=R`: push, flush, push_each and close then take and return
+    samples at R, while the session runs at `sample_rate` (16000 by default; 24000 or 48000 with 30-fps weights).  Per
+    call a stateful device resampler (ops.resampler_create, R -> sample_rate) feeds the session and a second one
+    (sample_rate -> R) takes the session's output rows in place; nothing leaves the device.  Each resampler is
+    scipy.signal.resample_poly with its defaults in float64, and its output does not depend on the cuts, so a stream's
+    concatenated output is, bit for bit, ops.resample(R -> sample_rate) -> a plain StreamEnhancer -> ops.resample(back).
+    The network then sees the feature scale it was trained on (a native 44.1 kHz frame would sit 8.81 dB above it), and
+    nothing is lost: the mel bank ends at 8 kHz at every rate.  R samples in give F(n) = max(0, ceil((n up - H) / down))
+    session samples, H = 10 max(up, down); a flush flushes the first resampler in the call that flushes the session and
+    then the second.  The session's limits (max_slices, a flush needs n <= slice * v) apply to the resampled counts and
+    are checked on the host before the first launch, so a refused call leaves all three objects as they were.
+    input_rate=None (or equal to sample_rate) is the object described above, with no resampler built."""
 
     def __init__(self, weights, n_streams, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, max_slices=4,
-                 video_dtype=torch.float32):
+                 video_dtype=torch.float32, input_rate=None):
         self.weights = weights
         g = data_processor.frame_geometry(int(sample_rate), slice_duration_ms, 1, float(video_frame_rate))
         self.geometry = g
@@ -189,31 +202,134 @@ class StreamEnhancer:
                                          fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX,
                                          video_dtype=video_dtype, max_slices=max_slices)
         self._busy = set()      # slots handed out by open()
+        self.sample_rate = int(sample_rate)
+        self.input_rate = None if input_rate is None or int(input_rate) == int(sample_rate) else int(input_rate)
+        self.resampler_in = self.resampler_out = None
+        if self.input_rate is not None:
+            dev = torch.device("cuda", weights.ctx.device_index)
+            self.resampler_in = ops.resampler_create(n_streams, self.input_rate, self.sample_rate, dev)
+            self.resampler_out = ops.resampler_create(n_streams, self.sample_rate, self.input_rate, dev)
 
     def push(self, samples, video=None, vmean=None, vstd=None, return_spectrograms=False):
         """samples [B, n] float32 (int16-scale), video [B, v, 128, 128, F] float32 or uint8 (the session's dtype) or
         None -> the [B, n_out] newly final samples; with return_spectrograms also the [B, k, 80, spf] slices the
-        network saw and predicted for the k slices this push completed."""
+        network saw and predicted for the k slices this push completed.  With input_rate the samples in and out are at
+        that rate (and the results come back per stream, as lists, once the streams are out of step)."""
+        if self.input_rate is not None:
+            return self._anyrate_lockstep(samples, video, False, vmean, vstd, return_spectrograms)
         return ops.stream_push(self.session, samples, video, vmean, vstd, return_spectrograms)
 
     def flush(self, vmean=None, vstd=None, return_spectrograms=False):
         """Close the streams as the offline call on the signal zero-padded to the video's length; returns the rest."""
+        if self.input_rate is not None:
+            return self._anyrate_lockstep(None, None, True, vmean, vstd, return_spectrograms)
         return ops.stream_flush(self.session, vmean, vstd, return_spectrograms)
 
     def reset(self):
         ops.stream_reset(self.session)
+        if self.input_rate is not None:
+            ops.resampler_reset_each(self.resampler_in)
+            ops.resampler_reset_each(self.resampler_out)
         self._busy = set()
+
+    # ---- input_rate: resampler in -> session -> resampler out, one call of each per push ----
+    def _anyrate_check(self, n_mid, v_new, flush):
+        """The session's refusals (stream_geom.h stream_rows) for a call with these per-stream counts, from the host
+        totals, before anything is launched: the first resampler cannot be taken back once it has run."""
+        s, g = self.session, self.geometry
+        spf = g["spectrogram_samples_per_slice"]
+        slice_, M = spf * g["hop_length"], s.max_slices
+        for b in range(s.n_streams):
+            dn, dv, fl = n_mid[b], v_new[b], flush[b]
+            if s.fl[b] and (dn > 0 or dv > 0 or fl):
+                why = "pushed or flushed after its flush: only a reset is legal"
+            else:
+                n2, v2 = s.ns[b] + dn, s.vs[b] + dv
+                if fl and n2 > slice_ * v2:
+                    why = "flush: more samples than the video slices cover (n > slice * v)"
+                else:
+                    _, k0, _ = ops.stream_counts(s.ns[b], s.vs[b], s.fl[b], s)
+                    f1, k1, _ = ops.stream_counts(n2, v2, s.fl[b] or fl, s)
+                    if k1 - k0 > M:
+                        why = "the call would complete more than max_slices slices"
+                    elif n2 - slice_ * v2 > slice_ * M:
+                        why = "more than max_slices slices of samples queued ahead of the video"
+                    elif v2 - f1 // spf > M:
+                        why = "more than max_slices video slices queued ahead of the samples"
+                    else:
+                        continue
+            raise _lib.AvseError(f"StreamEnhancer(input_rate={self.input_rate}): stream {b}: {why} (counts at "
+                                 f"{self.sample_rate} Hz; nothing was launched)")
+
+    def _anyrate_step(self, packed, off, n_new, vpacked, v_new, flush, vmean, vstd, return_spectrograms):
+        """One call of the chain on packed arguments -> (out [B, max count] at input_rate, counts, mel, pred, slices)."""
+        rin, rout, s = self.resampler_in, self.resampler_out, self.session
+        B = s.n_streams
+        for b in range(B):
+            if rin.fl[b] and (n_new[b] > 0 or flush[b]):
+                raise _lib.AvseError(f"StreamEnhancer(input_rate={self.input_rate}): stream {b}: pushed or flushed after "
+                                     "its flush: only a reset is legal")
+        n_mid = rin.expect(n_new, flush)
+        self._anyrate_check(n_mid, v_new, flush)
+        mid, n_mid = ops._resampler_push_packed(rin, packed, off, n_new, flush)
+        stride = int(mid.shape[1])
+        enh, mel, pred, ks, es = ops._stream_push_packed(s, mid, [b * stride for b in range(B)], n_mid, vpacked, v_new,
+                                                         flush, vmean, vstd, return_spectrograms)
+        stride = int(enh.shape[1])
+        out, n_ret = ops._resampler_push_packed(rout, enh, [b * stride for b in range(B)], es, flush)
+        return out, n_ret, mel, pred, ks
+
+    def _anyrate_lockstep(self, samples, video, flush, vmean, vstd, return_spectrograms):
+        w, s = self.weights, self.session
+        B = s.n_streams
+        n = v = 0
+        if samples is not None:
+            ops._dev_f32(samples, "samples")
+            if samples.dim() != 2 or samples.shape[0] != B:
+                raise ValueError(f"samples must be [{B}, n]")
+            n = int(samples.shape[1])
+        if video is not None:
+            if ops._dev_video(video, "video", (128, 128, w.F)) != s.video_dtype:
+                raise TypeError(f"video is {video.dtype}, the session was created for the other video dtype")
+            if video.dim() != 5 or video.shape[0] != B:
+                raise ValueError(f"video must be [{B}, v, 128, 128, {w.F}]")
+            v = int(video.shape[1])
+        todo = [flush and not f for f in s.fl]
+        if flush and not any(todo):
+            raise _lib.AvseError("flush after flush: only reset is legal")
+        out, n_ret, mel, pred, ks = self._anyrate_step(samples if n else None, [b * n for b in range(B)], [n] * B,
+                                                       video.reshape((B * v,) + tuple(video.shape[2:])) if v else None,
+                                                       [v] * B, todo, vmean, vstd, return_spectrograms)
+        if len(set(n_ret)) > 1 or len(set(ks)) > 1:
+            return ops._stream_split(out, mel, pred, ks, n_ret, return_spectrograms)
+        out = out[:, :n_ret[0]]
+        if not return_spectrograms:
+            return out
+        shape = (B, ks[0], 80, s.spf)
+        return out, mel.view(shape), pred.view(shape)
+
+    def _anyrate_each(self, samples, video, flush, vmean, vstd, return_spectrograms):
+        packed, off, n_new, vpacked, v_new, flush = ops._stream_pack_each(self.session, samples, video, flush, vmean, vstd)
+        out, n_ret, mel, pred, ks = self._anyrate_step(packed, off, n_new, vpacked, v_new, flush, vmean, vstd,
+                                                       return_spectrograms)
+        return ops._stream_split(out, mel, pred, ks, n_ret, return_spectrograms)
 
     # ---- independent streams: the slots of one session serve callers that never move together ----
     def push_each(self, samples=None, video=None, flush=None, vmean=None, vstd=None, return_spectrograms=False):
         """Every stream by its own amount (ops.stream_push_each): samples / video are lists with one tensor (1-D float32;
         [v, 128, 128, F]) or None per stream, flush a list of bools -> per-stream lists of what push returns.  A stream
-        without input costs nothing; each stream's output is, bit for bit, that of a session of its own."""
+        without input costs nothing; each stream's output is, bit for bit, that of a session of its own.  With
+        input_rate the samples in and out are at that rate."""
+        if self.input_rate is not None:
+            return self._anyrate_each(samples, video, flush, vmean, vstd, return_spectrograms)
         return ops.stream_push_each(self.session, samples, video, flush, vmean, vstd, return_spectrograms)
 
     def reset_streams(self, ids):
         """The listed streams back to the state after construction; the others keep streaming."""
         ops.stream_reset_each(self.session, ids)
+        if self.input_rate is not None:
+            ops.resampler_reset_each(self.resampler_in, ids)
+            ops.resampler_reset_each(self.resampler_out, ids)
 
     def open(self):
         """-> a free slot (the lowest stream no caller holds) for a caller that joins; close() gives it back."""
@@ -234,14 +350,21 @@ class StreamEnhancer:
     @property
     def counts(self):
         """Host totals: dict(samples, video_slices, frames, slices, emitted) while the streams are in step, else the
-        same keys with one list entry per stream."""
+        same keys with one list entry per stream.  With input_rate the keys above count at the session's rate, and
+        `received` / `returned` count the samples taken and given back at input_rate."""
         s = self.session
         if s.in_step:
             f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
-            return dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+            c = dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+            if self.input_rate is not None:
+                c.update(received=self.resampler_in.ns[0], returned=self.resampler_out.outs[0])
+            return c
         rows = [ops.stream_counts(n, v, fl, s) for n, v, fl in zip(s.ns, s.vs, s.fl)]
-        return dict(samples=list(s.ns), video_slices=list(s.vs), frames=[r[0] for r in rows],
-                    slices=[r[1] for r in rows], emitted=[r[2] for r in rows])
+        c = dict(samples=list(s.ns), video_slices=list(s.vs), frames=[r[0] for r in rows],
+                 slices=[r[1] for r in rows], emitted=[r[2] for r in rows])
+        if self.input_rate is not None:
+            c.update(received=list(self.resampler_in.ns), returned=list(self.resampler_out.outs))
+        return c
 
     @property
     def range_bits(self):

@@ -35,7 +35,9 @@ extern "C" {
  *    only, nothing existing changed): avse_mix_pairs, avse_video_stats, avse_eval_pairs,
  *    avse_eval_pairs_sized, avse_eval_pairs_ext, avse_stream_create, avse_stream_counts, avse_stream_push,
  *    avse_stream_flush, avse_stream_reset, avse_stream_destroy, avse_stream_push_each, avse_stream_reset_each,
- *    avse_stream_state, avse_stream_supported */
+ *    avse_stream_state, avse_stream_supported, avse_resample_supported, avse_resample_counts, avse_resample_ragged,
+ *    avse_resampler_create, avse_resampler_push_each, avse_resampler_reset_each, avse_resampler_state,
+ *    avse_resampler_destroy */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -484,6 +486,52 @@ int avse_stream_push_each(avse_stream* s,
 int avse_stream_reset_each(avse_stream* s, const uint8_t* which /* HOST [B] */, void* stream);
 /* HOST: per-stream totals (samples, video slices, flushed) of the session, [n_streams] each; any output nullable. */
 int avse_stream_state(const avse_stream* s, int64_t* n_samples, int64_t* n_video, uint8_t* flushed);
+
+/* ---- resampling: any sample rate around a session ----
+ * y = scipy.signal.resample_poly(x, up, down) with its defaults, up / down = (sr_out / g) / (sr_in / g),
+ * g = gcd(sr_in, sr_out): the filter h of avse_eval_pairs' step 1, H = 10 max(up, down),
+ *   y[k] = sum_j h[H + k down - j up] x[j] over the j in [0, n) that keep the tap index in [0, 2H],
+ * ceil(n up / down) outputs for n inputs.  Equal rates are a copy of the bits.  Taps and accumulator are float64, one
+ * fma per tap in ascending j (2H / up + 1 of them), the sum rounded once to float32: the value of output k is a function
+ * of k and the stream's samples alone, whatever the cuts, the batch or the other streams.
+ * Output k reads inputs up to floor((H + k down) / up), so after n inputs F(n) = max(0, ceil((n up - H) / down))
+ * outputs are final; a flush brings the total to ceil(n up / down), with zeros past the end as the one-shot call has
+ * them.  The next output needs at most the last T = 2H / up + 1 inputs (56 at 44100 -> 16000, 21 at 16000 -> 44100).
+ *
+ * HOST only: 0 when the pair is served, else AVSE_ERR_INVALID (a rate <= 0) or AVSE_ERR_UNSUPPORTED (max(up, down) > 640
+ * after reduction, e.g. 16001 -> 16000; the reduced ratio is in avse_last_error).  8, 11.025, 12, 16, 22.05, 24, 32,
+ * 44.1, 48, 88.2 and 96 kHz against 16 and 24 kHz are served in both directions. */
+int avse_resample_supported(int sr_in, int sr_out);
+/* HOST only: *n_out = F(n_in), or ceil(n_in up / down) when flushed.  n_in in 0 .. 2^40. */
+int avse_resample_counts(int sr_in, int sr_out, int64_t n_in, int flushed, int64_t* n_out);
+/* One-shot, ragged: utterance u's n_samples[u] samples at sig + sig_off[u] -> its ceil(n_samples[u] up / down) outputs
+ * at out + out_off[u] (offsets in floats, HOST arrays, as avse_spectrogram_ragged takes sig_off; n_samples[u] == 0 is
+ * legal and writes nothing).  The streaming kernel on a fresh state with every utterance flushed, in one launch.  The
+ * rows go up through context scratch, which grows outside a stream capture only; the taps of a ratio are built at the
+ * first call with it (the context keeps the last four).  Asynchronous on `stream`. */
+int avse_resample_ragged(avse_ctx* ctx, const float* sig, const int64_t* sig_off, const int64_t* n_samples,
+                         int64_t n_utt, int sr_in, int sr_out, float* out, const int64_t* out_off, void* stream);
+
+typedef struct avse_resampler avse_resampler;
+/* n_streams (1 .. 1024) independent streams at one rate pair.  State per stream: two copies of its last T samples
+ * (a call reads one and writes the other, so one launch serves outputs and history) and the host counters. */
+int avse_resampler_create(avse_ctx* ctx, int64_t n_streams, int sr_in, int sr_out, avse_resampler** out);
+/* Stream b receives n_new[b] samples at samples + sample_off[b] and is closed when flush && flush[b]; row b of
+ * out [n_streams][out_stride] receives the host_n_out[b] outputs that became final (the layout avse_stream_push_each
+ * reads through sample_off and writes as out).  One launch for all streams, an idle stream costs no blocks.
+ * Refused with AVSE_ERR_INVALID before any GPU work, the state unchanged, naming the first offending stream: a negative
+ * count, a stream pushed (or flushed again) after its flush, more outputs than out_stride.
+ * The call allocates nothing and does not synchronise: the rows go up from a ring of four pinned slots, and the host
+ * waits only when four calls are still queued.  Not capturable into a graph. */
+int avse_resampler_push_each(avse_resampler* r, const float* samples, const int64_t* sample_off /* HOST [B] */,
+                             const int64_t* n_new /* HOST [B] */, const uint8_t* flush /* HOST [B], nullable */,
+                             float* out, int64_t out_stride, int64_t* host_n_out /* HOST [B] */, void* stream);
+/* Streams with which[b] != 0 (NULL: all) go back to the state after create.  Host counters only: a fresh stream never
+ * reads its history. */
+int avse_resampler_reset_each(avse_resampler* r, const uint8_t* which /* HOST [B], nullable */, void* stream);
+/* HOST: per-stream totals (inputs received, outputs emitted, flushed), [n_streams] each; any output nullable. */
+int avse_resampler_state(const avse_resampler* r, int64_t* n_in, int64_t* n_out, uint8_t* flushed);
+void avse_resampler_destroy(avse_resampler* r);
 
 /* VideoNormalizer.normalize (data_processor.py:208-212), in place on device (float32 only: uint8 video takes the
  * normaliser fused into the forward, vnorm_mean / vnorm_std):

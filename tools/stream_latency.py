@@ -13,10 +13,13 @@ stream).  Per call:
   host_sync_ms  host clock around the call and a synchronise after it
 The device is synchronised between calls, so no call queues behind the one before.  Prints one JSON line per case with
 the median and the 99th percentile of each; --out appends them to a file.
+--input-rate R adds the case stream_push_input_rate: the same tick through StreamEnhancer(input_rate=R), i.e. a push of
+R / 5 samples (8,820 at 44.1 kHz) through resampler in -> session -> resampler out, beside the plain push of the same run.
 
   python tools/stream_latency.py --out profiles/stream_latency.jsonl
   python tools/stream_latency.py --sample-rate 48000 --streams 1,64                        # the 3-phase kernels
   python tools/stream_latency.py --fps 30 --sample-rate 24000 --streams 1,64               # 30-fps video: the 800-point kernels
+  python tools/stream_latency.py --input-rate 44100 --streams 1,64                          # + resampler in and out (K18)
   python tools/stream_latency.py --yardstick-only --root <checkout of the parent commit>   # the same script on the parent
 """
 import argparse
@@ -58,6 +61,8 @@ def main():
     ap.add_argument("--sample-rate", type=int, default=16000,
                     help="16000, 32000 or 48000 (25 fps: n_fft = rate / 25); with --fps 30: 24000 or 48000 (n_fft = rate / 30)")
     ap.add_argument("--fps", type=float, default=25.0, help="video frame rate: 25, or 30 (the [80, 24] x 6-frame network)")
+    ap.add_argument("--input-rate", type=int, default=0,
+                    help="also time the push through StreamEnhancer(input_rate=R): R / 5 samples per tick")
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -104,6 +109,13 @@ def main():
                 from avse_amd.pipeline import StreamEnhancer
                 enh = StreamEnhancer(dw, B, **rate)
                 cases.append(("stream_push", lambda i, enh=enh: enh.push(chunks[i % 8], video, mean, std)))
+                if args.input_rate:
+                    R = args.input_rate
+                    sig_r = ops.to_device(rng.normal(0, 3000, (B, (R // 5) * 8)).round().astype(np.float32))
+                    chunks_r = [sig_r[:, (R // 5) * k:(R // 5) * (k + 1)].contiguous() for k in range(8)]
+                    enh_r = StreamEnhancer(dw, B, input_rate=R, **rate)
+                    cases.append(("stream_push_input_rate",
+                                  lambda i, enh_r=enh_r, chunks_r=chunks_r: enh_r.push(chunks_r[i % 8], video, mean, std)))
             off = Enhancer(dw, **rate)
             cases.append(("enhancer_1_slice", lambda i, off=off: off(chunks[i % 8], video, mean, std)))
             for name, fn in cases:
@@ -112,6 +124,10 @@ def main():
                 if name == "stream_push":
                     r["emitted_samples"] = enh.counts["emitted"]
                     assert r["emitted_samples"] == sl * (n_calls - 1) - 2 * (sl // T), r   # every push completed its slice
+                if name == "stream_push_input_rate":
+                    r["input_rate"] = args.input_rate
+                    r["returned_samples"] = enh_r.counts["returned"]
+                    assert enh_r.counts["slices"] == n_calls - 1, r                         # every push completed its slice
                 lines.append(json.dumps(r))
                 print(lines[-1], flush=True)
     if args.out:
