@@ -142,6 +142,21 @@ SIGNATURES = {
     "avse_resampler_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
     "avse_resampler_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "avse_resampler_destroy": (None, [_c_void_p]),
+    # retiming (a rate is num, den): supported(in_num, in_den, out_num, out_den); counts(rates.., F, n_frames, flushed,
+    # host out_frames, host out_slices); ragged(ctx, frames, host frame_off, host n_frames, n_utt, video_dtype, rates.., F,
+    # out, out_slices_cap, host k, stream); retimer create(ctx, n_streams, rates.., F, video_dtype, out); push_each(r,
+    # frames, host frame_off, host n_new, host flush, out, out_slices_cap, host k_new, stream); reset_each(r, host which,
+    # stream); state(r, host n_in, host n_slices, host flushed)
+    "avse_retime_supported": (_int, [_i64, _i64, _i64, _i64]),
+    "avse_retime_counts": (_int, [_i64, _i64, _i64, _i64, _int, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "avse_retime_ragged": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _i64, _i64, _i64, _i64, _int,
+                                  _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "avse_retimer_create": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),
+    "avse_retimer_push_each": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                      _c_void_p]),
+    "avse_retimer_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
+    "avse_retimer_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_retimer_destroy": (None, [_c_void_p]),
     "avse_debug_scratch": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "avse_trainer_create": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_c_void_p)]),
     "avse_trainer_create_shape": (_int, [_c_void_p, _c_void_p, _i64, _i64, _int, _int, ctypes.POINTER(_c_void_p)]),

@@ -4,6 +4,7 @@ Every function here is a thin shape/dtype check around one C-ABI call (include/a
 on torch's current HIP stream.  Nothing computes on the CPU.
 """
 import ctypes
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -1246,6 +1247,232 @@ def resampler_state(resampler):
     _lib.check(_lib.load().avse_resampler_state(resampler.handle, ctypes.c_void_p(n.ctypes.data),
                                                 ctypes.c_void_p(m.ctypes.data), ctypes.c_void_p(f.ctypes.data)),
                "avse_resampler_state")
+    return n.tolist(), m.tolist(), [bool(x) for x in f]
+
+
+def frame_rate(fps):
+    """A frame rate as a rational: an int, a fractions.Fraction or a (num, den) pair is taken as it is; a float becomes
+    Fraction(x).limit_denominator(1001), so 29.97 is 2997/100 and 30000 / 1001 (NTSC, as a float) is 30000/1001.  Pass
+    the pair or the Fraction where the float would be ambiguous."""
+    if isinstance(fps, (tuple, list)):
+        if len(fps) != 2:
+            raise ValueError(f"a frame rate is a number or a (num, den) pair, got {fps!r}")
+        return Fraction(int(fps[0]), int(fps[1]))
+    if isinstance(fps, (int, Fraction)):
+        return Fraction(fps)
+    return Fraction(float(fps)).limit_denominator(1001)
+
+
+def _rates(fps_in, fps_out):
+    a, b = frame_rate(fps_in), frame_rate(fps_out)
+    return a.numerator, a.denominator, b.numerator, b.denominator
+
+
+def _dev_frames(t, name, dims):
+    """Mouth crops before retiming: a float32 or uint8 device tensor [..., 128, 128] with `dims` dimensions."""
+    dt = _dev_video(t, name, (128, 128))
+    if t.dim() != dims:
+        raise ValueError(f"{name} must be {'[U, n, 128, 128]' if dims == 4 else '[n, 128, 128]'}, got shape {tuple(t.shape)}")
+    return dt
+
+
+def retime_supported(fps_in, fps_out, return_message=False):
+    """avse_retime_supported (host only, no GPU): 0 when fps_in -> fps_out is served (max(p, q) <= 65536 for the reduced
+    p / q = fps_in / fps_out), else the status retime / retimer_create would raise with (3: unsupported, 1: invalid).
+    Rates as frame_rate takes them.  return_message: -> (status, the library's reason; "" for status 0)."""
+    lib = _lib.load()
+    rc = int(lib.avse_retime_supported(*_rates(fps_in, fps_out)))
+    if not return_message:
+        return rc
+    return rc, (lib.avse_last_error().decode(errors="replace") if rc else "")
+
+
+def retime_counts(fps_in, fps_out, frames_per_slice, n, flushed=False):
+    """avse_retime_counts (host only, no GPU) -> (output frames, slices) that are final after n input frames:
+    G(n) = floor((n - 1) q / p) + 1 frames (0 for n = 0), or all ceil(n q / p) of a flushed stream; slices = frames div
+    frames_per_slice."""
+    f, k = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(_lib.load().avse_retime_counts(*_rates(fps_in, fps_out), int(frames_per_slice), int(n), int(bool(flushed)),
+                                              ctypes.byref(f), ctypes.byref(k)), "avse_retime_counts")
+    return f.value, k.value
+
+
+def retime(frames, fps_in, fps_out, frames_per_slice):
+    """Linear frame-rate conversion into the session's slices in one avse_retime_ragged call: frames is a
+    [U, n, 128, 128] float32 or uint8 device tensor (-> [U, S, 128, 128, F]) or a list of [n_u, 128, 128] tensors of one
+    dtype (-> a list of [S_u, 128, 128, F] tensors, views of one buffer), S = ceil(n q / p) div F.  Output frame j blends
+    input frames j p div q and the next by (j p mod q) / q (include/avse.h states the rounding); past the end the last
+    frame is repeated, and the frames that do not fill a slice are dropped."""
+    F = int(frames_per_slice)
+    batch = isinstance(frames, torch.Tensor)
+    if batch:
+        vdt = _dev_frames(frames, "frames", 4)
+        U, n = int(frames.shape[0]), int(frames.shape[1])
+        buf, dev = frames, frames.device
+        lens = np.full(U, n, np.int64)
+    else:
+        frames = list(frames)
+        if not frames:
+            raise ValueError("retime needs at least one utterance")
+        vdt = _dev_frames(frames[0], "frames[0]", 3)
+        for k, t in enumerate(frames):
+            if _dev_frames(t, f"frames[{k}]", 3) != vdt:
+                raise TypeError("the utterances' frames must have one dtype")
+        U, dev = len(frames), frames[0].device
+        lens = np.array([t.shape[0] for t in frames], dtype=np.int64)
+        buf = torch.cat(frames)
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    ks = np.array([retime_counts(fps_in, fps_out, F, int(n), True)[1] for n in lens], dtype=np.int64)
+    total = int(ks.sum())
+    out = torch.empty((max(total, 1), 128, 128, F), dtype=buf.dtype, device=dev)
+    got = np.full(max(U, 1), -1, np.int64)
+    if U:
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_retime_ragged(
+                ctx.handle, _lib.ptr(buf) if buf.numel() else None, off.ctypes.data, lens.ctypes.data, U, vdt,
+                *_rates(fps_in, fps_out), F, _lib.ptr(out), total, got.ctypes.data, _lib.stream_handle(dev)),
+                "avse_retime_ragged")
+        if got.tolist() != ks.tolist():
+            raise _lib.AvseError(f"the retimer wrote {got.tolist()} slices, the host counts give {ks.tolist()}")
+    if batch:
+        return out[:total].view(U, int(ks[0]) if U else 0, 128, 128, F)
+    first = np.concatenate([[0], np.cumsum(ks)]).astype(int)
+    return [out[first[u]:first[u + 1]] for u in range(U)]
+
+
+class Retimer:
+    """avse_retimer: the device state of n_streams streams at one rate pair (retimer_create).  ns / ks / fl are the host
+    totals per stream (frames received, slices handed out, flushed), mirroring the library's counters."""
+
+    def __init__(self, ctx, handle, n_streams, fps_in, fps_out, frames_per_slice, video_dtype):
+        self.ctx, self.handle = ctx, handle      # the context outlives the retimer
+        self.n_streams, self.fps_in, self.fps_out, self.F = n_streams, fps_in, fps_out, frames_per_slice
+        self.video_dtype = video_dtype
+        self.ns, self.ks, self.fl = [0] * n_streams, [0] * n_streams, [False] * n_streams
+        self._cdll = _lib.load()
+
+    def expect(self, n_new, flush):
+        """Per stream, the slices a call with these counts completes, from the host totals (input for a flushed stream
+        completes nothing and is left to the library to refuse)."""
+        ks = []
+        for b in range(self.n_streams):
+            k = 0
+            if not self.fl[b]:
+                k = retime_counts(self.fps_in, self.fps_out, self.F, self.ns[b] + n_new[b], flush[b])[1] - self.ks[b]
+            ks.append(k)
+        return ks
+
+    def __del__(self):
+        h, lib = getattr(self, "handle", None), getattr(self, "_cdll", None)
+        if h is not None and h.value and lib is not None:
+            lib.avse_retimer_destroy(h)
+            self.handle = None
+
+
+def retimer_create(n_streams, fps_in, fps_out, frames_per_slice, video_dtype=torch.float32, device=None):
+    """avse_retimer_create on the device's context -> Retimer.  Rates as frame_rate takes them; a pair retime_supported
+    refuses raises _lib.AvseError (status 3).  video_dtype: torch.float32 or torch.uint8, the element type of every
+    push's frames and of the slices."""
+    if int(n_streams) < 1:
+        raise ValueError("n_streams must be positive")
+    if video_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"video_dtype must be torch.float32 or torch.uint8, got {video_dtype}")
+    vdt = _lib.AVSE_VIDEO_U8 if video_dtype == torch.uint8 else _lib.AVSE_VIDEO_F32
+    a, b = frame_rate(fps_in), frame_rate(fps_out)
+    ctx = _lib.context(device)
+    h = ctypes.c_void_p()
+    with torch.cuda.device(ctx.device_index):
+        _lib.check(_lib.load().avse_retimer_create(ctx.handle, int(n_streams), *_rates(a, b), int(frames_per_slice), vdt,
+                                                   ctypes.byref(h)), "avse_retimer_create")
+    return Retimer(ctx, h, int(n_streams), a, b, int(frames_per_slice), vdt)
+
+
+def _retimer_pack(r, frames):
+    """retimer_push_each's frames, checked and packed on the device (one torch.cat) -> (packed frames or None, first
+    frame per stream [B], frames per stream [B])."""
+    dev = torch.device("cuda", r.ctx.device_index)
+    n_new, parts = [], []
+    for b, x in enumerate(frames):
+        if x is not None and x.shape[0]:
+            if _dev_frames(x, f"frames[{b}]", 3) != r.video_dtype:
+                raise TypeError(f"frames[{b}] is {x.dtype}, the retimer was created for the other video dtype")
+            if x.device.index != dev.index:
+                raise ValueError(f"the retimer lives on {dev} but frames[{b}] is on {x.device}")
+            parts.append(x)
+        n_new.append(0 if x is None else int(x.shape[0]))
+    packed = (parts[0] if len(parts) == 1 else torch.cat(parts)) if parts else None
+    return packed, np.concatenate([[0], np.cumsum(n_new)[:-1]]), n_new
+
+
+def _retimer_push_packed(r, packed, off, n_new, flush, out_slices=None):
+    """The call of retimer_push_each on checked, packed arguments (stream b's n_new[b] frames start at frame off[b] of
+    `packed`) -> (the completed slices [sum k, 128, 128, F] stream-major, slices per stream)."""
+    dev = torch.device("cuda", r.ctx.device_index)
+    B = r.n_streams
+    ks = r.expect(n_new, flush)
+    cap = sum(ks) if out_slices is None else int(out_slices)
+    out = torch.empty((cap, 128, 128, r.F), dtype=torch.uint8 if r.video_dtype == _lib.AVSE_VIDEO_U8 else torch.float32,
+                      device=dev)
+    (_off, p_off), (_n, p_n) = _host_i64(off), _host_i64(n_new)
+    fl = np.ascontiguousarray(flush, dtype=np.uint8)
+    got = np.full(B, -1, np.int64)
+    with torch.cuda.device(dev):
+        rc = _lib.load().avse_retimer_push_each(r.handle, _lib.ptr(packed), p_off, p_n, ctypes.c_void_p(fl.ctypes.data),
+                                                _lib.ptr(out) if cap else None, cap, ctypes.c_void_p(got.ctypes.data),
+                                                _lib.stream_handle(dev))
+    _lib.check(rc, "avse_retimer_push_each")
+    if got.tolist() != ks:
+        raise _lib.AvseError(f"the retimer completed {got.tolist()} slices, the host totals give {ks}")
+    for b in range(B):
+        r.ns[b] += n_new[b]
+        r.ks[b] += ks[b]
+        r.fl[b] = r.fl[b] or flush[b]
+    return out, ks
+
+
+def retimer_push_each(retimer, frames=None, flush=None, out_slices=None):
+    """avse_retimer_push_each: frames is a list of B [n_b, 128, 128] device tensors in the retimer's dtype (None or empty
+    for an idle stream), flush a list of B bools (streams to close: their remaining frames come out as copies of the
+    last one, and the frames that do not fill a slice are dropped) -> a list of B [k_b, 128, 128, F] tensors, the slices
+    that became complete, views of one buffer in stream_push_each's packed video layout.  The concatenation of a stream's
+    slices is, bit for bit, retime() of all its frames, however they were cut.  out_slices: the slices the output buffer
+    holds (default: what the call completes); one too small is refused by the library with the state unchanged.
+    Asynchronous on torch's current stream."""
+    B = retimer.n_streams
+    frames = [None] * B if frames is None else list(frames)
+    flush = [False] * B if flush is None else [bool(f) for f in flush]
+    if not (len(frames) == len(flush) == B):
+        raise ValueError(f"frames and flush must have one entry per stream ({B})")
+    packed, off, n_new = _retimer_pack(retimer, frames)
+    out, ks = _retimer_push_packed(retimer, packed, off, n_new, flush, out_slices)
+    first = np.concatenate([[0], np.cumsum(ks)]).astype(int)
+    return [out[first[b]:first[b + 1]] for b in range(B)]
+
+
+def retimer_reset_each(retimer, streams=None):
+    """avse_retimer_reset_each: the listed streams (None: all) go back to the state after retimer_create."""
+    B = retimer.n_streams
+    which = np.ones(B, np.uint8) if streams is None else np.zeros(B, np.uint8)
+    for b in ([] if streams is None else streams):
+        if not 0 <= int(b) < B:
+            raise ValueError(f"no stream {b} in a retimer of {B}")
+        which[int(b)] = 1
+    dev = torch.device("cuda", retimer.ctx.device_index)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().avse_retimer_reset_each(retimer.handle, ctypes.c_void_p(which.ctypes.data),
+                                                       _lib.stream_handle(dev)), "avse_retimer_reset_each")
+    for b in np.flatnonzero(which):
+        retimer.ns[b], retimer.ks[b], retimer.fl[b] = 0, 0, False
+
+
+def retimer_state(retimer):
+    """avse_retimer_state: the library's per-stream totals -> (frames [B], slices [B], flushed [B]) as lists."""
+    B = retimer.n_streams
+    n, m, f = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.uint8)
+    _lib.check(_lib.load().avse_retimer_state(retimer.handle, ctypes.c_void_p(n.ctypes.data),
+                                              ctypes.c_void_p(m.ctypes.data), ctypes.c_void_p(f.ctypes.data)),
+               "avse_retimer_state")
     return n.tolist(), m.tolist(), [bool(x) for x in f]
 
 

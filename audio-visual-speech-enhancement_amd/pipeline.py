@@ -187,10 +187,24 @@ class StreamEnhancer:
     session samples, H = 10 max(up, down); a flush flushes the first resampler in the call that flushes the session and
     then the second.  The session's limits (max_slices, a flush needs n <= slice * v) apply to the resampled counts and
     are checked on the host before the first launch, so a refused call leaves all three objects as they were.
-    input_rate=None (or equal to sample_rate) is the object described above, with no resampler built."""
+    input_rate=None (or equal to sample_rate) is the object described above, with no resampler built.
+
+    A camera at any other frame rate goes through `input_fps=R`: `video_frame_rate` stays the rate of
+    the weights and the session, and the `video` arguments become mouth crops at R fps: push takes frames
+    [B, n, 128, 128], push_each and close take [n_b, 128, 128] per stream (float32 or uint8, the session's dtype).  Per
+    call a stateful device retimer (ops.retimer_create, R -> video_frame_rate; linear interpolation between the two
+    nearest frames, include/avse.h states the rounding) turns them into the session's slices, which go on to the session
+    with no copy; its output does not depend on the cuts, so a stream's concatenated result is, bit for bit,
+    ops.retime(all its frames) -> the same StreamEnhancer without input_fps, fed those slices.  R is an int, a
+    fractions.Fraction, a (num, den) pair or a float (ops.frame_rate: 29.97 is 2997/100, 30000 / 1001 is NTSC).  n frames
+    in give G(n) = floor((n - 1) q / p) + 1 output frames, p / q = R / video_frame_rate, of which every F make a slice; a
+    flush flushes the retimer first (the last frame is repeated up to ceil(n q / p) frames, what does not fill a slice is
+    dropped), then the rest of the chain.  Alone or together with input_rate; the session's limits are checked on the
+    host before the first launch either way.  input_fps=None (or equal to video_frame_rate) builds no retimer.  Whether
+    the 25-fps network prefers blended or repeated frames has not been measured."""
 
     def __init__(self, weights, n_streams, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, max_slices=4,
-                 video_dtype=torch.float32, input_rate=None):
+                 video_dtype=torch.float32, input_rate=None, input_fps=None):
         self.weights = weights
         g = data_processor.frame_geometry(int(sample_rate), slice_duration_ms, 1, float(video_frame_rate))
         self.geometry = g
@@ -209,19 +223,25 @@ class StreamEnhancer:
             dev = torch.device("cuda", weights.ctx.device_index)
             self.resampler_in = ops.resampler_create(n_streams, self.input_rate, self.sample_rate, dev)
             self.resampler_out = ops.resampler_create(n_streams, self.sample_rate, self.input_rate, dev)
+        self.input_fps = self.retimer = None
+        if input_fps is not None and ops.frame_rate(input_fps) != ops.frame_rate(video_frame_rate):
+            self.input_fps = ops.frame_rate(input_fps)
+            self.retimer = ops.retimer_create(n_streams, self.input_fps, video_frame_rate, weights.F, video_dtype,
+                                              torch.device("cuda", weights.ctx.device_index))
 
     def push(self, samples, video=None, vmean=None, vstd=None, return_spectrograms=False):
         """samples [B, n] float32 (int16-scale), video [B, v, 128, 128, F] float32 or uint8 (the session's dtype) or
         None -> the [B, n_out] newly final samples; with return_spectrograms also the [B, k, 80, spf] slices the
         network saw and predicted for the k slices this push completed.  With input_rate the samples in and out are at
-        that rate (and the results come back per stream, as lists, once the streams are out of step)."""
-        if self.input_rate is not None:
+        that rate (and the results come back per stream, as lists, once the streams are out of step).  With input_fps
+        video is [B, n, 128, 128]: n frames at that rate."""
+        if self.input_rate is not None or self.retimer is not None:
             return self._anyrate_lockstep(samples, video, False, vmean, vstd, return_spectrograms)
         return ops.stream_push(self.session, samples, video, vmean, vstd, return_spectrograms)
 
     def flush(self, vmean=None, vstd=None, return_spectrograms=False):
         """Close the streams as the offline call on the signal zero-padded to the video's length; returns the rest."""
-        if self.input_rate is not None:
+        if self.input_rate is not None or self.retimer is not None:
             return self._anyrate_lockstep(None, None, True, vmean, vstd, return_spectrograms)
         return ops.stream_flush(self.session, vmean, vstd, return_spectrograms)
 
@@ -230,12 +250,19 @@ class StreamEnhancer:
         if self.input_rate is not None:
             ops.resampler_reset_each(self.resampler_in)
             ops.resampler_reset_each(self.resampler_out)
+        if self.retimer is not None:
+            ops.retimer_reset_each(self.retimer)
         self._busy = set()
 
-    # ---- input_rate: resampler in -> session -> resampler out, one call of each per push ----
+    # ---- input_rate / input_fps: retimer -> resampler in -> session -> resampler out, one call of each per push ----
+    def _label(self):
+        return ", ".join([f"input_rate={self.input_rate}"] * (self.input_rate is not None) +
+                         [f"input_fps={self.input_fps}"] * (self.retimer is not None))
+
     def _anyrate_check(self, n_mid, v_new, flush):
-        """The session's refusals (stream_geom.h stream_rows) for a call with these per-stream counts, from the host
-        totals, before anything is launched: the first resampler cannot be taken back once it has run."""
+        """The session's refusals (stream_geom.h stream_rows) for a call with these per-stream counts (samples at the
+        session's rate, video slices), from the host totals, before anything is launched: the retimer and the first
+        resampler cannot be taken back once they have run."""
         s, g = self.session, self.geometry
         spf = g["spectrogram_samples_per_slice"]
         slice_, M = spf * g["hop_length"], s.max_slices
@@ -258,19 +285,29 @@ class StreamEnhancer:
                         why = "more than max_slices video slices queued ahead of the samples"
                     else:
                         continue
-            raise _lib.AvseError(f"StreamEnhancer(input_rate={self.input_rate}): stream {b}: {why} (counts at "
+            raise _lib.AvseError(f"StreamEnhancer({self._label()}): stream {b}: {why} (counts at "
                                  f"{self.sample_rate} Hz; nothing was launched)")
 
-    def _anyrate_step(self, packed, off, n_new, vpacked, v_new, flush, vmean, vstd, return_spectrograms):
-        """One call of the chain on packed arguments -> (out [B, max count] at input_rate, counts, mel, pred, slices)."""
-        rin, rout, s = self.resampler_in, self.resampler_out, self.session
+    def _anyrate_step(self, packed, off, n_new, vpacked, v_new, flush, vmean, vstd, return_spectrograms, f_off=None):
+        """One call of the chain on packed arguments -> (out [B, max count] at input_rate, counts, mel, pred, slices).
+        With input_fps vpacked holds frames, v_new counts them and f_off is each stream's first frame in vpacked."""
+        rin, rout, s, rt = self.resampler_in, self.resampler_out, self.session, self.retimer
         B = s.n_streams
         for b in range(B):
-            if rin.fl[b] and (n_new[b] > 0 or flush[b]):
-                raise _lib.AvseError(f"StreamEnhancer(input_rate={self.input_rate}): stream {b}: pushed or flushed after "
+            if (rin is not None and rin.fl[b] and (n_new[b] > 0 or flush[b])) or \
+                    (rt is not None and rt.fl[b] and (v_new[b] > 0 or flush[b])):
+                raise _lib.AvseError(f"StreamEnhancer({self._label()}): stream {b}: pushed or flushed after "
                                      "its flush: only a reset is legal")
-        n_mid = rin.expect(n_new, flush)
-        self._anyrate_check(n_mid, v_new, flush)
+        n_mid = rin.expect(n_new, flush) if rin is not None else list(n_new)
+        k_vid = rt.expect(v_new, flush) if rt is not None else list(v_new)
+        self._anyrate_check(n_mid, k_vid, flush)
+        if rt is not None:
+            vpacked, v_new = ops._retimer_push_packed(rt, vpacked, f_off, v_new, flush)
+            vpacked = vpacked if sum(v_new) else None
+        if rin is None:
+            out, mel, pred, ks, es = ops._stream_push_packed(s, packed, off, n_new, vpacked, v_new, flush, vmean, vstd,
+                                                             return_spectrograms)
+            return out, es, mel, pred, ks
         mid, n_mid = ops._resampler_push_packed(rin, packed, off, n_new, flush)
         stride = int(mid.shape[1])
         enh, mel, pred, ks, es = ops._stream_push_packed(s, mid, [b * stride for b in range(B)], n_mid, vpacked, v_new,
@@ -288,7 +325,13 @@ class StreamEnhancer:
             if samples.dim() != 2 or samples.shape[0] != B:
                 raise ValueError(f"samples must be [{B}, n]")
             n = int(samples.shape[1])
-        if video is not None:
+        if video is not None and self.retimer is not None:
+            if ops._dev_frames(video, "video", 4) != s.video_dtype:
+                raise TypeError(f"video is {video.dtype}, the session was created for the other video dtype")
+            if video.shape[0] != B:
+                raise ValueError(f"video must be [{B}, n, 128, 128] (frames at input_fps)")
+            v = int(video.shape[1])
+        elif video is not None:
             if ops._dev_video(video, "video", (128, 128, w.F)) != s.video_dtype:
                 raise TypeError(f"video is {video.dtype}, the session was created for the other video dtype")
             if video.dim() != 5 or video.shape[0] != B:
@@ -299,7 +342,8 @@ class StreamEnhancer:
             raise _lib.AvseError("flush after flush: only reset is legal")
         out, n_ret, mel, pred, ks = self._anyrate_step(samples if n else None, [b * n for b in range(B)], [n] * B,
                                                        video.reshape((B * v,) + tuple(video.shape[2:])) if v else None,
-                                                       [v] * B, todo, vmean, vstd, return_spectrograms)
+                                                       [v] * B, todo, vmean, vstd, return_spectrograms,
+                                                       f_off=[b * v for b in range(B)])
         if len(set(n_ret)) > 1 or len(set(ks)) > 1:
             return ops._stream_split(out, mel, pred, ks, n_ret, return_spectrograms)
         out = out[:, :n_ret[0]]
@@ -309,9 +353,19 @@ class StreamEnhancer:
         return out, mel.view(shape), pred.view(shape)
 
     def _anyrate_each(self, samples, video, flush, vmean, vstd, return_spectrograms):
-        packed, off, n_new, vpacked, v_new, flush = ops._stream_pack_each(self.session, samples, video, flush, vmean, vstd)
+        f_off = None
+        if self.retimer is not None:
+            B = self.session.n_streams
+            frames = [None] * B if video is None else list(video)
+            if len(frames) != B:
+                raise ValueError(f"samples, video and flush must have one entry per stream ({B})")
+            packed, off, n_new, _, _, flush = ops._stream_pack_each(self.session, samples, None, flush, vmean, vstd)
+            vpacked, f_off, v_new = ops._retimer_pack(self.retimer, frames)
+        else:
+            packed, off, n_new, vpacked, v_new, flush = ops._stream_pack_each(self.session, samples, video, flush, vmean,
+                                                                              vstd)
         out, n_ret, mel, pred, ks = self._anyrate_step(packed, off, n_new, vpacked, v_new, flush, vmean, vstd,
-                                                       return_spectrograms)
+                                                       return_spectrograms, f_off=f_off)
         return ops._stream_split(out, mel, pred, ks, n_ret, return_spectrograms)
 
     # ---- independent streams: the slots of one session serve callers that never move together ----
@@ -319,8 +373,9 @@ class StreamEnhancer:
         """Every stream by its own amount (ops.stream_push_each): samples / video are lists with one tensor (1-D float32;
         [v, 128, 128, F]) or None per stream, flush a list of bools -> per-stream lists of what push returns.  A stream
         without input costs nothing; each stream's output is, bit for bit, that of a session of its own.  With
-        input_rate the samples in and out are at that rate."""
-        if self.input_rate is not None:
+        input_rate the samples in and out are at that rate; with input_fps video[b] is [n_b, 128, 128], frames at that
+        rate."""
+        if self.input_rate is not None or self.retimer is not None:
             return self._anyrate_each(samples, video, flush, vmean, vstd, return_spectrograms)
         return ops.stream_push_each(self.session, samples, video, flush, vmean, vstd, return_spectrograms)
 
@@ -330,6 +385,8 @@ class StreamEnhancer:
         if self.input_rate is not None:
             ops.resampler_reset_each(self.resampler_in, ids)
             ops.resampler_reset_each(self.resampler_out, ids)
+        if self.retimer is not None:
+            ops.retimer_reset_each(self.retimer, ids)
 
     def open(self):
         """-> a free slot (the lowest stream no caller holds) for a caller that joins; close() gives it back."""
@@ -351,19 +408,25 @@ class StreamEnhancer:
     def counts(self):
         """Host totals: dict(samples, video_slices, frames, slices, emitted) while the streams are in step, else the
         same keys with one list entry per stream.  With input_rate the keys above count at the session's rate, and
-        `received` / `returned` count the samples taken and given back at input_rate."""
+        `received` / `returned` count the samples taken and given back at input_rate.  With input_fps `video_frames`
+        counts the frames received at that rate (video_slices: the slices the retimer has handed to the session)."""
         s = self.session
         if s.in_step:
             f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
             c = dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
             if self.input_rate is not None:
                 c.update(received=self.resampler_in.ns[0], returned=self.resampler_out.outs[0])
+            if self.retimer is not None:
+                rt = self.retimer
+                c.update(video_frames=rt.ns[0] if len(set(rt.ns)) == 1 else list(rt.ns))
             return c
         rows = [ops.stream_counts(n, v, fl, s) for n, v, fl in zip(s.ns, s.vs, s.fl)]
         c = dict(samples=list(s.ns), video_slices=list(s.vs), frames=[r[0] for r in rows],
                  slices=[r[1] for r in rows], emitted=[r[2] for r in rows])
         if self.input_rate is not None:
             c.update(received=list(self.resampler_in.ns), returned=list(self.resampler_out.outs))
+        if self.retimer is not None:
+            c.update(video_frames=list(self.retimer.ns))
         return c
 
     @property

@@ -37,7 +37,8 @@ extern "C" {
  *    avse_stream_flush, avse_stream_reset, avse_stream_destroy, avse_stream_push_each, avse_stream_reset_each,
  *    avse_stream_state, avse_stream_supported, avse_resample_supported, avse_resample_counts, avse_resample_ragged,
  *    avse_resampler_create, avse_resampler_push_each, avse_resampler_reset_each, avse_resampler_state,
- *    avse_resampler_destroy */
+ *    avse_resampler_destroy, avse_retime_supported, avse_retime_counts, avse_retime_ragged, avse_retimer_create,
+ *    avse_retimer_push_each, avse_retimer_reset_each, avse_retimer_state, avse_retimer_destroy */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -532,6 +533,64 @@ int avse_resampler_reset_each(avse_resampler* r, const uint8_t* which /* HOST [B
 /* HOST: per-stream totals (inputs received, outputs emitted, flushed), [n_streams] each; any output nullable. */
 int avse_resampler_state(const avse_resampler* r, int64_t* n_in, int64_t* n_out, uint8_t* flushed);
 void avse_resampler_destroy(avse_resampler* r);
+
+/* ---- retiming: any video frame rate in front of a session ----
+ * A rate is a rational num / den (30 fps: 30 / 1; NTSC: 30000 / 1001); p / q = fps_in / fps_out, reduced.  Output frame j
+ * sits at input position j p / q: with c = j p, i0 = c div q, r = c mod q, a = A[i0], b = A[min(i0 + 1, n - 1)], per
+ * pixel
+ *   float32  float32((double(q - r) a + double(r) b) / double(q)): both products exact in float64, one rounding at the
+ *            add, one at the divide, one to float32; r == 0 gives a's bits
+ *   uint8    (2 (a (q - r) + b r) + q) div (2 q) in integers: round-half-up, exact
+ * so an output frame is a function of j and the stream's frames alone, whatever the cuts, the batch or the other
+ * streams.  Linear interpolation only.  Output j reads inputs up to ceil(j p / q), so after n >= 1 inputs
+ * G(n) = floor((n - 1) q / p) + 1 outputs are final (G(0) = 0); a flush brings the total to ceil(n q / p), the frames
+ * past G(n) being copies of the last input.  frames_per_slice (F: 5 or 6) consecutive outputs form one slice
+ * [128][128][F], frame innermost: the layout of avse_stream_push_each's `video`.  G div F slices are complete; a flush
+ * drops the remainder of ceil(n q / p) over F, as preprocess_video_sample does (data_processor.py:24-30).  Equal rates
+ * regroup the bits into slices.
+ *
+ * HOST only: 0 when the pair is served, else AVSE_ERR_INVALID (a numerator or denominator outside 1 .. 2^31 - 1) or
+ * AVSE_ERR_UNSUPPORTED (max(p, q) > 65536 after reduction; the reduced ratio is in avse_last_error).  30, 30000/1001, 24,
+ * 15, 60 and 2997/100 fps against 25 and 30 fps are served in both directions. */
+int avse_retime_supported(int64_t in_num, int64_t in_den, int64_t out_num, int64_t out_den);
+/* HOST only: *out_frames = G(n_frames), or ceil(n_frames q / p) when flushed; *out_slices = that div frames_per_slice.
+ * Either output may be NULL, not both.  n_frames in 0 .. 2^40. */
+int avse_retime_counts(int64_t in_num, int64_t in_den, int64_t out_num, int64_t out_den, int frames_per_slice,
+                       int64_t n_frames, int flushed, int64_t* out_frames, int64_t* out_slices);
+/* One-shot, ragged: utterance u's n_frames[u] frames [128][128] (video_dtype, 4-byte aligned) start at frame
+ * frame_off[u] of `frames`; its host_k[u] = ceil(n_frames[u] q / p) div frames_per_slice slices are written to `out`
+ * packed utterance-major (out_slices_cap: the slices `out` holds; HOST arrays; n_frames[u] == 0 is legal and writes
+ * nothing; host_k is written only by a call that returns 0).  The streaming kernel on a fresh state with every utterance
+ * flushed, in one launch.  The rows go up through context scratch, which grows outside a stream capture only.
+ * Asynchronous on `stream`. */
+int avse_retime_ragged(avse_ctx* ctx, const void* frames, const int64_t* frame_off, const int64_t* n_frames,
+                       int64_t n_utt, int video_dtype, int64_t in_num, int64_t in_den, int64_t out_num, int64_t out_den,
+                       int frames_per_slice, void* out, int64_t out_slices_cap, int64_t* host_k, void* stream);
+
+typedef struct avse_retimer avse_retimer;
+/* n_streams (1 .. 1024) independent streams at one rate pair, slice length and dtype.  State per stream: two copies of
+ * its last input frame and of the finished frames of its unfinished slice (a call reads one copy and writes the other,
+ * so one launch serves slices and state), 2 x (1 + F) frames in all, and the host counters. */
+int avse_retimer_create(avse_ctx* ctx, int64_t n_streams, int64_t in_num, int64_t in_den, int64_t out_num,
+                        int64_t out_den, int frames_per_slice, int video_dtype, avse_retimer** out);
+/* Stream b receives n_new[b] frames starting at frame frame_off[b] of `frames` (packed [n][128][128] in the retimer's
+ * dtype, 4-byte aligned) and is closed when flush && flush[b]; the host_k_new[b] slices it completed are appended to
+ * `out` stream-major: exactly avse_stream_push_each's packed `video`, so `out` and host_k_new feed a session with no
+ * copy.  out_slices_cap: the slices `out` holds.  One launch for all streams, an idle stream costs no blocks.
+ * Refused with AVSE_ERR_INVALID before any GPU work, the state unchanged, naming the first offending stream: a negative
+ * count, totals past 2^40 frames, a stream pushed (or flushed again) after its flush, `out` NULL or holding fewer slices
+ * than the call completes.
+ * The call allocates nothing and does not synchronise: the rows go up from a ring of four pinned slots, and the host
+ * waits only when four calls are still queued.  Not capturable into a graph. */
+int avse_retimer_push_each(avse_retimer* r, const void* frames, const int64_t* frame_off /* HOST [B] */,
+                           const int64_t* n_new /* HOST [B] */, const uint8_t* flush /* HOST [B], nullable */,
+                           void* out, int64_t out_slices_cap, int64_t* host_k_new /* HOST [B] */, void* stream);
+/* Streams with which[b] != 0 (NULL: all) go back to the state after create.  Host counters only: a fresh stream reads
+ * neither copy of its state. */
+int avse_retimer_reset_each(avse_retimer* r, const uint8_t* which /* HOST [B], nullable */, void* stream);
+/* HOST: per-stream totals (frames received, slices handed out, flushed), [n_streams] each; any output nullable. */
+int avse_retimer_state(const avse_retimer* r, int64_t* n_in, int64_t* n_slices, uint8_t* flushed);
+void avse_retimer_destroy(avse_retimer* r);
 
 /* VideoNormalizer.normalize (data_processor.py:208-212), in place on device (float32 only: uint8 video takes the
  * normaliser fused into the forward, vnorm_mean / vnorm_std):

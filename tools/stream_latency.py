@@ -20,6 +20,7 @@ R / 5 samples (8,820 at 44.1 kHz) through resampler in -> session -> resampler o
   python tools/stream_latency.py --sample-rate 48000 --streams 1,64                        # the 3-phase kernels
   python tools/stream_latency.py --fps 30 --sample-rate 24000 --streams 1,64               # 30-fps video: the 800-point kernels
   python tools/stream_latency.py --input-rate 44100 --streams 1,64                          # + resampler in and out (K18)
+  python tools/stream_latency.py --input-fps 30 --streams 1,64                              # + retimer in front (K19)
   python tools/stream_latency.py --yardstick-only --root <checkout of the parent commit>   # the same script on the parent
 """
 import argparse
@@ -63,6 +64,9 @@ def main():
     ap.add_argument("--fps", type=float, default=25.0, help="video frame rate: 25, or 30 (the [80, 24] x 6-frame network)")
     ap.add_argument("--input-rate", type=int, default=0,
                     help="also time the push through StreamEnhancer(input_rate=R): R / 5 samples per tick")
+    ap.add_argument("--input-fps", type=int, default=0,
+                    help="also time the push through StreamEnhancer(input_fps=R): R / 5 camera frames per tick (R a "
+                         "multiple of 5, e.g. 30)")
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -116,6 +120,11 @@ def main():
                     enh_r = StreamEnhancer(dw, B, input_rate=R, **rate)
                     cases.append(("stream_push_input_rate",
                                   lambda i, enh_r=enh_r, chunks_r=chunks_r: enh_r.push(chunks_r[i % 8], video, mean, std)))
+                if args.input_fps:
+                    nf = args.input_fps // 5
+                    cam = ops.to_device(rng.integers(0, 256, (B, nf, 128, 128)).astype(np.float32))
+                    enh_f = StreamEnhancer(dw, B, input_fps=args.input_fps, **rate)
+                    cases.append(("stream_push_input_fps", lambda i, enh_f=enh_f, cam=cam: enh_f.push(chunks[i % 8], cam, mean, std)))
             off = Enhancer(dw, **rate)
             cases.append(("enhancer_1_slice", lambda i, off=off: off(chunks[i % 8], video, mean, std)))
             for name, fn in cases:
@@ -128,6 +137,10 @@ def main():
                     r["input_rate"] = args.input_rate
                     r["returned_samples"] = enh_r.counts["returned"]
                     assert enh_r.counts["slices"] == n_calls - 1, r                         # every push completed its slice
+                if name == "stream_push_input_fps":
+                    r["input_fps"] = args.input_fps
+                    r["video_frames"] = enh_f.counts["video_frames"]
+                    assert enh_f.counts["slices"] == n_calls - 1, r                         # every push completed its slice
                 lines.append(json.dumps(r))
                 print(lines[-1], flush=True)
     if args.out:
