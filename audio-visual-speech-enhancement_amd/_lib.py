@@ -102,6 +102,11 @@ SIGNATURES = {
                                           _c_void_p, _c_void_p, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "avse_forward_profile_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _i64,
                                           _c_void_p, _c_void_p, ctypes.POINTER(_flt)]),
+    # the mixed forms: avse_forward_video / avse_forward_checked_video with (host present) ahead of N, packed video
+    "avse_forward_mixed": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _c_void_p, _i64,
+                                  _c_void_p, _c_void_p]),
+    "avse_forward_mixed_checked": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p,
+                                          _c_void_p, _i64, _c_void_p, _c_void_p, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "avse_video_stats_video": (_int, [_c_void_p, _c_void_p, _int, _i64, _int, _int, _int, _c_void_p, _c_void_p,
                                       _c_void_p]),
     "avse_trainer_step_video": (_int, [_c_void_p, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p, _c_void_p, _i64, _flt,
@@ -125,6 +130,11 @@ SIGNATURES = {
     "avse_stream_push_each": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                      _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "avse_stream_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
+    # push_each with (host v_present) behind v_new and (host k_present) behind host k_new; blank(s, host n_blank)
+    "avse_stream_push_each_mixed": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p, _c_void_p, _c_void_p]),
+    "avse_stream_blank": (_int, [_c_void_p, _c_void_p]),
     "avse_stream_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     # host only: supported(sr, n_fft, hop, spf, n_mels, fmin, fmax) -> 0 or the status stream_create would return
     "avse_stream_supported": (_int, [_int, _int, _int, _int, _int, _flt, _flt]),

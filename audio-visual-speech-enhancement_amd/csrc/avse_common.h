@@ -354,6 +354,9 @@ int launch_out_conv(const void* in, const float* w64, float bias, float* out, in
                     hipStream_t s);
 int launch_broadcast_row(const void* src, void* dst, int64_t rows, int64_t row_bytes, int64_t stride_bytes,
                          hipStream_t s);
+// dst row r = src row row_of[r] (device, [rows]), or `fill` where row_of[r] < 0 (conv.hip k_gather_rows)
+int launch_gather_rows(const void* src, const void* fill, const int* row_of, void* dst, int64_t rows, int64_t row_bytes,
+                       int64_t src_stride_bytes, int64_t dst_stride_bytes, hipStream_t s);
 int launch_video_normalize(float* video, int64_t S, int H, int W, int F, const float* mean,
                            const float* stdv, hipStream_t s);
 int launch_mse(const float* a, const float* b, int64_t n, float* loss, float* partial, hipStream_t s);

@@ -345,6 +345,8 @@ avse_ctx::~avse_ctx() {
     if (side) (void)hipStreamDestroy(side);
     if (fork) (void)hipEventDestroy(fork);
     if (join) (void)hipEventDestroy(join);
+    for (hipEvent_t e : map_ev)
+        if (e) (void)hipEventDestroy(e);
 }   // then the members: every table and scratch buffer
 
 // =============================================================================================

@@ -818,6 +818,22 @@ __global__ void k_broadcast_row(const char* __restrict__ src, char* __restrict__
     }
 }
 
+// dst[r * dst_stride + j] = (row_of[r] < 0 ? fill : src + row_of[r] * src_stride)[j] for r < rows, j < row_bytes: the
+// concat rows of a mixed forward, from the packed embeddings of the clips with video or the constant one (16-B units
+// when every address and size allows).  Rows are bytes: 2048 elements of 4 (float, or a split pair) or 2 (bf16) bytes.
+__global__ void k_gather_rows(const char* __restrict__ src, const char* __restrict__ fill, const int* __restrict__ row_of,
+                              char* __restrict__ dst, long long rows, long long row_bytes, long long src_stride,
+                              long long dst_stride, int vec) {
+    const long long units = row_bytes / vec, total = rows * units;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / units, j = (i - r * units) * vec;
+        const int m = row_of[r];
+        const char* from = (m < 0 ? fill : src + m * src_stride) + j;
+        if (vec == 16) *reinterpret_cast<i32x4*>(dst + r * dst_stride + j) = *reinterpret_cast<const i32x4*>(from);
+        else dst[r * dst_stride + j] = *from;
+    }
+}
+
 // range guard of a forward whose cached all-zero-video embedding was out of the pair range (capi.hip)
 __global__ void k_flag_or(unsigned* flag, unsigned bits) {
     if (threadIdx.x == 0) atomicOr(flag, bits);
@@ -834,6 +850,18 @@ int launch_broadcast_row(const void* src, void* dst, int64_t rows, int64_t row_b
     const int vec = v16 ? 16 : 1;
     hipLaunchKernelGGL(k_broadcast_row, dim3(grid_for(rows * (row_bytes / vec), 256)), dim3(256), 0, s, (const char*)src,
                        (char*)dst, (long long)rows, (long long)row_bytes, (long long)stride_bytes, vec);
+    AVSE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_gather_rows(const void* src, const void* fill, const int* row_of, void* dst, int64_t rows, int64_t row_bytes,
+                       int64_t src_stride_bytes, int64_t dst_stride_bytes, hipStream_t s) {
+    const bool v16 = ((uintptr_t)src % 16 == 0) && ((uintptr_t)fill % 16 == 0) && ((uintptr_t)dst % 16 == 0) &&
+                     row_bytes % 16 == 0 && src_stride_bytes % 16 == 0 && dst_stride_bytes % 16 == 0;
+    const int vec = v16 ? 16 : 1;
+    hipLaunchKernelGGL(k_gather_rows, dim3(grid_for(rows * (row_bytes / vec), 256)), dim3(256), 0, s, (const char*)src,
+                       (const char*)fill, row_of, (char*)dst, (long long)rows, (long long)row_bytes,
+                       (long long)src_stride_bytes, (long long)dst_stride_bytes, vec);
     AVSE_HIP_CHECK(hipGetLastError());
     return 0;
 }

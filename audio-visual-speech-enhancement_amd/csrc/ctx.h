@@ -164,6 +164,14 @@ struct avse_ctx {
     };
     std::vector<Graph> graphs;
     hipStream_t cap = nullptr;   // capture stream
+    // avse_forward_mixed's row maps go up from a pinned ring, one slot of map_cap ints per call in turn (as the
+    // streaming session's staging ring); map_ev[i] is recorded once the copy out of slot i is queued
+    static constexpr int MAP_SLOTS = 4;
+    avse::Owned<int, true> map_host;
+    size_t map_cap = 0;
+    hipEvent_t map_ev[MAP_SLOTS] = {};
+    bool map_used[MAP_SLOTS] = {};
+    int map_slot = 0;
     ~avse_ctx();
 };
 

@@ -248,11 +248,11 @@ struct Run {
         return launch_conv(a, split ? dti : cdt, s);
     }
 
-    // video encoder (network.py:138-175) over n clips, activations at the arena offsets o, embedding into cat;
+    // video encoder (network.py:138-175) over n clips, activations at the arena offsets o, clip i's embedding at
+    // element i * CAT + AEMB of cat (the concat rows, or packed rows: CAT 2048, AEMB 0), split-K partials at part_off;
     // record: its six launches are the v_conv1 .. v_conv6 stages
     int video_encoder(const void* vid, int vid_dt, const float* vm, const float* vs, int64_t n, const size_t* o,
-                      void* cat, unsigned* rflag, bool record) {
-        const long long CAT = P.cat, AEMB = P.aemb;
+                      void* cat, long long CAT, long long AEMB, size_t part_off, unsigned* rflag, bool record) {
         auto vb = [&](int b) { return (void*)(c->arena + o[b]); };
         const int v_in[6] = {B_VIN, B_V1, B_V2, B_V3, B_V4, B_V5};
         int rc;
@@ -282,7 +282,7 @@ struct Run {
                 }
                 rc = G.halo == HALO_V1 || G.halo == HALO_V1P ? launch_conv_v1r(h, s) : launch_conv_stream(h, s);
             } else if (i == 5) {
-                rc = gemm_layer(5 + i, vb(v_in[i]), in_cs, cat, CAT, G.def.cout, AEMB, n, o[B_COUNT], rflag);   // concat[aemb:]
+                rc = gemm_layer(5 + i, vb(v_in[i]), in_cs, cat, CAT, G.def.cout, AEMB, n, part_off, rflag);   // concat[aemb:]
             } else {
                 ConvArgs a = conv_args(G, vb(v_in[i]), in_cs, vb(v_in[i + 1]), (long long)G.ho * G.wo * G.def.cout, G.def.cout, 0, n);
                 const int dti = pairs(a, i > 0, true, 5 + i, rflag);   // v_conv1 generic: fp32 video-prep input
@@ -310,7 +310,8 @@ struct Run {
         arena_bytes(1, dt, opt, o1, W->shape);
         unsigned* flag = c->range + 2;
         if (split) AVSE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned), s));
-        if (int rc = video_encoder(c->zero_video, AVSE_VIDEO_F32, nullptr, nullptr, 1, o1, c->arena + o1[B_CAT], flag, false))
+        if (int rc = video_encoder(c->zero_video, AVSE_VIDEO_F32, nullptr, nullptr, 1, o1, c->arena + o1[B_CAT], P.cat, P.aemb, o1[B_COUNT],
+                                   flag, false))
             return rc;
         AVSE_HIP_CHECK(hipMemcpyAsync(emb, c->arena + o1[B_CAT] + P.aemb * es(), 2048 * es(), hipMemcpyDeviceToDevice, s));
         if (split) AVSE_HIP_CHECK(hipMemcpyAsync(c->range_host + 2, flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -322,10 +323,66 @@ struct Run {
     }
 };
 
+// A mixed forward (avse_forward_mixed): M of the N clips have video, 0 < M < N (mixed_resolve turns the other masks
+// into the plain calls), and `video` holds those M packed in clip order.
+struct Mixed {
+    const uint8_t* present;   // HOST [N]
+    int64_t M;
+};
+
+// What a mixed forward keeps behind the N-clip arena layout, whose offsets it leaves alone: room for [N][2048]
+// embeddings, of which the video encoder writes the first M, packed (sized by N so that the offsets behind it do not
+// depend on the mask), the row map [N] and the split-K partials of the encoder's M-clip launches (the
+// N-clip workspace need not hold them: a plan splits short grids only).  Nothing else addresses this tail, so it is
+// free whatever the side stream runs.  Returns the arena size.
+struct MixedTail {
+    size_t emb, map, ws;
+};
+size_t mixed_tail(int64_t N, int64_t M, int dtype, const Options& o, const ArenaShape& a, MixedTail* t) {
+    const size_t es = dtype == AVSE_BF16 ? 2 : 4;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = std::max(arena_bytes(N, dtype, o, nullptr, a), arena_bytes(1, dtype, o, nullptr, a));
+    t->emb = off;
+    off += up((size_t)N * 2048 * es);
+    t->map = off;
+    off += up((size_t)N * sizeof(int));
+    t->ws = off;
+    return off + up(split_ws_bytes(M, dtype, o, a));
+}
+
+// The row map of a mixed forward, built in the next slot of the context's pinned ring and copied to `dev` on s: row i
+// is clip i's row of the packed embeddings, -1 for a clip without video.  Waits only when MAP_SLOTS maps are in flight.
+int upload_row_map(avse_ctx* c, const Mixed& mx, int64_t N, int* dev, hipStream_t s) {
+    if ((size_t)N > c->map_cap) {   // the ring grows, never per call: every copy out of the old one has to be done
+        for (int i = 0; i < avse_ctx::MAP_SLOTS; ++i) {
+            if (c->map_used[i]) AVSE_HIP_CHECK(hipEventSynchronize(c->map_ev[i]));
+            c->map_used[i] = false;
+            if (!c->map_ev[i]) AVSE_HIP_CHECK(hipEventCreateWithFlags(&c->map_ev[i], hipEventDisableTiming));
+        }
+        const size_t cap = std::max<size_t>(1024, (size_t)N * 2);
+        c->map_cap = 0;
+        if (c->map_host.alloc(sizeof(int) * cap * avse_ctx::MAP_SLOTS) != hipSuccess)
+            return fail(AVSE_ERR_OOM, "hipHostMalloc failed (mixed forward row map)");
+        c->map_cap = cap;
+    }
+    const int i = c->map_slot;
+    if (c->map_used[i]) AVSE_HIP_CHECK(hipEventSynchronize(c->map_ev[i]));
+    int* host = c->map_host + (size_t)i * c->map_cap;
+    int m = 0;
+    for (int64_t k = 0; k < N; ++k) host[k] = mx.present[k] ? m++ : -1;
+    AVSE_HIP_CHECK(hipMemcpyAsync(dev, host, sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
+    AVSE_HIP_CHECK(hipEventRecord(c->map_ev[i], s));
+    c->map_used[i] = true;
+    c->map_slot = (i + 1) % avse_ctx::MAP_SLOTS;
+    return 0;
+}
+
 // rflag: the split dtype's range-guard word the kernels report into (avse_ctx::range)
 // vdt: avse_video_dtype of `video`
+// mx: nullable, a mixed forward (not capturable: its row map goes up from the host)
 int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt, const float* vmean,
-                 const float* vstd, int64_t N, float* out, hipStream_t s, hipEvent_t* ev, unsigned* rflag) {
+                 const float* vstd, int64_t N, float* out, hipStream_t s, hipEvent_t* ev, unsigned* rflag,
+                 const Mixed* mx = nullptr) {
     if (!c || !W || !audio || !out) return fail(AVSE_ERR_INVALID, "NULL argument");
     if (vdt != AVSE_VIDEO_F32 && vdt != AVSE_VIDEO_U8) return fail(AVSE_ERR_INVALID, "unknown video dtype");
     if (vdt == AVSE_VIDEO_U8 && ((uintptr_t)video & 3))
@@ -338,6 +395,13 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     int rc = ensure_arena(c, N, W->dtype, W->shape, s);
     if (rc) return rc;
+    MixedTail tail{};
+    if (mx) {
+        if (!video || mx->M <= 0 || mx->M >= N) return fail(AVSE_ERR_INVALID, "mixed forward: bad mask");
+        if ((rc = not_capturing(s, "a mixed forward uploads its row map from the host: not inside a capture"))) return rc;
+        const size_t need = mixed_tail(N, mx->M, W->dtype, c->opt, W->shape, &tail);
+        if ((rc = grow(c->arena, need, s, "forward scratch"))) return rc;
+    }
     c->last_shape = W->shape;
     Run r(c, W, s, ev);
     const Options& opt = r.opt;
@@ -353,7 +417,9 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
     // The all-zero-video embedding runs here, before the audio branch is launched: the per-layer audio branch runs on
     // the side stream and its N-clip buffers overlap the N = 1 layout (round 3: a race that broke video == NULL
     // forwards whenever the audio encoder was not the fused kernel, e.g. at 29.97 fps)
-    if (!video && (rc = r.zero_video_embedding())) return rc;
+    if ((!video || mx) && (rc = r.zero_video_embedding())) return rc;
+    int* row_of = reinterpret_cast<int*>(c->arena + tail.map);
+    if (mx && (rc = upload_row_map(c, *mx, N, row_of, s))) return rc;
     // audio encoder (network.py:88-109): one fused kernel per clip (conv_aud.hip) when the layers have the network's
     // shapes (AVSE_NO_AUDENC=1: per-layer launches); profiled, its time shows as the audio_prep stage
     bool aud_fused = false;
@@ -420,8 +486,18 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
         if ((rc = r.conv(a, dti, G, sa)) || (rc = r.mark())) return rc;
     }
     if (concurrent) AVSE_HIP_CHECK(hipEventRecord(c->join, sa));
-    if (video) {
-        if ((rc = r.video_encoder(video, vdt, vmean, vstd, N, off, buf(B_CAT), rflag, true))) return rc;
+    if (mx) {
+        // the encoder over the M packed clips, in the N-clip layout's activation buffers, then every concat row from
+        // its clip's packed embedding or the constant one
+        const size_t es = r.es();
+        char* emb = c->arena + tail.emb;
+        if ((rc = r.video_encoder(video, vdt, vmean, vstd, mx->M, off, emb, 2048, 0, tail.ws, rflag, true))) return rc;
+        if ((rc = launch_gather_rows(emb, W->vzero_emb.load(std::memory_order_acquire), row_of, (char*)buf(B_CAT) + AEMB * es,
+                                     N, 2048 * es, 2048 * es, CAT * es, s)))
+            return rc;
+        if (split && W->vzero_range && rflag && (rc = launch_flag_or(rflag, W->vzero_range, s))) return rc;
+    } else if (video) {
+        if ((rc = r.video_encoder(video, vdt, vmean, vstd, N, off, buf(B_CAT), CAT, AEMB, off[B_COUNT], rflag, true))) return rc;
     } else {
         // all-zero video: broadcast the constant embedding computed above
         const size_t es = r.es();
@@ -504,9 +580,10 @@ int forward_impl(avse_ctx* c, const avse_weights* W, const float* audio, const v
 // 2.14 ms (tools/graph_probe.py), but replaying the forward alone inside the same step measured 2.234 vs 2.24-2.26 ms
 // direct (bench.py A/B, same box), so direct launches stay the default.
 int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
-                     const float* vmean, const float* vstd, int64_t N, float* out, void* stream, unsigned* rflag) {
-    if (!c || !W || N <= 0 || !c->opt.graph)
-        return forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag);
+                     const float* vmean, const float* vstd, int64_t N, float* out, void* stream, unsigned* rflag,
+                     const Mixed* mx = nullptr) {
+    if (!c || !W || N <= 0 || !c->opt.graph || mx)   // a mixed forward is never replayed: its mask is host data
+        return forward_impl(c, W, audio, video, vdt, vmean, vstd, N, out, (hipStream_t)stream, nullptr, rflag, mx);
     AVSE_HIP_CHECK(hipSetDevice(c->device));
     if (W->device != c->device) return fail(AVSE_ERR_INVALID, "weights and context are on different devices");
     int rc = ensure_arena(c, N, W->dtype, W->shape, (hipStream_t)stream);   // no allocation inside the capture
@@ -552,6 +629,71 @@ int forward_dispatch(avse_ctx* c, const avse_weights* W, const float* audio, con
     return 0;
 }
 
+// The mask of a mixed call, before any GPU work: counts the clips with video and turns the masks that need no row map
+// into the plain calls (all present: `video` is the whole batch; none: video == NULL, which takes no normaliser).
+// *mixed: 0 < M < N, and mx describes it.
+int mixed_resolve(const uint8_t* present, const void*& video, const float*& vmean, const float*& vstd, int64_t N,
+                  Mixed* mx, bool* mixed) {
+    *mixed = false;
+    if (N < 0 || N > (int64_t)(1 << 30) / (128 * 128)) return fail(AVSE_ERR_INVALID, "bad N");
+    if (!present) return fail(AVSE_ERR_INVALID, "present is NULL");
+    if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be set or both NULL");
+    int64_t M = 0;
+    for (int64_t i = 0; i < N; ++i) M += present[i] != 0;
+    if (M > 0 && !video) return fail(AVSE_ERR_INVALID, "video == NULL but the mask has clips with video");
+    if (M == 0) {
+        video = nullptr;
+        vmean = vstd = nullptr;
+    }
+    mx->present = present;
+    mx->M = M;
+    *mixed = M > 0 && M < N;
+    return 0;
+}
+
+// avse_forward_checked_video, and avse_forward_mixed_checked with its mask resolved (mx, nullable)
+int forward_checked(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt, const float* vmean,
+                    const float* vstd, int64_t N, float* out, void* stream, int mode, uint32_t* host_bits, const Mixed* mx) {
+    if (host_bits) *host_bits = 0;
+    if (!c || !W) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (mode != AVSE_RANGE_RECOMPUTE && mode != AVSE_RANGE_ERROR) return fail(AVSE_ERR_INVALID, "bad range mode");
+    if (W->dtype != AVSE_F32_SPLIT || N <= 0) {
+        if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, c->range.p.get(), mx)) return rc;
+        return avse::debug_poll(stream);
+    }
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = not_capturing(s, "avse_forward_checked waits for its stream: capture avse_forward instead")) return rc;
+    unsigned* flag = c->range + 1;
+    AVSE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned), s));
+    // (option graph: the forward itself replays its hipGraph, so the launches after each wait are one graph launch)
+    if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, flag, mx)) return rc;
+    AVSE_HIP_CHECK(hipMemcpyAsync(c->range_host + 1, flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    AVSE_HIP_CHECK(hipStreamSynchronize(s));
+    const unsigned bits = c->range_host[1];
+    if (host_bits) *host_bits = bits;
+    if (!bits) return avse::debug_poll(stream);
+    if (mode == AVSE_RANGE_ERROR)
+        return fail(AVSE_ERR_RANGE, "AVSE_F32_SPLIT: an activation left the f16 pair range (range bits 0x" +
+                                        [](unsigned b) { char t[16]; std::snprintf(t, sizeof(t), "%x", b); return std::string(t); }(bits) +
+                                        "): the outputs are not float32-accurate");
+    // recompute the batch on the exact-fp32 network (the same kernels as AVSE_F32 weights), built once from the blob
+    const avse_weights* twin = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(W->twin_mu);
+        if (!W->f32_twin) {
+            avse_weights* t = nullptr;
+            if (int rc = avse_weights_load_shape(c, W->blob.data(), (int64_t)W->blob.size(), AVSE_F32, W->shape.plan.T,
+                                                 W->shape.plan.F, &t))
+                return rc;
+            W->f32_twin = t;
+        }
+        twin = W->f32_twin;
+    }
+    if (int rc = forward_impl(c, twin, audio, video, vdt, vmean, vstd, N, out, s, nullptr, nullptr, mx)) return rc;
+    return avse::debug_poll(stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -579,6 +721,27 @@ int avse_forward_video(avse_ctx* c, const avse_weights* W, const float* audio, c
     if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, c ? c->range.p.get() : nullptr))
         return rc;
     return avse::debug_poll(stream);
+}
+
+int avse_forward_mixed(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
+                       const float* vmean, const float* vstd, const uint8_t* present, int64_t N, float* out, void* stream) {
+    Mixed mx{};
+    bool mixed = false;
+    if (int rc = mixed_resolve(present, video, vmean, vstd, N, &mx, &mixed)) return rc;
+    if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, c ? c->range.p.get() : nullptr,
+                                  mixed ? &mx : nullptr))
+        return rc;
+    return avse::debug_poll(stream);
+}
+
+int avse_forward_mixed_checked(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
+                               const float* vmean, const float* vstd, const uint8_t* present, int64_t N, float* out,
+                               void* stream, int mode, uint32_t* host_bits) {
+    if (host_bits) *host_bits = 0;
+    Mixed mx{};
+    bool mixed = false;
+    if (int rc = mixed_resolve(present, video, vmean, vstd, N, &mx, &mixed)) return rc;
+    return forward_checked(c, W, audio, video, vdt, vmean, vstd, N, out, stream, mode, host_bits, mixed ? &mx : nullptr);
 }
 
 int avse_range_status(avse_ctx* c, void* stream, uint32_t* host_bits) {
@@ -610,42 +773,7 @@ int avse_forward_checked(avse_ctx* c, const avse_weights* W, const float* audio,
 int avse_forward_checked_video(avse_ctx* c, const avse_weights* W, const float* audio, const void* video, int vdt,
                                const float* vmean, const float* vstd, int64_t N, float* out, void* stream, int mode,
                                uint32_t* host_bits) {
-    if (host_bits) *host_bits = 0;
-    if (!c || !W) return fail(AVSE_ERR_INVALID, "NULL argument");
-    if (mode != AVSE_RANGE_RECOMPUTE && mode != AVSE_RANGE_ERROR) return fail(AVSE_ERR_INVALID, "bad range mode");
-    if (W->dtype != AVSE_F32_SPLIT || N <= 0)
-        return avse_forward_video(c, W, audio, video, vdt, vmean, vstd, N, out, stream);
-    AVSE_HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = not_capturing(s, "avse_forward_checked waits for its stream: capture avse_forward instead")) return rc;
-    unsigned* flag = c->range + 1;
-    AVSE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned), s));
-    // (option graph: the forward itself replays its hipGraph, so the launches after each wait are one graph launch)
-    if (int rc = forward_dispatch(c, W, audio, video, vdt, vmean, vstd, N, out, stream, flag)) return rc;
-    AVSE_HIP_CHECK(hipMemcpyAsync(c->range_host + 1, flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    AVSE_HIP_CHECK(hipStreamSynchronize(s));
-    const unsigned bits = c->range_host[1];
-    if (host_bits) *host_bits = bits;
-    if (!bits) return avse::debug_poll(stream);
-    if (mode == AVSE_RANGE_ERROR)
-        return fail(AVSE_ERR_RANGE, "AVSE_F32_SPLIT: an activation left the f16 pair range (range bits 0x" +
-                                        [](unsigned b) { char t[16]; std::snprintf(t, sizeof(t), "%x", b); return std::string(t); }(bits) +
-                                        "): the outputs are not float32-accurate");
-    // recompute the batch on the exact-fp32 network (the same kernels as AVSE_F32 weights), built once from the blob
-    const avse_weights* twin = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(W->twin_mu);
-        if (!W->f32_twin) {
-            avse_weights* t = nullptr;
-            if (int rc = avse_weights_load_shape(c, W->blob.data(), (int64_t)W->blob.size(), AVSE_F32, W->shape.plan.T,
-                                                 W->shape.plan.F, &t))
-                return rc;
-            W->f32_twin = t;
-        }
-        twin = W->f32_twin;
-    }
-    if (int rc = forward_impl(c, twin, audio, video, vdt, vmean, vstd, N, out, s, nullptr, nullptr)) return rc;
-    return avse::debug_poll(stream);
+    return forward_checked(c, W, audio, video, vdt, vmean, vstd, N, out, stream, mode, host_bits, nullptr);
 }
 
 int avse_forward_profile(avse_ctx* c, const avse_weights* W, const float* audio, const float* video,

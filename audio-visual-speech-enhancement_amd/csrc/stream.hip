@@ -488,6 +488,24 @@ __global__ __launch_bounds__(256) void k_stream_route(RouteArgs a, const StreamR
     if (tid == 0) a.run_max[b] = cur;
 }
 
+// One video slice's move in a call with slices that have no video (avse_stream_push_each_mixed): from the call's packed
+// video (src_q 0: slice src of it) or the queue (src_q 1: slot src of [B][RV]) to the compacted network input (dst_q 0:
+// clip dst of the clips with video) or the queue (dst_q 1).  The host lists only slices that have video and move.
+struct StreamMove {
+    int32_t src_q, src, dst_q, dst;
+};
+static_assert(sizeof(StreamMove) == 2 * sizeof(StreamItem), "a move takes two item slots of the route table");
+
+// ROUTE_X blocks per listed move
+__global__ __launch_bounds__(256) void k_stream_move(const char* __restrict__ vnew, char* vq, char* vstage, long long vbytes,
+                                                     int vec16, const StreamMove* __restrict__ moves) {
+    const StreamMove m = moves[blockIdx.x / ROUTE_X];
+    const int part = blockIdx.x % ROUTE_X;
+    const char* src = (m.src_q ? (const char*)vq : vnew) + (long long)m.src * vbytes;
+    char* dst = (m.dst_q ? vq : vstage) + (long long)m.dst * vbytes;
+    route_copy(src, dst, vbytes, vec16, part, threadIdx.x);
+}
+
 struct SynthArgs {
     const float2* phase_ring;
     float* frame_ring;
@@ -637,6 +655,14 @@ struct avse_stream {
     hipEvent_t staged[SLOTS] = {};
     bool staged_used[SLOTS] = {};
     int slot = 0;
+    // slices without video (avse_stream_push_each_mixed): host state.  vflag[b][k % RV] says whether queued video slice
+    // k of stream b has video; every slot outside a stream's queue [slices done, v) holds 1, so the calls that know no
+    // blank slice never write it.  blank_live counts the queued blank slices of all streams: while it is not 0 every
+    // call takes the per-stream path that reads the flags.
+    std::vector<uint8_t> vflag, clip_present;
+    std::vector<int64_t> n_blank;
+    std::vector<StreamItem> route_tmp;
+    int64_t blank_live = 0;
     ~avse_stream() {
         for (hipEvent_t e : staged)
             if (e) (void)hipEventDestroy(e);
@@ -656,6 +682,9 @@ int stream_init_state(avse_stream* s, hipStream_t st) {
     AVSE_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)s->run_max.p.get(), (int)0xff800000u, (size_t)s->B, st));   // -inf
     s->broken = false;
     stream_set_all(s, StreamState{0, 0, 0, 0});
+    std::fill(s->vflag.begin(), s->vflag.end(), (uint8_t)1);
+    std::fill(s->n_blank.begin(), s->n_blank.end(), (int64_t)0);
+    s->blank_live = 0;
     return 0;
 }
 
@@ -735,7 +764,7 @@ int stream_stage_upload(avse_stream* s, size_t bytes, hipStream_t st) {
 int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample_off, const int64_t* n_new, const void* video,
                      const int64_t* v_new, const uint8_t* flush, const float* vmean, const float* vstd, float* out,
                      int64_t out_stride, int64_t* host_n_out, int64_t* host_max_out, float* mel_db, float* pred_db,
-                     int64_t* host_k_new, void* stream) {
+                     int64_t* host_k_new, void* stream, const uint8_t* v_present = nullptr, uint8_t* host_k_present = nullptr) {
     const StreamCfg g{s->n_fft, s->hop, s->spf, s->max_slices};
     const int B = (int)s->B;
     StreamRow* rows = s->rows.data();
@@ -744,8 +773,35 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
         return fail(AVSE_ERR_INVALID, "stream " + std::to_string(p.bad) + ": " + stream_message(p.status));
     int64_t fed = 0;
     for (int b = 0; b < B; ++b) fed += rows[b].n_new - rows[b].n_old;
-    if ((fed > 0 && (!samples || !sample_off)) || (p.video_total > 0 && !video)) return fail(AVSE_ERR_INVALID, "NULL argument");
-    if (p.video_total > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
+    // v_present (nullable: all present): which of the call's video slices have video; `video` holds only those.  A
+    // call is `mixed` when it brings a blank slice or one is still queued: its video moves are listed one by one
+    int64_t present_total = p.video_total;
+    if (v_present) {
+        present_total = 0;
+        for (int64_t i = 0; i < p.video_total; ++i) present_total += v_present[i] != 0;
+    }
+    const bool mixed = present_total != p.video_total || s->blank_live > 0;
+    if (fed > 0 && (!samples || !sample_off)) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (present_total > 0 && !video) {
+        if (!v_present) return fail(AVSE_ERR_INVALID, "NULL argument");
+        int64_t i = 0;   // the first slice that has video, and its stream
+        while (!v_present[i]) ++i;
+        int b = 0;
+        while (i >= rows[b].video_off + rows[b].v_new) ++b;
+        return fail(AVSE_ERR_INVALID, "stream " + std::to_string(b) + ": video is NULL but a slice is marked present");
+    }
+    if (present_total > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
+    const int RV = s->RV;
+    // has video slice k of stream b video?  queued ones by their flag, this call's by v_present
+    auto has_video = [&](int b, int64_t k) -> bool {
+        if (k < rows[b].v_old) return s->vflag[(size_t)b * RV + (size_t)(k % RV)] != 0;
+        return !v_present || v_present[rows[b].video_off + (k - rows[b].v_old)] != 0;
+    };
+    if (host_k_present) {
+        uint8_t* kp = host_k_present;
+        for (int b = 0; b < B; ++b)
+            for (int kk = 0; kk < rows[b].k_new; ++kk) *kp++ = has_video(b, rows[b].k_old + kk);
+    }
     hipStream_t st = (hipStream_t)stream;
     if (p.any) {
         if (int rc = not_capturing(st, "a per-stream push cannot be captured into a graph")) return rc;
@@ -764,14 +820,44 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
     std::memcpy(host, rows, row_bytes);
     StreamItem* h_spec = reinterpret_cast<StreamItem*>(host + row_bytes);
     StreamItem* h_route = h_spec + p.items.spec;
-    StreamItem* h_synth = h_route + p.items.route;
+    // mixed: the route table holds the clamp items of the streams that complete slices, then the moves of the slices
+    // that have video (two item slots each: never more than the ROUTE_X items per moving slice it replaces)
+    int64_t n_clamp = 0, n_moves = 0, n_present_clips = 0;
+    int64_t route_units = p.items.route;
+    if (mixed) {
+        for (int b = 0; b < B; ++b) n_clamp += rows[b].k_new > 0;
+        StreamItem* clamp = h_route;
+        StreamMove* moves = reinterpret_cast<StreamMove*>(h_route + n_clamp);
+        int64_t packed = 0;   // slices with video of this call's `video` seen so far (stream-major, as they are packed)
+        for (int b = 0; b < B; ++b) {
+            const StreamRow& r = rows[b];
+            if (r.k_new > 0) *clamp++ = {(int32_t)b, STREAM_CLAMP};
+            for (int kk = 0; kk < r.nv; ++kk) {
+                const int64_t k = r.k_old + kk;
+                const bool from_q = k < r.v_old, to_net = kk < r.k_new;
+                if (from_q && !to_net) continue;   // stays queued
+                const bool has = has_video(b, k);
+                if (to_net) s->clip_present[(size_t)r.clip0 + kk] = has;
+                const int32_t qslot = (int32_t)((int64_t)b * RV + k % RV);
+                if (has) {
+                    moves[n_moves++] = StreamMove{from_q ? 1 : 0, from_q ? qslot : (int32_t)packed, to_net ? 0 : 1,
+                                                  to_net ? (int32_t)n_present_clips : qslot};
+                    if (!from_q) ++packed;
+                    if (to_net) ++n_present_clips;
+                }
+            }
+        }
+        route_units = n_clamp + 2 * n_moves;
+    }
+    StreamItem* h_synth = h_route + route_units;
     StreamItem* h_ola = h_synth + p.items.synth;
-    stream_fill_items(g, rows, B, h_spec, h_route, h_synth, h_ola);
-    if (int rc = stream_stage_upload(s, row_bytes + sizeof(StreamItem) * (size_t)p.items.total(), st)) return rc;
+    stream_fill_items(g, rows, B, h_spec, mixed ? s->route_tmp.data() : h_route, h_synth, h_ola);
+    const size_t n_items = (size_t)(p.items.spec + route_units + p.items.synth + p.items.ola);
+    if (int rc = stream_stage_upload(s, row_bytes + sizeof(StreamItem) * n_items, st)) return rc;
     const StreamRow* d_rows = reinterpret_cast<const StreamRow*>(s->tables.p.get());
     const StreamItem* d_spec = reinterpret_cast<const StreamItem*>(s->tables + row_bytes);
     const StreamItem* d_route = d_spec + p.items.spec;
-    const StreamItem* d_synth = d_route + p.items.route;
+    const StreamItem* d_synth = d_route + route_units;
     const StreamItem* d_ola = d_synth + p.items.synth;
     // from here on a failure leaves the device state half updated: the session is broken until reset
     auto run = [&]() -> int {
@@ -785,13 +871,28 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
             });
             AVSE_HIP_CHECK(hipGetLastError());
         }
-        if (p.items.route > 0) {
+        if (mixed) {
+            const RouteArgs ra = route_args(s, video, mel_db);
+            if (n_moves > 0) {
+                hipLaunchKernelGGL(k_stream_move, dim3((unsigned)(ROUTE_X * n_moves)), dim3(256), 0, st, ra.vnew, ra.vq, ra.vstage,
+                                   ra.vbytes, ra.vec16, reinterpret_cast<const StreamMove*>(d_route + n_clamp));
+                AVSE_HIP_CHECK(hipGetLastError());
+            }
+            if (n_clamp > 0) {   // the clamp blocks alone: the same kernel, no video item listed
+                hipLaunchKernelGGL(k_stream_route<true>, dim3((unsigned)n_clamp), dim3(256), 0, st, ra, d_rows, d_route);
+                AVSE_HIP_CHECK(hipGetLastError());
+            }
+        } else if (p.items.route > 0) {
             hipLaunchKernelGGL(k_stream_route<true>, dim3((unsigned)p.items.route), dim3(256), 0, st,
                                route_args(s, video, mel_db), d_rows, d_route);
             AVSE_HIP_CHECK(hipGetLastError());
         }
         if (p.clips > 0) {
-            if (int rc = avse_forward_video(s->ctx, s->w, s->net_in, s->vstage, s->vdt, vmean, vstd, p.clips, s->pred, stream))
+            // mixed: vstage holds the clips with video, compacted, and the forward takes the clips' mask
+            if (int rc = mixed ? avse_forward_mixed(s->ctx, s->w, s->net_in, s->vstage, s->vdt, vmean, vstd,
+                                                    s->clip_present.data(), p.clips, s->pred, stream)
+                               : avse_forward_video(s->ctx, s->w, s->net_in, s->vstage, s->vdt, vmean, vstd, p.clips, s->pred,
+                                                    stream))
                 return rc;
             if (pred_db)
                 AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)p.clips * NMEL * s->spf,
@@ -814,6 +915,26 @@ int stream_step_each(avse_stream* s, const float* samples, const int64_t* sample
     if (int rc = run()) {
         s->broken = true;
         return rc;
+    }
+    if (mixed) {
+        // the flags after the call: a slice that went through the network frees its slot (1 again), one that is queued
+        // now keeps what the call said of it
+        for (int b = 0; b < B; ++b) {
+            const StreamRow& r = rows[b];
+            for (int64_t k = r.v_old; k < r.v_old + r.v_new; ++k) {   // before the slots below change
+                const bool has = has_video(b, k);
+                s->n_blank[b] += !has;
+                if (!has && k >= r.k_old + r.k_new) {
+                    s->vflag[(size_t)b * RV + (size_t)(k % RV)] = 0;
+                    ++s->blank_live;
+                }
+            }
+            for (int64_t k = r.k_old; k < std::min<int64_t>(r.k_old + r.k_new, r.v_old); ++k) {
+                uint8_t& f = s->vflag[(size_t)b * RV + (size_t)(k % RV)];
+                s->blank_live -= !f;
+                f = 1;
+            }
+        }
     }
     stream_commit(rows, B, s->st.data());
     stream_refresh_uniform(s);
@@ -1001,9 +1122,11 @@ int avse_stream_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, in
     s->st.assign(B, StreamState{0, 0, 0, 0});
     s->rows.resize(B);
     s->arg_n.resize(B); s->arg_v.resize(B); s->arg_off.resize(B); s->arg_flush.resize(B);
+    s->vflag.assign(B * s->RV, 1); s->clip_present.assign(clips, 1); s->n_blank.assign(B, 0);
     const StreamItemCounts per_stream = stream_item_caps(StreamCfg{n_fft, hop, frames_per_slice, max_slices});
     s->cap.spec = per_stream.spec * n_streams; s->cap.route = per_stream.route * n_streams;
     s->cap.synth = per_stream.synth * n_streams; s->cap.ola = per_stream.ola * n_streams;
+    s->route_tmp.resize((size_t)s->cap.route);
     s->slot_bytes = (sizeof(StreamRow) * B + sizeof(StreamItem) * (size_t)s->cap.total() + 255) & ~(size_t)255;
     if (s->tables.alloc(s->slot_bytes) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (stream session)");
     if (s->staging.alloc(s->slot_bytes * avse_stream::SLOTS) != hipSuccess)
@@ -1043,7 +1166,7 @@ int avse_stream_push(avse_stream* s, const float* samples, int64_t n_new, int64_
     if (n_new > 0 && sample_stride < n_new) return fail(AVSE_ERR_INVALID, "sample_stride below n_new");
     if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
     if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
-    if (!s->uniform)
+    if (!s->uniform || s->blank_live > 0)   // queued blank slices: the per-stream path reads their flags
         return stream_step_spread(s, false, samples, n_new, sample_stride, video, v_new, vmean, vstd, out, out_stride,
                                   host_n_out, mel_db, pred_db, stream);
     if (s->st[0].flushed) return fail(AVSE_ERR_INVALID, "push after flush: only avse_stream_reset is legal");
@@ -1059,7 +1182,7 @@ int avse_stream_flush(avse_stream* s, const float* vmean, const float* vstd, flo
     if (out_stride < 0) return fail(AVSE_ERR_INVALID, "negative counts");
     if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
     if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
-    if (!s->uniform)
+    if (!s->uniform || s->blank_live > 0)
         return stream_step_spread(s, true, nullptr, 0, 0, nullptr, 0, vmean, vstd, out, out_stride, host_n_out, mel_db, pred_db,
                                   stream);
     if (s->st[0].flushed) return fail(AVSE_ERR_INVALID, "flush after flush: only avse_stream_reset is legal");
@@ -1076,6 +1199,24 @@ int avse_stream_push_each(avse_stream* s, const float* samples, const int64_t* s
     if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
     return stream_step_each(s, samples, sample_off, n_new, video, v_new, flush, vmean, vstd, out, out_stride, host_n_out,
                             nullptr, mel_db, pred_db, host_k_new, stream);
+}
+
+int avse_stream_push_each_mixed(avse_stream* s, const float* samples, const int64_t* sample_off, const int64_t* n_new,
+                                const void* video, const int64_t* v_new, const uint8_t* v_present, const uint8_t* flush,
+                                const float* vmean, const float* vstd, float* out, int64_t out_stride, int64_t* host_n_out,
+                                float* mel_db, float* pred_db, int64_t* host_k_new, uint8_t* host_k_present, void* stream) {
+    if (!s || !n_new || !v_new || !host_n_out) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (out_stride < 0) return fail(AVSE_ERR_INVALID, "negative counts");
+    if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
+    if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_stream_reset it");
+    return stream_step_each(s, samples, sample_off, n_new, video, v_new, flush, vmean, vstd, out, out_stride, host_n_out,
+                            nullptr, mel_db, pred_db, host_k_new, stream, v_present, host_k_present);
+}
+
+int avse_stream_blank(const avse_stream* s, int64_t* n_blank) {
+    if (!s || !n_blank) return fail(AVSE_ERR_INVALID, "NULL argument");
+    for (int64_t b = 0; b < s->B; ++b) n_blank[b] = s->n_blank[b];
+    return 0;
 }
 
 int avse_stream_reset(avse_stream* s, void* stream) {
@@ -1107,7 +1248,15 @@ int avse_stream_reset_each(avse_stream* s, const uint8_t* which, void* stream) {
     });
     AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
     for (int b = 0; b < B; ++b)
-        if (which[b]) s->st[b] = StreamState{0, 0, 0, 0};
+        if (which[b]) {
+            s->st[b] = StreamState{0, 0, 0, 0};
+            for (int i = 0; i < s->RV; ++i) {   // its queued blank flags go with it
+                uint8_t& f = s->vflag[(size_t)b * s->RV + i];
+                s->blank_live -= !f;
+                f = 1;
+            }
+            s->n_blank[b] = 0;
+        }
     stream_refresh_uniform(s);
     return debug_poll(stream);
 }

@@ -350,18 +350,36 @@ class DeviceWeights:
             self.handle = None
 
 
-def _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std):
+def present_mask(video_present, n, video_rows, what="video_present"):
+    """A video_present argument as the host uint8 array [n] libavse reads: a host bool array or sequence of length n,
+    `video_rows` (None: no video given) of them set.  Shapes only, so a bad mask is a ValueError before any device or
+    library work."""
+    if isinstance(video_present, torch.Tensor):
+        if video_present.is_cuda:
+            raise TypeError(f"{what} is host data: a numpy array, a sequence or a CPU tensor")
+        video_present = video_present.numpy()
+    m = np.asarray(video_present)
+    if m.ndim != 1 or m.shape[0] != n:
+        raise ValueError(f"{what} has shape {m.shape}, expected [{n}]")
+    m = np.ascontiguousarray(m.astype(bool), dtype=np.uint8)
+    if int(m.sum()) != (0 if video_rows is None else int(video_rows)):
+        raise ValueError(f"{what} marks {int(m.sum())} clips with video but video has "
+                         f"{'no' if video_rows is None else int(video_rows)} rows: video is packed, one row per marked clip")
+    return m
+
+
+def _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std, present=None):
     _dev_f32(audio, "audio", (80, weights.T))
     N = audio.shape[0]
     vdt = _lib.AVSE_VIDEO_F32      # video=None: either dtype
     if video is not None:
         vdt = _dev_video(video, "video", (128, 128, weights.F))
-        if video.shape[0] != N:
+        if present is None and video.shape[0] != N:
             raise ValueError("audio and video batch sizes differ")
     if (vnorm_mean is None) != (vnorm_std is None):
         raise ValueError("vnorm_mean and vnorm_std must both be given")
     if vnorm_mean is not None:
-        if video is None:
+        if video is None and present is None:   # a mixed caller always carries its normaliser
             raise ValueError("video=None (all-zero video) takes no normaliser")
         _dev_f32(vnorm_mean, "vnorm_mean", (128, 128))
         _dev_f32(vnorm_std, "vnorm_std", (128, 128))
@@ -372,7 +390,8 @@ def _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std):
     return N, vdt
 
 
-def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, checked=False, on_range="recompute"):
+def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, checked=False, on_range="recompute",
+            video_present=None):
     """K2-K5: network forward.  audio [N, 80, 20], video [N, 128, 128, 5] float32 device tensors
     (video un-normalised when vnorm_* are given; video may also be the crops' uint8 values, 4-byte aligned: the
     result is the float32 call's, bit for bit).  Returns [N, 80, 20] float32.  ([N, 80, T] / [N, 128, 128, F]
@@ -387,8 +406,20 @@ def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, ch
     left the f16 pair range, recomputes the batch on the exact-fp32 kernels (on_range="recompute") or raises
     _lib.RangeError (on_range="error"); not allowed while the stream is capturing.  weights.last_range_bits holds the
     guard bits of the last checked call (0: every pair in range).  The synchronous reference-shaped API
-    (network.SpeechEnhancementNetwork.predict / evaluate, the CLI predict) opts in for float32_split weights."""
-    N, vdt = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std)
+    (network.SpeechEnhancementNetwork.predict / evaluate, the CLI predict) opts in for float32_split weights.
+
+    video_present=mask (avse_forward_mixed): a host bool array or sequence [N], True where the clip has video.  video
+    is then PACKED: mask.sum() rows, the clips with video in order (None when there are none); vnorm_* apply to them.
+    A clip without video is the all-zero normalised input, so with float32 and float32_split weights out[i] has the
+    bits of forward(video)[i] where the mask is set and of forward(video=None)[i] where it is not.  The network was not
+    trained with missing video: the quality of its audio-only estimate is unmeasured.  Such a call is asynchronous but
+    not capturable, unless the mask is all True or all False."""
+    present = None
+    if video_present is not None:
+        if not isinstance(audio, torch.Tensor) or audio.dim() < 1:
+            raise TypeError("audio must be a ROCm device tensor")
+        present = present_mask(video_present, audio.shape[0], None if video is None else video.shape[0])
+    N, vdt = _check_forward_args(weights, audio, video, vnorm_mean, vnorm_std, present)
     if out is None:
         out = torch.empty((N, 80, weights.T), dtype=torch.float32, device=audio.device)
     _dev_f32(out, "out", (80, weights.T))
@@ -400,15 +431,27 @@ def forward(weights, audio, video, vnorm_mean=None, vnorm_std=None, out=None, ch
         if checked:
             mode = {"recompute": _lib.AVSE_RANGE_RECOMPUTE, "error": _lib.AVSE_RANGE_ERROR}[on_range]
             bits = ctypes.c_uint32()
-            rc = _lib.load().avse_forward_checked_video(
-                weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
-                _lib.ptr(vnorm_std), N, _lib.ptr(out), _lib.stream_handle(audio.device), mode, ctypes.byref(bits))
+            if present is not None:
+                rc = _lib.load().avse_forward_mixed_checked(
+                    weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+                    _lib.ptr(vnorm_std), present.ctypes.data_as(ctypes.c_void_p), N, _lib.ptr(out),
+                    _lib.stream_handle(audio.device), mode, ctypes.byref(bits))
+            else:
+                rc = _lib.load().avse_forward_checked_video(
+                    weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+                    _lib.ptr(vnorm_std), N, _lib.ptr(out), _lib.stream_handle(audio.device), mode, ctypes.byref(bits))
             weights.last_range_bits = bits.value
             _check_video(rc, "avse_forward_checked", video)
             if bits.value:
                 import warnings
                 warnings.warn(f"float32_split forward of {N} clips: {_lib.range_bit_names(bits.value)} left the f16 pair "
                               "range; the batch was recomputed on the exact-fp32 kernels", RuntimeWarning, stacklevel=2)
+        elif present is not None:
+            # the library reads `present` during the call (it builds the row map from it): nothing to keep alive
+            _check_video(_lib.load().avse_forward_mixed(
+                weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
+                _lib.ptr(vnorm_std), present.ctypes.data_as(ctypes.c_void_p), N, _lib.ptr(out),
+                _lib.stream_handle(audio.device)), "avse_forward_mixed", video)
         else:
             _check_video(_lib.load().avse_forward_video(
                 weights.ctx.handle, weights.handle, _lib.ptr(audio), _lib.ptr(video), vdt, _lib.ptr(vnorm_mean),
@@ -790,6 +833,7 @@ class StreamSession:
         self.weights, self.handle = weights, handle      # the weights (and their context) outlive the session
         self.n_streams, self.spf, self.video_dtype, self.max_slices = n_streams, spf, video_dtype, max_slices
         self.ns, self.vs, self.fl = [0] * n_streams, [0] * n_streams, [False] * n_streams
+        self._v_present, self.k_present = None, [[] for _ in range(n_streams)]
         self._cdll = _lib.load()
 
     @property
@@ -934,9 +978,24 @@ def _host_i64(values):
     return a, ctypes.c_void_p(a.ctypes.data)
 
 
+class NoVideo:
+    """k video slices without video (camera off, mouth lost, packets late) as an entry of stream_push_each's `video`:
+    they carry no bytes, count as video slices everywhere, and are predicted from the all-zero normalised video (the
+    network was not trained with missing video; the quality of its audio-only estimate is unmeasured)."""
+
+    def __init__(self, k=1):
+        if int(k) != k or int(k) < 0:
+            raise ValueError(f"NoVideo(k) needs a slice count k >= 0, got {k!r}")
+        self.k = int(k)
+
+    def __repr__(self):
+        return f"NoVideo({self.k})"
+
+
 def _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std):
     """stream_push_each's arguments, checked and packed on the device (one torch.cat each)
-    -> (packed samples, offsets [B], n_new [B], packed video, v_new [B], flush [B])."""
+    -> (packed samples, offsets [B], n_new [B], packed video, v_new [B], flush [B]); session._v_present is set to the
+    host flags [sum v_new] of the slices (None: every slice has video)."""
     w = session.weights
     dev = torch.device("cuda", w.ctx.device_index)
     B = session.n_streams
@@ -945,7 +1004,7 @@ def _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std):
     flush = [False] * B if flush is None else [bool(f) for f in flush]
     if not (len(samples) == len(video) == len(flush) == B):
         raise ValueError(f"samples, video and flush must have one entry per stream ({B})")
-    n_new, v_new, s_parts, v_parts = [], [], [], []
+    n_new, v_new, s_parts, v_parts, flags = [], [], [], [], []
     for b in range(B):
         x, vid = samples[b], video[b]
         if x is not None and x.numel():
@@ -954,13 +1013,21 @@ def _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std):
                 raise ValueError(f"samples[{b}] must be 1-D")
             s_parts.append(x)
         n_new.append(0 if x is None else int(x.numel()))
-        if vid is not None and vid.shape[0]:
-            if _dev_video(vid, f"video[{b}]", (128, 128, w.F)) != session.video_dtype:
-                raise TypeError(f"video[{b}] is {vid.dtype}, the session was created for the other video dtype")
-            if vid.dim() != 4:
-                raise ValueError(f"video[{b}] must be [v, 128, 128, {w.F}]")
-            v_parts.append(vid)
-        v_new.append(0 if vid is None else int(vid.shape[0]))
+        nv = 0
+        # a tensor, None, NoVideo(k), or a list of tensors and NoVideo in arrival order
+        for part in (vid if isinstance(vid, (list, tuple)) else [vid]):
+            if isinstance(part, NoVideo):
+                flags += [0] * part.k
+                nv += part.k
+            elif part is not None and part.shape[0]:
+                if _dev_video(part, f"video[{b}]", (128, 128, w.F)) != session.video_dtype:
+                    raise TypeError(f"video[{b}] is {part.dtype}, the session was created for the other video dtype")
+                if part.dim() != 4:
+                    raise ValueError(f"video[{b}] must be [v, 128, 128, {w.F}]")
+                v_parts.append(part)
+                flags += [1] * int(part.shape[0])
+                nv += int(part.shape[0])
+        v_new.append(nv)
     if (vnorm_mean is None) != (vnorm_std is None):
         raise ValueError("vnorm_mean and vnorm_std must both be given")
     if vnorm_mean is not None:
@@ -972,6 +1039,7 @@ def _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std):
     packed = torch.cat(s_parts) if s_parts else None
     vpacked = torch.cat(v_parts) if v_parts else None
     off = np.concatenate([[0], np.cumsum(n_new)[:-1]])
+    session._v_present = None if all(flags) else np.ascontiguousarray(flags, dtype=np.uint8)
     return packed, off, n_new, vpacked, v_new, flush
 
 
@@ -980,20 +1048,26 @@ def stream_push_each(session, samples=None, video=None, flush=None, vnorm_mean=N
     """avse_stream_push_each: every stream moves by its own amount.  samples: a list of B 1-D float32 device tensors
     (None or empty for a stream without new samples), video: a list of B [v, 128, 128, F] tensors in the session's dtype
     (None for a stream without new video), flush: a list of B bools (streams to close as stream_flush does); any of the
-    three may be None as a whole.  The inputs are packed on the device (one torch.cat each).
+    three may be None as a whole.  The inputs are packed on the device (one torch.cat each).  An entry of video may
+    also be NoVideo(k), k slices without video, or a list of tensors and NoVideo in arrival order
+    (avse_stream_push_each_mixed); session.k_present then says, per stream, which of the slices the call completed had
+    video, and stream_blank(session) counts the blank slices received.
     -> a list of B 1-D tensors, stream b's newly final samples; with return_spectrograms also two lists of [k_b, 80, spf]
     tensors, the slices the network saw and predicted for the k_b slices stream b completed in this call.  Asynchronous
     on torch's current stream; a stream without input or flush launches no blocks."""
     packed, off, n_new, vpacked, v_new, flush = _stream_pack_each(session, samples, video, flush, vnorm_mean, vnorm_std)
     out, mel, pred, ks, es = _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnorm_mean, vnorm_std,
-                                                 return_spectrograms)
+                                                 return_spectrograms, present=session._v_present)
     return _stream_split(out, mel, pred, ks, es, return_spectrograms)
 
 
-def _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnorm_mean, vnorm_std, return_spectrograms):
+def _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnorm_mean, vnorm_std, return_spectrograms,
+                        present=None):
     """The call of stream_push_each on checked, packed arguments: stream b's n_new[b] samples start at element off[b] of
     the float32 buffer `packed` (any layout: tight, or the rows of a [B, stride] buffer), its v_new[b] video slices lie
-    stream-major in `vpacked`.  -> (out [B, max n_out], mel, pred, slices per stream, samples per stream)."""
+    stream-major in `vpacked`.  -> (out [B, max n_out], mel, pred, slices per stream, samples per stream).
+    present: host uint8 [sum v_new], 0 for a slice without video (vpacked then holds only the others); None: all have.
+    session.k_present is set to the per-stream lists of which completed slices had video."""
     dev = torch.device("cuda", session.weights.ctx.device_index)
     B = session.n_streams
     ks, es = _stream_expect(session, n_new, v_new, flush)
@@ -1005,12 +1079,17 @@ def _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnor
     (_off, p_off), (_n, p_n), (_v, p_v) = _host_i64(off), _host_i64(n_new), _host_i64(v_new)
     fl = np.ascontiguousarray(flush, dtype=np.uint8)
     got, got_k = np.full(B, -1, np.int64), np.full(B, -1, np.int64)
+    kp = np.ones(max(1, sum(ks)), np.uint8)
     with torch.cuda.device(dev):
-        rc = _lib.load().avse_stream_push_each(
-            session.handle, _lib.ptr(packed), p_off, p_n, _lib.ptr(vpacked), p_v, ctypes.c_void_p(fl.ctypes.data),
+        rc = _lib.load().avse_stream_push_each_mixed(
+            session.handle, _lib.ptr(packed), p_off, p_n, _lib.ptr(vpacked), p_v,
+            ctypes.c_void_p(present.ctypes.data) if present is not None else None, ctypes.c_void_p(fl.ctypes.data),
             _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), _lib.ptr(out), int(out.shape[1]), ctypes.c_void_p(got.ctypes.data),
-            _lib.ptr(mel), _lib.ptr(pred), ctypes.c_void_p(got_k.ctypes.data), _lib.stream_handle(dev))
+            _lib.ptr(mel), _lib.ptr(pred), ctypes.c_void_p(got_k.ctypes.data), ctypes.c_void_p(kp.ctypes.data),
+            _lib.stream_handle(dev))
     _lib.check(rc, "avse_stream_push_each")
+    first = np.concatenate([[0], np.cumsum(ks)]).astype(int)
+    session.k_present = [[bool(x) for x in kp[first[b]:first[b + 1]]] for b in range(B)]
     if got.tolist() != es or got_k.tolist() != ks:
         raise _lib.AvseError(f"the session emitted {got.tolist()} samples of {got_k.tolist()} slices, the host totals "
                              f"give {es} of {ks}")
@@ -1019,6 +1098,13 @@ def _stream_push_packed(session, packed, off, n_new, vpacked, v_new, flush, vnor
         session.vs[b] += v_new[b]
         session.fl[b] = session.fl[b] or flush[b]
     return out, mel, pred, ks, es
+
+
+def stream_blank(session):
+    """avse_stream_blank: blank slices (NoVideo) received per stream since its last reset, as a list."""
+    n = np.zeros(session.n_streams, np.int64)
+    _lib.check(_lib.load().avse_stream_blank(session.handle, ctypes.c_void_p(n.ctypes.data)), "avse_stream_blank")
+    return n.tolist()
 
 
 def stream_reset_each(session, streams):

@@ -18,9 +18,21 @@ avse_spectrogram_ragged, the forward over the concatenated clips, one avse_istft
 Every utterance is independent (top_db is per utterance), so a multi-GPU run shards utterances
 (parallel.sharded_enhance) with no collective before the final gather.
 """
+import numpy as np
 import torch
 
 from . import _lib, data_processor, ops
+
+
+NoVideo = ops.NoVideo      # k video slices without video, as an entry of StreamEnhancer's `video` arguments
+
+
+def _has_blank(video):
+    """does a push_each `video` argument hold a NoVideo entry?"""
+    for v in ([] if video is None else video):
+        if isinstance(v, NoVideo) or (isinstance(v, (list, tuple)) and any(isinstance(p, NoVideo) for p in v)):
+            return True
+    return False
 
 
 class Enhancer:
@@ -37,11 +49,37 @@ class Enhancer:
     def geometry(self, n_video_slices):
         return data_processor.frame_geometry(self.sr, self.slice_ms, n_video_slices, self.fps)
 
-    def __call__(self, signals, video, vmean=None, vstd=None, timings=None):
+    @staticmethod
+    def _present(video_present, counts):
+        """video_present of __call__ ([U, S] bool) / enhance_ragged (one sequence per utterance) as one host bool
+        array over the concatenated clips; None stays None."""
+        if video_present is None:
+            return None
+        if isinstance(video_present, torch.Tensor):
+            video_present = video_present.cpu().numpy()
+        rows = [np.asarray(r, dtype=bool).reshape(-1) for r in video_present]
+        if [r.shape[0] for r in rows] != [int(c) for c in counts]:
+            raise ValueError(f"video_present has {[r.shape[0] for r in rows]} entries per utterance, the video has "
+                             f"{[int(c) for c in counts]} slices")
+        return np.concatenate(rows)
+
+    @staticmethod
+    def _chunk_video(frames, present, a, b):
+        """The video arguments of ops.forward for clips a..b: the rows with video gathered on the device (the rows
+        without are never read), or the whole chunk when every clip has video."""
+        if present is None or present[a:b].all():
+            return frames[a:b], None
+        idx = torch.from_numpy(np.flatnonzero(present[a:b])).to(frames.device)
+        return (frames[a:b].index_select(0, idx) if idx.numel() else None), present[a:b]
+
+    def __call__(self, signals, video, vmean=None, vstd=None, timings=None, video_present=None):
         """signals [U, L] float32 (int16-scale samples, padded / truncated to S slices like
         preprocess_audio_signal), video [U, S, 128, 128, frames] float32 or uint8 raw mouth crops; vmean / vstd the
         VideoNormalizer images.  Returns [U, hop * (S * spf - 1)] float32 enhanced speech.
-        `timings`, when a dict, receives the stages' HIP-event milliseconds (adds synchronisation)."""
+        `timings`, when a dict, receives the stages' HIP-event milliseconds (adds synchronisation).
+        video_present: [U, S] bool (host), False where a slice has no video (ops.forward's video_present: the slice is
+        predicted from the all-zero normalised video; the network was not trained for that, and the quality of its
+        audio-only estimate is unmeasured).  video keeps its full shape; the contents of such slices are never read."""
         if signals.dim() != 2 or video.dim() != 5 or video.shape[0] != signals.shape[0]:
             raise ValueError("signals must be [U, L] and video [U, S, H, W, frames] with the same U")
         U, S = video.shape[0], video.shape[1]
@@ -64,6 +102,7 @@ class Enhancer:
         if ev:
             ev[1].record()
         n = U * S
+        present = self._present(video_present, [S] * U)
         clips = mel.view(n, data_processor.N_MELS, spf)
         frames = video.reshape((n,) + tuple(video.shape[2:]))
         pred = torch.empty_like(clips)
@@ -75,7 +114,8 @@ class Enhancer:
             self.weights.ctx.set_aside_range()   # earlier forwards' bits stay readable by range_status()
 
         def chunk(a, b, checked):
-            ops.forward(self.weights, clips[a:b], frames[a:b], vmean, vstd, out=pred[a:b], checked=checked)
+            v, m = self._chunk_video(frames, present, a, b)
+            ops.forward(self.weights, clips[a:b], v, vmean, vstd, out=pred[a:b], checked=checked, video_present=m)
 
         for a in range(0, n, self.chunk):
             b = min(n, a + self.chunk)
@@ -101,12 +141,13 @@ class Enhancer:
                            istft_ms=ev[2].elapsed_time(ev[3]))
         return out
 
-    def enhance_ragged(self, signals, videos, vmean=None, vstd=None):
+    def enhance_ragged(self, signals, videos, vmean=None, vstd=None, video_present=None):
         """__call__ for utterances of mixed lengths: signals[u] is [L_u] float32, videos[u] [S_u, 128, 128, frames]
         (float32 or uint8, one dtype for all).  One ragged STFT, the forward over the concatenated clips of all
         utterances (in chunks of <= `chunk`, which may span utterances), one ragged ISTFT.  Each signal is padded /
         truncated to its own S_u slices first, as __call__ does for the batch.  Returns a list of [hop * (S_u * spf - 1)]
-        tensors (views of one buffer), each the bits __call__ gives for that utterance alone."""
+        tensors (views of one buffer), each the bits __call__ gives for that utterance alone.
+        video_present: one bool sequence [S_u] per utterance, as __call__'s."""
         signals, videos = list(signals), list(videos)
         if len(signals) != len(videos) or not signals:
             raise ValueError("signals and videos must be non-empty lists of one length")
@@ -132,6 +173,7 @@ class Enhancer:
         if [int(c) for c in counts] != [int(v.shape[0]) for v in videos]:
             raise ValueError("the spectrogram's slice counts differ from the videos'")
         n = clips.shape[0]
+        present = self._present(video_present, counts)
         frames = torch.cat(videos) if len(videos) > 1 else videos[0]
         pred = torch.empty_like(clips)
         split = self.weights.dtype == _lib.AVSE_F32_SPLIT
@@ -140,7 +182,8 @@ class Enhancer:
             self.weights.ctx.set_aside_range()
 
         def chunk(a, b, checked):
-            ops.forward(self.weights, clips[a:b], frames[a:b], vmean, vstd, out=pred[a:b], checked=checked)
+            v, m = self._chunk_video(frames, present, a, b)
+            ops.forward(self.weights, clips[a:b], v, vmean, vstd, out=pred[a:b], checked=checked, video_present=m)
 
         for a in range(0, n, self.chunk):
             b = min(n, a + self.chunk)
@@ -216,6 +259,7 @@ class StreamEnhancer:
                                          fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX,
                                          video_dtype=video_dtype, max_slices=max_slices)
         self._busy = set()      # slots handed out by open()
+        self._blank_seen = False   # a NoVideo entry was given: counts then has blank_slices
         self.sample_rate = int(sample_rate)
         self.input_rate = None if input_rate is None or int(input_rate) == int(sample_rate) else int(input_rate)
         self.resampler_in = self.resampler_out = None
@@ -234,7 +278,22 @@ class StreamEnhancer:
         None -> the [B, n_out] newly final samples; with return_spectrograms also the [B, k, 80, spf] slices the
         network saw and predicted for the k slices this push completed.  With input_rate the samples in and out are at
         that rate (and the results come back per stream, as lists, once the streams are out of step).  With input_fps
-        video is [B, n, 128, 128]: n frames at that rate."""
+        video is [B, n, 128, 128]: n frames at that rate.
+        video=NoVideo(k): k slices without video for every stream (camera off, mouth lost, packets late).  They count
+        as video slices and are predicted from the all-zero normalised video, so the streams go on emitting; the
+        network was not trained with missing video, and the quality of its audio-only estimate is unmeasured.
+        last_video_present then says which completed slices had video.  Not with input_fps (see push_each)."""
+        if isinstance(video, NoVideo):
+            B = self.session.n_streams
+            if samples is not None and (samples.dim() != 2 or samples.shape[0] != B):
+                raise ValueError(f"samples must be [{B}, n]")
+            res = self.push_each(None if samples is None else list(samples), [video] * B, None, vmean, vstd,
+                                 return_spectrograms)
+            parts = res if return_spectrograms else (res,)
+            if any(len({tuple(t.shape) for t in p}) > 1 for p in parts):
+                return res      # the streams are out of step: per-stream lists, as push gives then
+            stacked = tuple(torch.stack(list(p)) for p in parts)
+            return stacked if return_spectrograms else stacked[0]
         if self.input_rate is not None or self.retimer is not None:
             return self._anyrate_lockstep(samples, video, False, vmean, vstd, return_spectrograms)
         return ops.stream_push(self.session, samples, video, vmean, vstd, return_spectrograms)
@@ -288,7 +347,8 @@ class StreamEnhancer:
             raise _lib.AvseError(f"StreamEnhancer({self._label()}): stream {b}: {why} (counts at "
                                  f"{self.sample_rate} Hz; nothing was launched)")
 
-    def _anyrate_step(self, packed, off, n_new, vpacked, v_new, flush, vmean, vstd, return_spectrograms, f_off=None):
+    def _anyrate_step(self, packed, off, n_new, vpacked, v_new, flush, vmean, vstd, return_spectrograms, f_off=None,
+                      present=None):
         """One call of the chain on packed arguments -> (out [B, max count] at input_rate, counts, mel, pred, slices).
         With input_fps vpacked holds frames, v_new counts them and f_off is each stream's first frame in vpacked."""
         rin, rout, s, rt = self.resampler_in, self.resampler_out, self.session, self.retimer
@@ -306,12 +366,12 @@ class StreamEnhancer:
             vpacked = vpacked if sum(v_new) else None
         if rin is None:
             out, mel, pred, ks, es = ops._stream_push_packed(s, packed, off, n_new, vpacked, v_new, flush, vmean, vstd,
-                                                             return_spectrograms)
+                                                             return_spectrograms, present=present)
             return out, es, mel, pred, ks
         mid, n_mid = ops._resampler_push_packed(rin, packed, off, n_new, flush)
         stride = int(mid.shape[1])
         enh, mel, pred, ks, es = ops._stream_push_packed(s, mid, [b * stride for b in range(B)], n_mid, vpacked, v_new,
-                                                         flush, vmean, vstd, return_spectrograms)
+                                                         flush, vmean, vstd, return_spectrograms, present=present)
         stride = int(enh.shape[1])
         out, n_ret = ops._resampler_push_packed(rout, enh, [b * stride for b in range(B)], es, flush)
         return out, n_ret, mel, pred, ks
@@ -353,7 +413,7 @@ class StreamEnhancer:
         return out, mel.view(shape), pred.view(shape)
 
     def _anyrate_each(self, samples, video, flush, vmean, vstd, return_spectrograms):
-        f_off = None
+        f_off = present = None
         if self.retimer is not None:
             B = self.session.n_streams
             frames = [None] * B if video is None else list(video)
@@ -364,8 +424,9 @@ class StreamEnhancer:
         else:
             packed, off, n_new, vpacked, v_new, flush = ops._stream_pack_each(self.session, samples, video, flush, vmean,
                                                                               vstd)
+            present = self.session._v_present
         out, n_ret, mel, pred, ks = self._anyrate_step(packed, off, n_new, vpacked, v_new, flush, vmean, vstd,
-                                                       return_spectrograms, f_off=f_off)
+                                                       return_spectrograms, f_off=f_off, present=present)
         return ops._stream_split(out, mel, pred, ks, n_ret, return_spectrograms)
 
     # ---- independent streams: the slots of one session serve callers that never move together ----
@@ -374,7 +435,15 @@ class StreamEnhancer:
         [v, 128, 128, F]) or None per stream, flush a list of bools -> per-stream lists of what push returns.  A stream
         without input costs nothing; each stream's output is, bit for bit, that of a session of its own.  With
         input_rate the samples in and out are at that rate; with input_fps video[b] is [n_b, 128, 128], frames at that
-        rate."""
+        rate.
+        An entry of video may also be NoVideo(k), k slices without video, or a list of tensors and NoVideo in arrival
+        order (ops.stream_push_each); input_rate composes unchanged.  NoVideo together with input_fps raises ValueError:
+        a gap in a retimed stream needs a rule for the slice the gap cuts, which is not built."""
+        blank = _has_blank(video)
+        if self.retimer is not None and blank:
+            raise ValueError("NoVideo with input_fps: a gap in a retimed stream needs a rule for the slice the gap cuts "
+                             "(not built); feed such a stream at the weights' frame rate")
+        self._blank_seen = self._blank_seen or blank
         if self.input_rate is not None or self.retimer is not None:
             return self._anyrate_each(samples, video, flush, vmean, vstd, return_spectrograms)
         return ops.stream_push_each(self.session, samples, video, flush, vmean, vstd, return_spectrograms)
@@ -396,24 +465,37 @@ class StreamEnhancer:
                 return b
         raise RuntimeError(f"all {self.session.n_streams} streams of the session are in use")
 
-    def close(self, slot, vmean=None, vstd=None):
-        """A caller hangs up: flushes the slot, resets it and frees it -> its last samples (1-D)."""
-        flush = [b == slot for b in range(self.session.n_streams)]
-        last = self.push_each(flush=flush, vmean=vmean, vstd=vstd)[slot]
+    def close(self, slot, vmean=None, vstd=None, samples=None, video=None):
+        """A caller hangs up: flushes the slot, resets it and frees it -> its last samples (1-D).  samples / video: the
+        slot's last input (video as an entry of push_each: a tensor, NoVideo(k) or a list of both), fed in the same
+        call."""
+        B = self.session.n_streams
+        flush = [b == slot for b in range(B)]
+        each = lambda x: None if x is None else [x if b == slot else None for b in range(B)]
+        last = self.push_each(each(samples), each(video), flush, vmean=vmean, vstd=vstd)[slot]
         self.reset_streams([slot])
         self._busy.discard(slot)
         return last
 
     @property
+    def last_video_present(self):
+        """Per stream, which of the slices the last per-stream call completed had video (a list of bools each)."""
+        return [list(k) for k in self.session.k_present]
+
+    @property
     def counts(self):
         """Host totals: dict(samples, video_slices, frames, slices, emitted) while the streams are in step, else the
-        same keys with one list entry per stream.  With input_rate the keys above count at the session's rate, and
+        same keys with one list entry per stream.  Once the enhancer has been given a NoVideo entry, blank_slices
+        counts the slices without video received (video_slices includes them).  With input_rate the keys above count at the session's rate, and
         `received` / `returned` count the samples taken and given back at input_rate.  With input_fps `video_frames`
         counts the frames received at that rate (video_slices: the slices the retimer has handed to the session)."""
         s = self.session
         if s.in_step:
             f, k, e = ops.stream_counts(s.n, s.v, s.flushed, s)
             c = dict(samples=s.n, video_slices=s.v, frames=f, slices=k, emitted=e)
+            if self._blank_seen:
+                blank = ops.stream_blank(s)
+                c.update(blank_slices=blank[0] if len(set(blank)) == 1 else blank)
             if self.input_rate is not None:
                 c.update(received=self.resampler_in.ns[0], returned=self.resampler_out.outs[0])
             if self.retimer is not None:
@@ -423,6 +505,8 @@ class StreamEnhancer:
         rows = [ops.stream_counts(n, v, fl, s) for n, v, fl in zip(s.ns, s.vs, s.fl)]
         c = dict(samples=list(s.ns), video_slices=list(s.vs), frames=[r[0] for r in rows],
                  slices=[r[1] for r in rows], emitted=[r[2] for r in rows])
+        if self._blank_seen:
+            c.update(blank_slices=ops.stream_blank(s))
         if self.input_rate is not None:
             c.update(received=list(self.resampler_in.ns), returned=list(self.resampler_out.outs))
         if self.retimer is not None:

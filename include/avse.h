@@ -38,7 +38,8 @@ extern "C" {
  *    avse_stream_state, avse_stream_supported, avse_resample_supported, avse_resample_counts, avse_resample_ragged,
  *    avse_resampler_create, avse_resampler_push_each, avse_resampler_reset_each, avse_resampler_state,
  *    avse_resampler_destroy, avse_retime_supported, avse_retime_counts, avse_retime_ragged, avse_retimer_create,
- *    avse_retimer_push_each, avse_retimer_reset_each, avse_retimer_state, avse_retimer_destroy */
+ *    avse_retimer_push_each, avse_retimer_reset_each, avse_retimer_state, avse_retimer_destroy, avse_forward_mixed,
+ *    avse_forward_mixed_checked, avse_stream_push_each_mixed, avse_stream_blank */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -304,6 +305,32 @@ int avse_forward_checked_video(avse_ctx* ctx, const avse_weights* w, const float
                                int video_dtype, const float* vnorm_mean, const float* vnorm_std, int64_t N, float* out,
                                void* stream, int mode, uint32_t* host_bits);
 
+/* avse_forward_video for a batch in which some clips have no video (camera off, mouth lost, packets late):
+ *   present    HOST [N]           non-zero: the clip has video
+ *   video      [M][128][128][F]   PACKED: only the M = count(present) clips with video, in clip order, in video_dtype;
+ *                                 may be NULL when M == 0
+ *   vnorm_*                       apply to the clips with video; allowed (and unused) when M == 0
+ * A clip without video is the all-zero NORMALISED input, i.e. the video == NULL input of avse_forward (with a
+ * normaliser: the mean image): its embedding is the constant vector of the weights object.  The video encoder runs
+ * over the M packed clips only and one kernel fills every concat row from its clip's embedding or the constant one.
+ * With AVSE_F32 and AVSE_F32_SPLIT weights, whose forwards are batch-invariant, out[i] has the bits of the call the
+ * clip would have had alone: avse_forward_video(video) where present, avse_forward_video(NULL) where not.  The network
+ * was not trained with missing video: the quality of its audio-only estimate is unmeasured.
+ * M == N enqueues exactly avse_forward_video's launches, M == 0 exactly those of video == NULL.  Otherwise the call is
+ * asynchronous but NOT capturable (the row map goes up from pinned host memory), and option graph does not replay it.
+ * avse_ctx_reserve / avse_ctx_reserve_weights size the scratch of the plain calls only: the first mixed call of a given
+ * (N, M) may still grow it once (for the packed embeddings, the row map and the M-clip split-K partials).
+ * AVSE_ERR_INVALID before any GPU work: present == NULL, video == NULL with M > 0, and avse_forward_video's rules. */
+int avse_forward_mixed(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video, int video_dtype,
+                       const float* vnorm_mean, const float* vnorm_std, const uint8_t* present, int64_t N, float* out,
+                       void* stream);
+
+/* avse_forward_checked_video with avse_forward_mixed's `present` and packed video; the exact-fp32 recompute takes the
+ * same mask and video, and the constant embedding's range bits count whenever a clip without video is in the batch. */
+int avse_forward_mixed_checked(avse_ctx* ctx, const avse_weights* w, const float* audio, const void* video,
+                               int video_dtype, const float* vnorm_mean, const float* vnorm_std, const uint8_t* present,
+                               int64_t N, float* out, void* stream, int mode, uint32_t* host_bits);
+
 /* Range-guard bits (as avse_forward_checked's) raised by the AVSE_F32_SPLIT forwards of plain avse_forward /
  * avse_forward_profile calls on this context since the last avse_range_status; waits for `stream` (the stream those
  * forwards ran on) and clears them. */
@@ -487,6 +514,31 @@ int avse_stream_push_each(avse_stream* s,
 int avse_stream_reset_each(avse_stream* s, const uint8_t* which /* HOST [B] */, void* stream);
 /* HOST: per-stream totals (samples, video slices, flushed) of the session, [n_streams] each; any output nullable. */
 int avse_stream_state(const avse_stream* s, int64_t* n_samples, int64_t* n_video, uint8_t* flushed);
+
+/* avse_stream_push_each for streams whose video may be missing (camera off, mouth lost, packets late), so that such a
+ * stream goes on emitting:
+ *   v_present       HOST [sum v_new], stream-major, nullable (NULL: every slice has video): non-zero, the slice has video
+ *   video           only the slices that have video, packed stream-major; may be NULL when there are none
+ *   host_k_present  HOST [sum host_k_new], nullable: which of the slices this call completed had video
+ * A slice without video ("blank") carries no bytes and counts as a video slice everywhere: in v, in the slices done,
+ * in the flush rule n <= slice * v, in the max_slices queue limits and in avse_stream_counts.  It is predicted from the
+ * all-zero normalised video, the input of avse_forward(video == NULL) (avse_forward_mixed says why that is exact); the
+ * network was not trained with missing video, and the quality of its audio-only estimate is unmeasured.  Which queued
+ * slices are blank is host state of the session, cleared by avse_stream_reset and avse_stream_reset_each.  While a blank
+ * slice is queued every call of the session, the lock-step ones included, lists its video moves one by one (k_stream_move)
+ * and runs avse_forward_mixed on the compacted clips; a session that never received a blank slice enqueues what
+ * avse_stream_push_each enqueues, which is this call with v_present == NULL.  AVSE_ERR_INVALID with "stream b: ..."
+ * and the session as it was: video == NULL while a slice is marked present, and every refusal of avse_stream_push_each
+ * (a blank slice past the queue limit among them). */
+int avse_stream_push_each_mixed(avse_stream* s,
+        const float* samples, const int64_t* sample_off /* HOST [B] */, const int64_t* n_new /* HOST [B] */,
+        const void* video, const int64_t* v_new /* HOST [B] */, const uint8_t* v_present /* HOST [sum v_new], nullable */,
+        const uint8_t* flush /* HOST [B], nullable */, const float* vnorm_mean, const float* vnorm_std,
+        float* out, int64_t out_stride, int64_t* host_n_out /* HOST [B] */,
+        float* mel_db /* nullable */, float* pred_db /* nullable */, int64_t* host_k_new /* HOST [B], nullable */,
+        uint8_t* host_k_present /* HOST [sum host_k_new], nullable */, void* stream);
+/* HOST: blank slices received per stream since its last reset. */
+int avse_stream_blank(const avse_stream* s, int64_t* n_blank /* HOST [B] */);
 
 /* ---- resampling: any sample rate around a session ----
  * y = scipy.signal.resample_poly(x, up, down) with its defaults, up / down = (sr_out / g) / (sr_in / g),
