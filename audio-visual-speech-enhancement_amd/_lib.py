@@ -138,6 +138,25 @@ SIGNATURES = {
     "avse_stream_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     # host only: supported(sr, n_fft, hop, spf, n_mels, fmin, fmax) -> 0 or the status stream_create would return
     "avse_stream_supported": (_int, [_int, _int, _int, _int, _int, _flt, _flt]),
+    # sliding sessions (windows at a stride of video frames): supported(sr, n_fft, hop, spf, F, stride, n_mels, fmin,
+    # fmax); create(ctx, weights, n_streams, sr, n_fft, hop, spf, stride, n_mels, fmin, fmax, amin, top_db, video_dtype,
+    # max_windows, out); counts(s or NULL, stride, n, f, flushed, host frames, windows, predicted, emitted);
+    # counts_geom(n_fft, hop, spf, F, stride, n, f, flushed, ...); push_each(s, samples, host sample_off, host n_new,
+    # video frames, host f_new, host flush, vmean, vstd, out, out_stride, host n_out, mel_db, pred_db, host w_new,
+    # stream); reset_each(s, host which, stream); reset(s, stream); state(s, host n, host f, host flushed)
+    "avse_slide_supported": (_int, [_int, _int, _int, _int, _int, _int, _int, _flt, _flt]),
+    "avse_slide_create": (_int, [_c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _int, _int, _flt, _flt, _flt, _flt,
+                                 _int, _i64, ctypes.POINTER(_c_void_p)]),
+    "avse_slide_counts": (_int, [_c_void_p, _int, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "avse_slide_counts_geom": (_int, [_int, _int, _int, _int, _int, _i64, _i64, _int, ctypes.POINTER(_i64),
+                                      ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "avse_slide_push_each": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_slide_reset_each": (_int, [_c_void_p, _c_void_p, _c_void_p]),
+    "avse_slide_reset": (_int, [_c_void_p, _c_void_p]),
+    "avse_slide_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "avse_slide_destroy": (None, [_c_void_p]),
     # resampling: supported(sr_in, sr_out); counts(sr_in, sr_out, n_in, flushed, host n_out); ragged(ctx, sig, host
     # sig_off, host n_samples, n_utt, sr_in, sr_out, out, host out_off, stream); resampler create(ctx, n_streams, sr_in,
     # sr_out, out); push_each(r, samples, host sample_off, host n_new, host flush, out, out_stride, host n_out, stream);

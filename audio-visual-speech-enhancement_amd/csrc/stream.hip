@@ -59,6 +59,7 @@
 #include "frame800.h"
 #include "frame_poly.h"
 #include "spec_tables.h"
+#include "slide_geom.h"
 #include "stream_geom.h"
 
 #ifdef AVSE_NO_WPE   // A/B: no occupancy cap (as stft.hip)
@@ -589,6 +590,142 @@ __global__ __launch_bounds__(256) void k_stream_reset(float* tail, float* run_ma
         tail[((long long)copy * B + b) * N + (j - copy * N)] = 0.f;
     }
     if (threadIdx.x == 0) run_max[b] = -INFINITY;
+}
+
+// ---- K21: the sliding session (avse_slide_*, slide_geom.h).  Network windows start at every `stride`-th video frame;
+// the analysis and the overlap-add are k_stream_spec<BASE, P, true> and k_stream_ola<BASE, P, true> on rows that
+// slide_geom.h fills, the three kernels below take the place of k_stream_route and k_stream_synth. ----
+struct SlideRouteArgs {
+    const float* mel_ring;    // [B][RS][80][spf], slice-slotted as k_stream_spec fills it
+    const float* fmax_ring;   // [B][R]
+    float* run_max;           // [B]: maximum over every frame up to the last window's last
+    float* net_in;            // [clips][80][spf]
+    float* mel_out;           // nullable: the same values for the caller
+    int spf, qs, R, RS;
+    float top_db;
+};
+
+// The clamp block of one stream (item.b): windows [w_old, w_old + w_new) become clips clip0 .. of the network's input.
+// Window j reads frames [qs j, qs j + spf), up to two slots of the mel ring, and adds frames [qs j + spf - qs,
+// qs j + spf) (window 0: all spf) to the running maximum: the prefix maximum in window order, no atomics.
+__global__ __launch_bounds__(256) void k_slide_route(SlideRouteArgs a, const SlideRow* __restrict__ rows,
+                                                     const StreamItem* __restrict__ items) {
+    __shared__ float win_max[SLIDE_MAX_WINDOWS];
+    const int tid = threadIdx.x;
+    const int b = items[blockIdx.x].b;
+    const SlideRow& r = rows[b];
+    for (int kk = tid >> 6; kk < r.w_new; kk += 4) {
+        const long long j = r.w_old + kk;
+        const long long t_hi = (long long)a.qs * j + a.spf, t_lo = j == 0 ? 0 : t_hi - a.qs;
+        float m = -INFINITY;
+        for (long long t = t_lo + (tid & 63); t < t_hi; t += 64) m = fmaxf(m, a.fmax_ring[(long long)b * a.R + (int)(t % a.R)]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if ((tid & 63) == 0) win_max[kk] = m;
+    }
+    float cur = a.run_max[b];
+    __syncthreads();   // the windows' maxima are there, and every thread has read the old running maximum
+    const int per = NMEL * a.spf;
+    for (int kk = 0; kk < r.w_new; ++kk) {
+        cur = fmaxf(cur, win_max[kk]);
+        const float floor_db = a.top_db >= 0.f ? cur - a.top_db : -INFINITY;
+        const long long t0 = (long long)a.qs * (r.w_old + kk);
+        const long long d0 = ((long long)r.clip0 + kk) * per;
+        for (int i = tid; i < per; i += 256) {
+            const int m = i / a.spf, c = i - m * a.spf;
+            const long long t = t0 + c, sl = t / a.spf;
+            const float x = a.mel_ring[(((long long)b * a.RS + (int)(sl % a.RS)) * NMEL + m) * a.spf + (int)(t - sl * a.spf)];
+            const float v = fmaxf(x, floor_db);
+            a.net_in[d0 + i] = v;
+            if (a.mel_out) a.mel_out[d0 + i] = v;
+        }
+    }
+    if (tid == 0) a.run_max[b] = cur;
+}
+
+struct SlideGatherArgs {
+    const char* vnew;         // the call's packed video: [sum f_new] frames of [128][128]
+    char* vring;              // [B][RVf] frames, frame f of a stream in slot f % RVf
+    char* vstage;             // [clips][128][128][F]
+    int stride, RVf, vec16;   // vec16: vnew is 16-byte aligned
+};
+
+// 16 bytes of a frame: from the ring (aligned), or from the caller's buffer as four dwords when that is only 4-byte
+// aligned
+__device__ __forceinline__ uint4 load16(const char* p, bool aligned) {
+    if (aligned) return *reinterpret_cast<const uint4*>(p);
+    const unsigned* q = reinterpret_cast<const unsigned*>(p);
+    return make_uint4(q[0], q[1], q[2], q[3]);
+}
+
+// The video of a call.  A window item (chunk >= 0) is part chunk % SLIDE_GATHER_X of the transpose of window
+// w_old + chunk / SLIDE_GATHER_X: its F frames [128][128], each from the ring (received in an earlier call) or from
+// the call's buffer, into the clip's [128][128][F].  A thread takes 16 bytes of consecutive pixels from each frame
+// (coalesced rows) and writes the F 16-byte vectors that hold those pixels' F values.  An append item (chunk < 0)
+// copies frame app0 + (-1 - chunk) of the call into its ring slot; the windows of this call never read that slot (they
+// take the frame from the call's buffer), and it shares no slot with a frame they do read (slide_geom.h, RVf).
+template <class T, int F>
+__global__ __launch_bounds__(256) void k_slide_gather(SlideGatherArgs a, const SlideRow* __restrict__ rows,
+                                                      const StreamItem* __restrict__ items) {
+    constexpr int G = 16 / (int)sizeof(T);              // pixels per 16-byte vector
+    constexpr long long FB = 128 * 128 * sizeof(T);      // bytes of a frame
+    constexpr int NG = 128 * 128 / G;                    // vectors per frame
+    const StreamItem it = items[blockIdx.x];
+    const SlideRow& r = rows[it.b];
+    const int tid = threadIdx.x;
+    if (it.chunk < 0) {
+        const long long fr = r.app0 + (-1 - it.chunk);
+        const char* src = a.vnew + (r.video_off + (fr - r.f_old)) * FB;
+        char* dst = a.vring + ((long long)it.b * a.RVf + (int)(fr % a.RVf)) * FB;
+        for (int g = tid; g < NG; g += 256) reinterpret_cast<uint4*>(dst)[g] = load16(src + 16LL * g, a.vec16 != 0);
+        return;
+    }
+    const int kk = it.chunk / SLIDE_GATHER_X, part = it.chunk - SLIDE_GATHER_X * kk;
+    const char* src[F];
+    bool aligned[F];
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        const long long fr = (long long)a.stride * (r.w_old + kk) + i;
+        const bool ring = fr < r.f_old;
+        src[i] = ring ? a.vring + ((long long)it.b * a.RVf + (int)(fr % a.RVf)) * FB
+                      : a.vnew + (r.video_off + (fr - r.f_old)) * FB;
+        aligned[i] = ring || a.vec16 != 0;
+    }
+    uint4* dst = reinterpret_cast<uint4*>(a.vstage + ((long long)r.clip0 + kk) * (F * FB));
+    for (int g = part * (NG / SLIDE_GATHER_X) + tid; g < (part + 1) * (NG / SLIDE_GATHER_X); g += 256) {
+        union { uint4 v; T e[G]; } in[F];
+        union { uint4 v[F]; T e[G * F]; } o;
+#pragma unroll
+        for (int i = 0; i < F; ++i) in[i].v = load16(src[i] + 16LL * g, aligned[i]);
+#pragma unroll
+        for (int p = 0; p < G; ++p)
+#pragma unroll
+            for (int i = 0; i < F; ++i) o.e[p * F + i] = in[i].e[p];
+#pragma unroll
+        for (int i = 0; i < F; ++i) dst[(long long)g * F + i] = o.v[i];
+    }
+}
+
+// One group of FPG frames of a stream's newly predicted frames [T0, T0 + nt).  The accessor maps an emitted frame t to
+// (window, column): every column of window 0 (t < spf), then the last qs columns of each later window,
+// j = (t - spf) / qs + 1, column t - qs j; window j of the call is clip clip0 + j - w_old.
+template <int BASE, int P>
+__global__ __launch_bounds__(64) void k_slide_synth(IstftArgs a, SynthArgs s, int qs, const SlideRow* __restrict__ rows,
+                                                    const StreamItem* __restrict__ items) {
+    const StreamItem it = items[blockIdx.x];
+    const SlideRow& r = rows[it.b];
+    const int b = it.b, t0 = it.chunk * istft640::FPG;
+    const int ng = min(istft640::FPG, r.nt - t0);
+    auto mel_db = [&](int m, int f) {
+        const long long t = r.T0 + t0 + f;
+        const long long j = t < a.spf ? 0 : (t - a.spf) / qs + 1;
+        return a.mel_db[(((long long)r.clip0 + (j - r.w_old)) * a.n_mels + m) * (long long)a.spf + (int)(t - qs * j)];
+    };
+    auto stft = [&](int k, int f) { return s.phase_ring[((long long)b * s.R + (int)((r.T0 + t0 + f) % s.R)) * 321 + k]; };
+    auto frame = [&](int f) { return s.frame_ring + ((long long)b * s.R + (int)((r.T0 + t0 + f) % s.R)) * (BASE * P); };
+    if constexpr (BASE == 800) istft800::synth_frames<P>(a, ng, mel_db, stft, frame);
+    else if constexpr (P == 1) istft640::synth_frames(a, ng, mel_db, stft, frame);
+    else istft_poly::synth_frames<P>(a, ng, mel_db, stft, frame);
 }
 
 // the frame arithmetic a geometry runs on: n_fft = base * P.  0: none is built (avse_stream_supported's rule:
@@ -1275,6 +1412,306 @@ void avse_stream_destroy(avse_stream* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     delete s;
+}
+
+}  // extern "C"
+
+// ---- K21: the sliding session ----
+struct avse_slide {
+    avse_stream core;         // K17's rings, tables and staging ring, sized by slide_geom.h's bounds; its video queue,
+                              // host counters and blank flags stay empty
+    SlideCfg g{};
+    size_t fbytes = 0;        // bytes of a video frame
+    Owned<char> vring;        // [B][RVf] frames
+    std::vector<SlideState> st;
+    std::vector<SlideRow> xrows;
+    SlideItemCounts cap;      // items per table, all streams
+};
+
+namespace {
+
+int slide_init_state(avse_slide* s, hipStream_t st) {
+    if (int rc = stream_init_state(&s->core, st)) return rc;
+    std::fill(s->st.begin(), s->st.end(), SlideState{0, 0, 0, 0});
+    return 0;
+}
+
+template <class T>
+void launch_gather(int F, unsigned blocks, hipStream_t st, const SlideGatherArgs& a, const SlideRow* rows, const StreamItem* items) {
+    if (F == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slide_gather<T, 5>), dim3(blocks), dim3(256), 0, st, a, rows, items);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slide_gather<T, 6>), dim3(blocks), dim3(256), 0, st, a, rows, items);
+}
+
+int slide_counts(const SlideCfg& g, int64_t n, int64_t f, int flushed, int64_t* frames, int64_t* windows, int64_t* predicted,
+                 int64_t* emitted) {
+    if (n < 0 || f < 0) return fail(AVSE_ERR_INVALID, "negative counts");
+    if (g.n_fft < 2 || g.hop < 1 || g.F < 1 || g.spf < 1 || g.spf % g.F) return fail(AVSE_ERR_INVALID, "bad slide geometry");
+    if (g.stride < 1 || g.stride > g.F) return fail(AVSE_ERR_INVALID, "the stride must be 1 .. video_frames");
+    if (flushed && n > (int64_t)g.hop * g.q() * f) return fail(AVSE_ERR_INVALID, "a flush needs n <= hop * q * f");
+    const SlideCounts c = slide_totals(g, n, f, flushed != 0);
+    if (frames) *frames = c.frames;
+    if (windows) *windows = c.windows;
+    if (predicted) *predicted = c.predicted;
+    if (emitted) *emitted = c.emitted;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int avse_slide_supported(int sr, int n_fft, int hop, int frames_per_slice, int video_frames, int stride, int n_mels, float fmin,
+                         float fmax) {
+    if (video_frames < 1) return fail(AVSE_ERR_INVALID, "bad stream geometry");
+    if (int rc = avse_stream_supported(sr, n_fft, hop, frames_per_slice, n_mels, fmin, fmax)) return rc;
+    if (stride < 1 || stride > video_frames) return fail(AVSE_ERR_INVALID, "the stride must be 1 .. video_frames");
+    if (frames_per_slice % video_frames)
+        return fail(AVSE_ERR_UNSUPPORTED, "a sliding session needs frames_per_slice % video_frames == 0");
+    if (video_frames != 5 && video_frames != 6)
+        return fail(AVSE_ERR_UNSUPPORTED, "the sliding session's video gather is built for 5 and 6 video frames per window");
+    return 0;
+}
+
+int avse_slide_create(avse_ctx* c, const avse_weights* w, int64_t n_streams, int sr, int n_fft, int hop, int frames_per_slice,
+                      int stride, int n_mels, float fmin, float fmax, float amin, float top_db, int video_dtype,
+                      int64_t max_windows, avse_slide** out) {
+    if (!c || !w || !out) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (n_streams < 1 || max_windows < 1 || sr <= 0 || n_fft < 2 || hop <= 0 || frames_per_slice < 1 || n_mels < 1 || !(amin > 0.f))
+        return fail(AVSE_ERR_INVALID, "bad stream geometry");
+    if (video_dtype != AVSE_VIDEO_F32 && video_dtype != AVSE_VIDEO_U8) return fail(AVSE_ERR_INVALID, "unknown video dtype");
+    if (stride < 1) return fail(AVSE_ERR_INVALID, "the stride must be 1 .. video_frames");
+    // what does not depend on the weights first, so that a geometry no kernel serves is refused before they are read
+    if (int rc = avse_stream_supported(sr, n_fft, hop, frames_per_slice, n_mels, fmin, fmax)) return rc;
+    int wt = 0, wf = 0;
+    if (int rc = avse_weights_shape(w, &wt, &wf)) return rc;
+    if (int rc = avse_slide_supported(sr, n_fft, hop, frames_per_slice, wf, stride, n_mels, fmin, fmax)) return rc;
+    if (n_streams > 1024 || max_windows > SLIDE_MAX_WINDOWS)
+        return fail(AVSE_ERR_UNSUPPORTED, "at most 1024 streams and max_windows 80");
+    if (w->device != c->device) return fail(AVSE_ERR_INVALID, "weights and context are on different devices");
+    if (wt != frames_per_slice)
+        return fail(AVSE_ERR_INVALID, "the weights were loaded for slices of " + std::to_string(wt) + " frames, not " +
+                                          std::to_string(frames_per_slice));
+    AVSE_HIP_CHECK(hipSetDevice(c->device));
+    std::unique_ptr<avse_slide> sl(new avse_slide());
+    sl->g = SlideCfg{n_fft, hop, frames_per_slice, wf, stride, max_windows};
+    avse_stream* s = &sl->core;
+    s->ctx = c; s->w = w; s->B = n_streams; s->max_slices = max_windows;
+    s->sr = sr; s->n_fft = n_fft; s->hop = hop; s->spf = frames_per_slice; s->n_mels = n_mels; s->vdt = video_dtype; s->F = wf;
+    s->amin = amin; s->top_db = top_db;
+    s->db_floor = (float)(20.0 * std::log10((double)amin));
+    s->base = stream_base(sr, n_fft);
+    s->P = n_fft / s->base;
+    if (int rc = build_spec_tables(s->spec, sr, n_fft, n_mels, fmin, fmax)) return rc;
+    if (s->spec.mel.max_width != MW) return fail(AVSE_ERR_UNSUPPORTED, "the mel tables differ from the bank avse_stream_supported saw");
+    if (int rc = build_istft_tables(s->ist, sr, n_fft, n_mels, fmin, fmax)) return rc;
+    s->RS = sl->g.RS();
+    s->R = sl->g.R();
+    sl->fbytes = (size_t)128 * 128 * (video_dtype == AVSE_VIDEO_U8 ? 1 : 4);
+    s->vbytes = sl->fbytes * wf;
+    const size_t B = (size_t)n_streams, clips = B * (size_t)max_windows, per = (size_t)NMEL * s->spf;
+    if (s->tail.alloc(sizeof(float) * 2 * B * n_fft) != hipSuccess ||
+        s->mel_ring.alloc(sizeof(float) * B * s->RS * per) != hipSuccess ||
+        s->fmax_ring.alloc(sizeof(float) * B * s->R) != hipSuccess ||
+        s->run_max.alloc(sizeof(float) * B) != hipSuccess ||
+        s->net_in.alloc(sizeof(float) * clips * per) != hipSuccess ||
+        s->pred.alloc(sizeof(float) * clips * per) != hipSuccess ||
+        s->frame_ring.alloc(sizeof(float) * B * s->R * n_fft) != hipSuccess ||
+        s->phase_ring.alloc(sizeof(float2) * B * s->R * 321) != hipSuccess ||
+        sl->vring.alloc(B * sl->g.RVf() * sl->fbytes) != hipSuccess || s->vstage.alloc(clips * s->vbytes) != hipSuccess)
+        return fail(AVSE_ERR_OOM, "hipMalloc failed (slide session)");
+    sl->st.assign(B, SlideState{0, 0, 0, 0});
+    s->rows.resize(B);
+    sl->xrows.resize(B);
+    const SlideItemCounts per_stream = slide_item_caps(sl->g);
+    sl->cap.spec = per_stream.spec * n_streams; sl->cap.route = per_stream.route * n_streams;
+    sl->cap.gather = per_stream.gather * n_streams; sl->cap.synth = per_stream.synth * n_streams;
+    sl->cap.ola = per_stream.ola * n_streams;
+    s->slot_bytes = ((sizeof(StreamRow) + sizeof(SlideRow)) * B + sizeof(StreamItem) * (size_t)sl->cap.total() + 255) & ~(size_t)255;
+    if (s->tables.alloc(s->slot_bytes) != hipSuccess) return fail(AVSE_ERR_OOM, "hipMalloc failed (slide session)");
+    if (s->staging.alloc(s->slot_bytes * avse_stream::SLOTS) != hipSuccess)
+        return fail(AVSE_ERR_OOM, "hipHostMalloc failed (slide session)");
+    for (hipEvent_t& e : s->staged) AVSE_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // a slot read before its first write holds zeros, never stale memory
+    AVSE_HIP_CHECK(hipMemset(s->frame_ring, 0, s->frame_ring.bytes));
+    AVSE_HIP_CHECK(hipMemset(s->phase_ring, 0, s->phase_ring.bytes));
+    AVSE_HIP_CHECK(hipMemset(s->mel_ring, 0, s->mel_ring.bytes));
+    AVSE_HIP_CHECK(hipMemset(s->fmax_ring, 0, s->fmax_ring.bytes));
+    AVSE_HIP_CHECK(hipMemset(sl->vring, 0, sl->vring.bytes));
+    if (int rc = avse_ctx_reserve_weights(c, w, (int64_t)clips)) return rc;   // pushes never grow the forward scratch
+    if (int rc = slide_init_state(sl.get(), nullptr)) return rc;
+    AVSE_HIP_CHECK(hipStreamSynchronize(nullptr));
+    *out = sl.release();
+    return 0;
+}
+
+int avse_slide_counts_geom(int n_fft, int hop, int frames_per_slice, int video_frames, int stride, int64_t n_samples,
+                           int64_t n_video_frames, int flushed, int64_t* frames, int64_t* windows, int64_t* predicted,
+                           int64_t* emitted) {
+    return slide_counts(SlideCfg{n_fft, hop, frames_per_slice, video_frames, stride, 1}, n_samples, n_video_frames, flushed, frames,
+                        windows, predicted, emitted);
+}
+
+int avse_slide_counts(const avse_slide* s, int stride, int64_t n_samples, int64_t n_video_frames, int flushed, int64_t* frames,
+                      int64_t* windows, int64_t* predicted, int64_t* emitted) {
+    SlideCfg g = s ? s->g : SlideCfg{640, 160, 20, 5, 1, 1};
+    g.stride = stride;
+    return slide_counts(g, n_samples, n_video_frames, flushed, frames, windows, predicted, emitted);
+}
+
+int avse_slide_push_each(avse_slide* sl, const float* samples, const int64_t* sample_off, const int64_t* n_new, const void* video,
+                         const int64_t* f_new, const uint8_t* flush, const float* vmean, const float* vstd, float* out,
+                         int64_t out_stride, int64_t* host_n_out, float* mel_db, float* pred_db, int64_t* host_w_new,
+                         void* stream) {
+    if (!sl || !n_new || !f_new || !host_n_out) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (out_stride < 0) return fail(AVSE_ERR_INVALID, "negative counts");
+    if ((vmean == nullptr) != (vstd == nullptr)) return fail(AVSE_ERR_INVALID, "vnorm_mean and vnorm_std must both be given");
+    avse_stream* s = &sl->core;
+    if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_slide_reset it");
+    const SlideCfg& g = sl->g;
+    const int B = (int)s->B;
+    StreamRow* rows = s->rows.data();
+    SlideRow* xrows = sl->xrows.data();
+    const SlidePlan p = slide_rows(g, sl->st.data(), B, sample_off, n_new, f_new, flush, out != nullptr, out_stride, rows, xrows);
+    if (p.status != SLIDE_OK)
+        return fail(AVSE_ERR_INVALID, "stream " + std::to_string(p.bad) + ": " + slide_message(p.status));
+    int64_t fed = 0;
+    for (int b = 0; b < B; ++b) fed += rows[b].n_new - rows[b].n_old;
+    if ((fed > 0 && (!samples || !sample_off)) || (p.video_total > 0 && !video)) return fail(AVSE_ERR_INVALID, "NULL argument");
+    if (p.video_total > 0 && (reinterpret_cast<uintptr_t>(video) & 3)) return fail(AVSE_ERR_INVALID, "video must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (p.any) {
+        if (int rc = not_capturing(st, "a sliding push cannot be captured into a graph")) return rc;
+    }
+    for (int b = 0; b < B; ++b) {
+        host_n_out[b] = rows[b].n_out;
+        if (host_w_new) host_w_new[b] = xrows[b].w_new;
+    }
+    if (!p.any) return 0;
+    AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
+    // the tables: both rows of every stream, then the five item tables, in one copy
+    char* host = nullptr;
+    if (int rc = stream_stage_acquire(s, &host)) return rc;
+    const size_t row_bytes = sizeof(StreamRow) * (size_t)B, xrow_bytes = sizeof(SlideRow) * (size_t)B;
+    std::memcpy(host, rows, row_bytes);
+    std::memcpy(host + row_bytes, xrows, xrow_bytes);
+    StreamItem* h_spec = reinterpret_cast<StreamItem*>(host + row_bytes + xrow_bytes);
+    StreamItem* h_route = h_spec + p.items.spec;
+    StreamItem* h_gather = h_route + p.items.route;
+    StreamItem* h_synth = h_gather + p.items.gather;
+    StreamItem* h_ola = h_synth + p.items.synth;
+    slide_fill_items(rows, xrows, B, h_spec, h_route, h_gather, h_synth, h_ola);
+    if (int rc = stream_stage_upload(s, row_bytes + xrow_bytes + sizeof(StreamItem) * (size_t)p.items.total(), st)) return rc;
+    const StreamRow* d_rows = reinterpret_cast<const StreamRow*>(s->tables.p.get());
+    const SlideRow* d_xrows = reinterpret_cast<const SlideRow*>(s->tables + row_bytes);
+    const StreamItem* d_spec = reinterpret_cast<const StreamItem*>(s->tables + row_bytes + xrow_bytes);
+    const StreamItem* d_route = d_spec + p.items.spec;
+    const StreamItem* d_gather = d_route + p.items.route;
+    const StreamItem* d_synth = d_gather + p.items.gather;
+    const StreamItem* d_ola = d_synth + p.items.synth;
+    // from here on a failure leaves the device state half updated: the session is broken until reset
+    auto run = [&]() -> int {
+        if (p.items.spec > 0) {
+            SpecStreamArgs a = spec_args(s, samples, 0);  // row stride 0: + the row's sample_off
+            a.tail_in = s->tail;                          // copies 0 / 1: the kernel picks by the row's parity
+            a.tail_out = s->tail + (size_t)B * s->n_fft;
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_spec<BASE, P, true>), dim3((unsigned)p.items.spec), dim3(64 * SWAVES), 0, st,
+                                   a, d_rows, d_spec);
+            });
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.items.gather > 0) {
+            SlideGatherArgs ga;
+            ga.vnew = reinterpret_cast<const char*>(video); ga.vring = sl->vring; ga.vstage = s->vstage;
+            ga.stride = g.stride; ga.RVf = g.RVf();
+            ga.vec16 = (reinterpret_cast<uintptr_t>(video) & 15) == 0;
+            if (s->vdt == AVSE_VIDEO_U8) launch_gather<uint8_t>(g.F, (unsigned)p.items.gather, st, ga, d_xrows, d_gather);
+            else launch_gather<float>(g.F, (unsigned)p.items.gather, st, ga, d_xrows, d_gather);
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.clips > 0) {
+            SlideRouteArgs ra;
+            ra.mel_ring = s->mel_ring; ra.fmax_ring = s->fmax_ring; ra.run_max = s->run_max;
+            ra.net_in = s->net_in; ra.mel_out = mel_db;
+            ra.spf = s->spf; ra.qs = g.qs(); ra.R = s->R; ra.RS = s->RS; ra.top_db = s->top_db;
+            hipLaunchKernelGGL(k_slide_route, dim3((unsigned)p.items.route), dim3(256), 0, st, ra, d_xrows, d_route);
+            AVSE_HIP_CHECK(hipGetLastError());
+            if (int rc = avse_forward_video(s->ctx, s->w, s->net_in, s->vstage, s->vdt, vmean, vstd, p.clips, s->pred, stream))
+                return rc;
+            if (pred_db)
+                AVSE_HIP_CHECK(hipMemcpyAsync(pred_db, s->pred, sizeof(float) * (size_t)p.clips * NMEL * s->spf,
+                                              hipMemcpyDeviceToDevice, st));
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {   // T0, nt: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slide_synth<BASE, P>), dim3((unsigned)p.items.synth), dim3(64), 0, st,
+                                   istft_args(s), synth_args(s, 0, 0), g.qs(), d_xrows, d_synth);
+            });
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        if (p.items.ola > 0) {
+            with_phases(s->base, s->P, [&](auto BASE, auto P) {   // e_old, T, n_out: the rows'
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_ola<BASE, P, true>), dim3((unsigned)p.items.ola), dim3(256), 0, st,
+                                   ola_args(s, out, out_stride, 0, 0, 0), d_rows, d_ola);
+            });
+            AVSE_HIP_CHECK(hipGetLastError());
+        }
+        return 0;
+    };
+    if (int rc = run()) {
+        s->broken = true;
+        return rc;
+    }
+    slide_commit(rows, xrows, B, sl->st.data());
+    return debug_poll(stream);
+}
+
+int avse_slide_reset(avse_slide* sl, void* stream) {
+    if (!sl) return fail(AVSE_ERR_INVALID, "NULL argument");
+    AVSE_HIP_CHECK(hipSetDevice(sl->core.ctx->device));
+    return slide_init_state(sl, (hipStream_t)stream);
+}
+
+int avse_slide_reset_each(avse_slide* sl, const uint8_t* which, void* stream) {
+    if (!sl || !which) return fail(AVSE_ERR_INVALID, "NULL argument");
+    avse_stream* s = &sl->core;
+    if (s->broken) return fail(AVSE_ERR_INVALID, "the session is broken by an earlier failure: avse_slide_reset it");
+    const int B = (int)s->B;
+    int n = 0;
+    for (int b = 0; b < B; ++b) n += which[b] != 0;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = not_capturing(st, "a per-stream reset cannot be captured into a graph")) return rc;
+    AVSE_HIP_CHECK(hipSetDevice(s->ctx->device));
+    char* host = nullptr;
+    if (int rc = stream_stage_acquire(s, &host)) return rc;
+    int* ids = reinterpret_cast<int*>(host);
+    n = 0;
+    for (int b = 0; b < B; ++b)
+        if (which[b]) ids[n++] = b;
+    if (int rc = stream_stage_upload(s, sizeof(int) * (size_t)n, st)) return rc;
+    const int* ids_d = reinterpret_cast<const int*>(s->tables.p.get());
+    with_phases(s->base, s->P, [&](auto BASE, auto P) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stream_reset<BASE, P>), dim3((unsigned)n), dim3(256), 0, st, s->tail.p.get(), s->run_max.p.get(), ids_d, B);
+    });
+    AVSE_HIP_CHECK(hipGetLastError());   // nothing ran: the session is as it was
+    for (int b = 0; b < B; ++b)
+        if (which[b]) sl->st[b] = SlideState{0, 0, 0, 0};
+    return debug_poll(stream);
+}
+
+int avse_slide_state(const avse_slide* sl, int64_t* n_samples, int64_t* n_video_frames, uint8_t* flushed) {
+    if (!sl) return fail(AVSE_ERR_INVALID, "NULL argument");
+    for (int64_t b = 0; b < sl->core.B; ++b) {
+        if (n_samples) n_samples[b] = sl->st[b].n;
+        if (n_video_frames) n_video_frames[b] = sl->st[b].f;
+        if (flushed) flushed[b] = sl->st[b].flushed;
+    }
+    return 0;
+}
+
+void avse_slide_destroy(avse_slide* sl) {
+    if (!sl) return;
+    (void)hipSetDevice(sl->core.ctx->device);
+    delete sl;
 }
 
 }  // extern "C"

@@ -1156,6 +1156,199 @@ def stream_reset(session):
     session.ns, session.vs, session.fl = [0] * B, [0] * B, [False] * B
 
 
+# ---- sliding sessions: windows at a stride of video frames ----
+def slide_supported(sample_rate=16000, n_fft=640, hop_length=160, frames_per_slice=20, video_frames=5, stride=1, n_mels=80,
+                    fmin=0.0, fmax=8000.0, return_message=False):
+    """avse_slide_supported (host only, no GPU): 0 when slide_create serves this geometry, bank and stride
+    (stream_supported's rule, 1 <= stride <= video_frames, frames_per_slice % video_frames == 0), else the status it
+    would raise with.  return_message: -> (status, the library's reason; "" for status 0)."""
+    lib = _lib.load()
+    rc = int(lib.avse_slide_supported(int(sample_rate), int(n_fft), int(hop_length), int(frames_per_slice),
+                                      int(video_frames), int(stride), int(n_mels), float(fmin), float(fmax)))
+    if not return_message:
+        return rc
+    return rc, (lib.avse_last_error().decode(errors="replace") if rc else "")
+
+
+def slide_counts(n_samples, n_video_frames, flushed=False, stride=1, session=None, geometry=None):
+    """avse_slide_counts (host only, no GPU): (frames analysed, windows through the network, frames predicted, samples
+    emitted) of a stream that has received n_samples samples and n_video_frames video frames.  session: its geometry
+    and stride (`stride` is then ignored); else geometry = (n_fft, hop, frames_per_slice, video_frames), by default
+    (640, 160, 20, 5), with `stride`."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    refs = [ctypes.byref(o) for o in out]
+    lib = _lib.load()
+    if session is not None:
+        rc = lib.avse_slide_counts(session.handle, session.stride, int(n_samples), int(n_video_frames),
+                                   int(bool(flushed)), *refs)
+    elif geometry is not None:
+        n_fft, hop, spf, F = (int(x) for x in geometry)
+        rc = lib.avse_slide_counts_geom(n_fft, hop, spf, F, int(stride), int(n_samples), int(n_video_frames),
+                                        int(bool(flushed)), *refs)
+    else:
+        rc = lib.avse_slide_counts(None, int(stride), int(n_samples), int(n_video_frames), int(bool(flushed)), *refs)
+    _lib.check(rc, "avse_slide_counts")
+    return tuple(o.value for o in out)
+
+
+class SlideSession:
+    """avse_slide: the device state of n_streams sliding streams (slide_create).  ns / fs / fl are the host totals per
+    stream (samples, video frames, flushed), mirroring the library's counters."""
+
+    def __init__(self, weights, handle, n_streams, spf, stride, video_dtype, max_windows):
+        self.weights, self.handle = weights, handle      # the weights (and their context) outlive the session
+        self.n_streams, self.spf, self.stride = n_streams, spf, stride
+        self.video_dtype, self.max_windows = video_dtype, max_windows
+        self.ns, self.fs, self.fl = [0] * n_streams, [0] * n_streams, [False] * n_streams
+        self._cdll = _lib.load()
+
+    @property
+    def in_step(self):
+        return len(set(zip(self.ns, self.fs, self.fl))) == 1
+
+    def __del__(self):
+        h, lib = getattr(self, "handle", None), getattr(self, "_cdll", None)
+        if h is not None and h.value and lib is not None:
+            lib.avse_slide_destroy(h)
+            self.handle = None
+
+
+def slide_create(weights, n_streams, stride=1, sample_rate=16000, n_fft=640, hop_length=160, frames_per_slice=20, n_mels=80,
+                 fmin=0.0, fmax=8000.0, amin=1e-5, top_db=80.0, video_dtype=torch.float32, max_windows=8):
+    """avse_slide_create on the weights' context -> SlideSession: a streaming session whose network windows start at
+    every `stride`-th video frame (1 .. the weights' video frames per slice).  max_windows (1 .. 80): the most windows
+    one call may complete per stream, and how many windows either input may run ahead of the other."""
+    if not isinstance(weights, DeviceWeights):
+        raise TypeError("weights must be DeviceWeights")
+    if int(n_streams) < 1 or int(max_windows) < 1:
+        raise ValueError("n_streams and max_windows must be positive")
+    if video_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"video_dtype must be torch.float32 or torch.uint8, got {video_dtype}")
+    vdt = _lib.AVSE_VIDEO_U8 if video_dtype == torch.uint8 else _lib.AVSE_VIDEO_F32
+    h = ctypes.c_void_p()
+    with torch.cuda.device(weights.ctx.device_index):
+        _lib.check(_lib.load().avse_slide_create(
+            weights.ctx.handle, weights.handle, int(n_streams), int(sample_rate), int(n_fft), int(hop_length),
+            int(frames_per_slice), int(stride), int(n_mels), float(fmin), float(fmax), float(amin),
+            float(-1.0 if top_db is None else top_db), vdt, int(max_windows), ctypes.byref(h)), "avse_slide_create")
+    return SlideSession(weights, h, int(n_streams), int(frames_per_slice), int(stride), vdt, int(max_windows))
+
+
+def _slide_expect(sess, n_new, f_new, flush):
+    """Per stream, what a call with these per-stream counts completes and emits: (windows [B], samples [B]), from the
+    host totals.  Input for a flushed stream emits nothing and is left to the library to refuse."""
+    ws, es = [], []
+    for b in range(sess.n_streams):
+        _, w0, _, e0 = slide_counts(sess.ns[b], sess.fs[b], sess.fl[b], session=sess)
+        w1, e1 = w0, e0
+        if not sess.fl[b]:
+            _, w1, _, e1 = slide_counts(sess.ns[b] + n_new[b], sess.fs[b] + f_new[b], flush[b], session=sess)
+        ws.append(w1 - w0)
+        es.append(e1 - e0)
+    return ws, es
+
+
+def slide_push_each(session, samples=None, video=None, flush=None, vnorm_mean=None, vnorm_std=None,
+                    return_spectrograms=False):
+    """avse_slide_push_each: every stream moves by its own amount.  samples: a list of B 1-D float32 device tensors
+    (None or empty for a stream without new samples), video: a list of B [k, 128, 128] tensors of video FRAMES in the
+    session's dtype (None for a stream without new video), flush: a list of B bools; any of the three may be None as a
+    whole.  -> a list of B 1-D tensors, stream b's newly final samples; with return_spectrograms also two lists of
+    [w_b, 80, spf] tensors, the whole windows the network saw and predicted for the w_b windows stream b completed in
+    this call.  Asynchronous on torch's current stream."""
+    w = session.weights
+    dev = torch.device("cuda", w.ctx.device_index)
+    B = session.n_streams
+    samples = [None] * B if samples is None else list(samples)
+    video = [None] * B if video is None else list(video)
+    flush = [False] * B if flush is None else [bool(f) for f in flush]
+    if not (len(samples) == len(video) == len(flush) == B):
+        raise ValueError(f"samples, video and flush must have one entry per stream ({B})")
+    n_new, f_new, s_parts, v_parts = [], [], [], []
+    for b in range(B):
+        x, vid = samples[b], video[b]
+        if isinstance(vid, NoVideo):
+            raise ValueError("NoVideo in a sliding session: a window that is partly blank needs a rule (not built)")
+        if x is not None and x.numel():
+            _dev_f32(x, f"samples[{b}]")
+            if x.dim() != 1:
+                raise ValueError(f"samples[{b}] must be 1-D")
+            s_parts.append(x)
+        n_new.append(0 if x is None else int(x.numel()))
+        if vid is not None and vid.shape[0]:
+            if _dev_video(vid, f"video[{b}]", (128, 128)) != session.video_dtype:
+                raise TypeError(f"video[{b}] is {vid.dtype}, the session was created for the other video dtype")
+            if vid.dim() != 3:
+                raise ValueError(f"video[{b}] must be [k, 128, 128] (video frames)")
+            v_parts.append(vid)
+        f_new.append(0 if vid is None else int(vid.shape[0]))
+    if (vnorm_mean is None) != (vnorm_std is None):
+        raise ValueError("vnorm_mean and vnorm_std must both be given")
+    if vnorm_mean is not None:
+        _dev_f32(vnorm_mean, "vnorm_mean", (128, 128))
+        _dev_f32(vnorm_std, "vnorm_std", (128, 128))
+    for t in s_parts + v_parts + [vnorm_mean, vnorm_std]:
+        if t is not None and t.device.index != dev.index:
+            raise ValueError(f"the session lives on {dev} but an argument is on {t.device}")
+    packed = (s_parts[0] if len(s_parts) == 1 else torch.cat(s_parts)) if s_parts else None
+    vpacked = (v_parts[0] if len(v_parts) == 1 else torch.cat(v_parts)) if v_parts else None
+    off = np.concatenate([[0], np.cumsum(n_new)[:-1]])
+    ws, es = _slide_expect(session, n_new, f_new, flush)
+    out = torch.empty((B, max(es)), dtype=torch.float32, device=dev)
+    mel = pred = None
+    if return_spectrograms:
+        mel = torch.empty((sum(ws), 80, session.spf), dtype=torch.float32, device=dev)
+        pred = torch.empty_like(mel)
+    (_off, p_off), (_n, p_n), (_f, p_f) = _host_i64(off), _host_i64(n_new), _host_i64(f_new)
+    fl = np.ascontiguousarray(flush, dtype=np.uint8)
+    got, got_w = np.full(B, -1, np.int64), np.full(B, -1, np.int64)
+    with torch.cuda.device(dev):
+        rc = _lib.load().avse_slide_push_each(
+            session.handle, _lib.ptr(packed), p_off, p_n, _lib.ptr(vpacked), p_f, ctypes.c_void_p(fl.ctypes.data),
+            _lib.ptr(vnorm_mean), _lib.ptr(vnorm_std), _lib.ptr(out), int(out.shape[1]), ctypes.c_void_p(got.ctypes.data),
+            _lib.ptr(mel), _lib.ptr(pred), ctypes.c_void_p(got_w.ctypes.data), _lib.stream_handle(dev))
+    _lib.check(rc, "avse_slide_push_each")
+    if got.tolist() != es or got_w.tolist() != ws:
+        raise _lib.AvseError(f"the session emitted {got.tolist()} samples of {got_w.tolist()} windows, the host totals "
+                             f"give {es} of {ws}")
+    for b in range(B):
+        session.ns[b] += n_new[b]
+        session.fs[b] += f_new[b]
+        session.fl[b] = session.fl[b] or flush[b]
+    return _stream_split(out, mel, pred, ws, es, return_spectrograms)
+
+
+def slide_reset_each(session, streams=None):
+    """avse_slide_reset_each: the listed streams (None: all, avse_slide_reset, which also mends a broken session) go
+    back to the state after slide_create, ordered on torch's current stream; the others are untouched."""
+    dev = torch.device("cuda", session.weights.ctx.device_index)
+    if streams is None:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_slide_reset(session.handle, _lib.stream_handle(dev)), "avse_slide_reset")
+        streams = range(session.n_streams)
+    else:
+        which = np.zeros(session.n_streams, np.uint8)
+        for b in streams:
+            if not 0 <= int(b) < session.n_streams:
+                raise ValueError(f"no stream {b} in a session of {session.n_streams}")
+            which[int(b)] = 1
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_slide_reset_each(session.handle, ctypes.c_void_p(which.ctypes.data),
+                                                         _lib.stream_handle(dev)), "avse_slide_reset_each")
+        streams = np.flatnonzero(which)
+    for b in streams:
+        session.ns[b], session.fs[b], session.fl[b] = 0, 0, False
+
+
+def slide_state(session):
+    """avse_slide_state: the library's per-stream totals -> (samples [B], video frames [B], flushed [B]) as lists."""
+    B = session.n_streams
+    n, f, fl = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.uint8)
+    _lib.check(_lib.load().avse_slide_state(session.handle, ctypes.c_void_p(n.ctypes.data), ctypes.c_void_p(f.ctypes.data),
+                                            ctypes.c_void_p(fl.ctypes.data)), "avse_slide_state")
+    return n.tolist(), f.tolist(), [bool(x) for x in fl]
+
+
 def resample_supported(sr_in, sr_out, return_message=False):
     """avse_resample_supported (host only, no GPU): 0 when sr_in -> sr_out is served (max(up, down) <= 640 after
     reduction), else the status resample / resampler_create would raise with (3: unsupported, 1: invalid).

@@ -520,3 +520,134 @@ class StreamEnhancer:
         if self.weights.dtype != _lib.AVSE_F32_SPLIT:
             return 0
         return self.weights.ctx.range_status()
+
+
+class SlidingStreamEnhancer:
+    """Low-latency streaming: a StreamEnhancer whose network windows start at every `stride`-th video
+    frame instead of every slice.  Video arrives as frames ([128, 128] mouth crops), not as slices.  The network runs on
+    the most recent 200-ms window each time `stride` new video frames and their samples are there; window 0 contributes
+    all its predicted columns, every later window its newest q * stride (q = spectrogram frames per video frame).
+    Beyond the first window a sample therefore waits for q * stride * hop + n_fft / 2 + hop samples (70 ms at 16 kHz,
+    25 fps, stride 1) instead of a whole slice plus the tail (230 ms), for F / stride times the forwards.  Keeping the
+    newest columns is the choice latency asks for; whether centre columns would sound better has not been measured.
+
+    Each window's input is clamped at the causal floor of StreamEnhancer evaluated at the window's last frame, so the
+    output does not depend on how the input was cut.  stride = F is, bit for bit, a StreamEnhancer fed the same frames
+    stacked into slices.  max_windows: the most windows one call may complete per stream, and how many windows either
+    input may run ahead of the other.  Geometries as StreamEnhancer (ops.slide_supported is the rule).
+
+    input_rate, input_fps and NoVideo are not built around a sliding session (ValueError): the resampler composes
+    unchanged and the retimer with one frame per slice, but a blank frame needs a rule for windows that are partly
+    blank."""
+
+    def __init__(self, weights, n_streams, stride=1, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200,
+                 max_windows=8, video_dtype=torch.float32, input_rate=None, input_fps=None):
+        if input_rate is not None or input_fps is not None:
+            raise ValueError("SlidingStreamEnhancer: input_rate / input_fps are not built around a sliding session; "
+                             "resample or retime before it")
+        self.weights = weights
+        g = data_processor.frame_geometry(int(sample_rate), slice_duration_ms, 1, float(video_frame_rate))
+        self.geometry = g
+        spf = g["spectrogram_samples_per_slice"]
+        if spf != weights.T:
+            raise ValueError(f"{video_frame_rate} fps gives [80, {spf}] slices; the weights are for [80, {weights.T}]")
+        self.stride = int(stride)
+        self.sample_rate = int(sample_rate)
+        self.session = ops.slide_create(weights, n_streams, stride=self.stride, sample_rate=int(sample_rate),
+                                        n_fft=g["n_fft"], hop_length=g["hop_length"], frames_per_slice=spf,
+                                        n_mels=data_processor.N_MELS, fmin=data_processor.MEL_FMIN,
+                                        fmax=data_processor.MEL_FMAX, video_dtype=video_dtype, max_windows=max_windows)
+        self._busy = set()      # slots handed out by open()
+
+    @property
+    def latency_samples(self):
+        """Samples a sample waits beyond the first window: q * stride * hop + n_fft / 2 + hop."""
+        g = self.geometry
+        q = g["spectrogram_samples_per_slice"] // self.weights.F
+        return q * self.stride * g["hop_length"] + g["n_fft"] // 2 + g["hop_length"]
+
+    def _lockstep(self, samples, video, flush, vmean, vstd, return_spectrograms):
+        s = self.session
+        B = s.n_streams
+        if isinstance(video, NoVideo):
+            raise ValueError("SlidingStreamEnhancer: NoVideo needs a rule for windows that are partly blank (not built)")
+        if samples is not None and (samples.dim() != 2 or samples.shape[0] != B):
+            raise ValueError(f"samples must be [{B}, n]")
+        if video is not None and (video.dim() != 4 or video.shape[0] != B):
+            raise ValueError(f"video must be [{B}, k, 128, 128] (video frames)")
+        todo = [flush and not f for f in s.fl]
+        if flush and not any(todo):
+            raise _lib.AvseError("flush after flush: only reset is legal")
+        res = ops.slide_push_each(s, None if samples is None else list(samples), None if video is None else list(video),
+                                  todo, vmean, vstd, return_spectrograms)
+        parts = res if return_spectrograms else (res,)
+        if any(len({tuple(t.shape) for t in p}) > 1 for p in parts):
+            return res      # the streams are out of step: per-stream lists
+        stacked = tuple(torch.stack(list(p)) for p in parts)
+        return stacked if return_spectrograms else stacked[0]
+
+    def push(self, samples, video=None, vmean=None, vstd=None, return_spectrograms=False):
+        """samples [B, n] float32 (int16-scale) or None, video [B, k, 128, 128] float32 or uint8 (the session's dtype):
+        k video frames, or None -> the [B, n_out] newly final samples; with return_spectrograms also the [B, w, 80, spf]
+        whole windows the network saw and predicted for the w windows this push completed.  Per-stream lists once the
+        streams are out of step, as StreamEnhancer.push."""
+        return self._lockstep(samples, video, False, vmean, vstd, return_spectrograms)
+
+    def flush(self, vmean=None, vstd=None, return_spectrograms=False):
+        """Close the streams as the signal zero-padded to hop * q * (video frames received); returns the rest.  Video
+        frames past the last full stride are dropped."""
+        return self._lockstep(None, None, True, vmean, vstd, return_spectrograms)
+
+    def push_each(self, samples=None, video=None, flush=None, vmean=None, vstd=None, return_spectrograms=False):
+        """Every stream by its own amount (ops.slide_push_each): samples / video are lists with one tensor (1-D float32;
+        [k, 128, 128] video frames) or None per stream, flush a list of bools -> per-stream lists of what push returns.
+        Each stream's output is, bit for bit, that of a session of its own."""
+        if _has_blank(video):
+            raise ValueError("SlidingStreamEnhancer: NoVideo needs a rule for windows that are partly blank (not built)")
+        return ops.slide_push_each(self.session, samples, video, flush, vmean, vstd, return_spectrograms)
+
+    def reset(self):
+        ops.slide_reset_each(self.session)
+        self._busy = set()
+
+    def reset_streams(self, ids):
+        """The listed streams back to the state after construction; the others keep streaming."""
+        ops.slide_reset_each(self.session, ids)
+
+    def open(self):
+        """-> a free slot (the lowest stream no caller holds) for a caller that joins; close() gives it back."""
+        for b in range(self.session.n_streams):
+            if b not in self._busy:
+                self._busy.add(b)
+                return b
+        raise RuntimeError(f"all {self.session.n_streams} streams of the session are in use")
+
+    def close(self, slot, vmean=None, vstd=None, samples=None, video=None, return_spectrograms=False):
+        """A caller hangs up: flushes the slot, resets it and frees it -> its last samples (1-D); with
+        return_spectrograms also the [w, 80, spf] windows the flush completed, as seen and as predicted.  samples /
+        video: the slot's last input, fed in the same call."""
+        B = self.session.n_streams
+        flush = [b == slot for b in range(B)]
+        each = lambda x: None if x is None else [x if b == slot else None for b in range(B)]
+        res = self.push_each(each(samples), each(video), flush, vmean, vstd, return_spectrograms)
+        self.reset_streams([slot])
+        self._busy.discard(slot)
+        return tuple(r[slot] for r in res) if return_spectrograms else res[slot]
+
+    @property
+    def counts(self):
+        """Host totals: dict(samples, video_frames, frames, windows, predicted, emitted) while the streams are in step,
+        else the same keys with one list entry per stream."""
+        s = self.session
+        rows = [ops.slide_counts(n, f, fl, session=s) for n, f, fl in zip(s.ns, s.fs, s.fl)]
+        c = dict(samples=list(s.ns), video_frames=list(s.fs), frames=[r[0] for r in rows], windows=[r[1] for r in rows],
+                 predicted=[r[2] for r in rows], emitted=[r[3] for r in rows])
+        return {k: v[0] for k, v in c.items()} if s.in_step else c
+
+    @property
+    def range_bits(self):
+        """float32_split: the range-guard bits the pushes' forwards raised since the last read (waits for the stream;
+        Context.range_status); 0 for the other dtypes."""
+        if self.weights.dtype != _lib.AVSE_F32_SPLIT:
+            return 0
+        return self.weights.ctx.range_status()

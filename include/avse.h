@@ -39,7 +39,9 @@ extern "C" {
  *    avse_resampler_create, avse_resampler_push_each, avse_resampler_reset_each, avse_resampler_state,
  *    avse_resampler_destroy, avse_retime_supported, avse_retime_counts, avse_retime_ragged, avse_retimer_create,
  *    avse_retimer_push_each, avse_retimer_reset_each, avse_retimer_state, avse_retimer_destroy, avse_forward_mixed,
- *    avse_forward_mixed_checked, avse_stream_push_each_mixed, avse_stream_blank */
+ *    avse_forward_mixed_checked, avse_stream_push_each_mixed, avse_stream_blank, avse_slide_supported,
+ *    avse_slide_create, avse_slide_counts, avse_slide_counts_geom, avse_slide_push_each, avse_slide_reset_each,
+ *    avse_slide_reset, avse_slide_state, avse_slide_destroy */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -539,6 +541,76 @@ int avse_stream_push_each_mixed(avse_stream* s,
         uint8_t* host_k_present /* HOST [sum host_k_new], nullable */, void* stream);
 /* HOST: blank slices received per stream since its last reset. */
 int avse_stream_blank(const avse_stream* s, int64_t* n_blank /* HOST [B] */);
+
+/* ---- low-latency streaming: sliding windows at a stride of `stride` video frames ----
+ * A sliding session is a streaming session whose network windows start at every `stride`-th video frame, not at every
+ * slice, so that beyond the first window a sample waits for one stride of video plus the synthesis tail
+ * (q s H + N/2 + H samples: 70 ms at 16 kHz, 25 fps, stride 1) instead of a whole slice (230 ms).  It costs F / stride
+ * times the forwards.  N = n_fft, H = hop, spf = frames_per_slice, F = the weights' video frames per slice,
+ * q = spf / F, s = stride.  A stream that has received n samples and f video FRAMES (each one [128][128] crop; video does
+ * not arrive as slices here) has
+ *   frames    as avse_stream_push: frame t, same window and left reflection, arrives once n >= H t + N/2
+ *   windows   = min(wa, wv), wa = frames >= spf ? (frames - spf) / (q s) + 1 : 0, wv = f >= F ? (f - F) / s + 1 : 0;
+ *               window j is video frames [s j, s j + F) and spectrogram frames [q s j, q s j + spf)
+ *   input     of window j: the unclamped mel-dB of its spf frames, clamped from below at (the maximum of the unclamped
+ *               mel-dB of the stream's frames 0 .. q s j + spf - 1) - top_db (top_db < 0: no clamp): the causal floor
+ *               of avse_stream_push at the window's last frame, independent of how the input was cut; its F video
+ *               frames as [128][128][F], frame innermost, the normaliser fused as in avse_forward_video
+ *   kept      window 0 contributes all spf predicted columns, window j > 0 its last q s (frames [q s j + spf - q s,
+ *               q s j + spf)); predicted = windows > 0 ? spf + q s (windows - 1) : 0.  Keeping the newest columns is
+ *               the choice latency asks for; whether centre columns would sound better has not been measured
+ *   emitted   = max(0, H predicted - N/2): the mixture phase of the same frame, frames added in increasing order, each
+ *               sample divided by the window sum-square of the frames covering it, as avse_stream_push
+ *   flush     closes the stream as the signal zero-padded (or of length) H q f, right reflection there, frames = q f:
+ *               it needs n <= H q f; the remaining windows run, emitted = predicted > 0 ? H (predicted - 1) : 0; video
+ *               frames past the last full stride are dropped
+ * With s = F all of this is avse_stream_push_each fed the same frames stacked into slices (v = f / F), bit for bit.
+ * Host-only: avse_stream_supported's rule plus 1 <= stride <= video_frames (else AVSE_ERR_INVALID),
+ * frames_per_slice % video_frames == 0 and video_frames 5 or 6 (else AVSE_ERR_UNSUPPORTED). */
+typedef struct avse_slide avse_slide;
+int avse_slide_supported(int sr, int n_fft, int hop, int frames_per_slice, int video_frames, int stride, int n_mels,
+                         float fmin, float fmax);
+/* All state and scratch is sized here (the forward's through avse_ctx_reserve_weights(ctx, weights, n_streams *
+ * max_windows)); create synchronises, later calls allocate nothing.  max_windows M, 1 .. 80: the most windows one call
+ * may complete per stream, and how far (in windows) either input may run ahead of the other.  video_frames is the
+ * weights'. */
+int avse_slide_create(avse_ctx* ctx, const avse_weights* weights, int64_t n_streams, int sr, int n_fft, int hop,
+                      int frames_per_slice, int stride, int n_mels, float fmin, float fmax, float amin, float top_db,
+                      int video_dtype, int64_t max_windows, avse_slide** out);
+/* HOST: the totals above.  s == NULL is n_fft 640, hop 160, 20 frames and 5 video frames per slice; avse_slide_counts_geom
+ * takes the geometry itself.  Outputs nullable.  AVSE_ERR_INVALID: negative counts, a stride outside 1 .. video_frames,
+ * flushed with n > H q f. */
+int avse_slide_counts(const avse_slide* s, int stride, int64_t n_samples, int64_t n_video_frames, int flushed,
+                      int64_t* frames, int64_t* windows, int64_t* predicted, int64_t* emitted);
+int avse_slide_counts_geom(int n_fft, int hop, int frames_per_slice, int video_frames, int stride, int64_t n_samples,
+                           int64_t n_video_frames, int flushed, int64_t* frames, int64_t* windows, int64_t* predicted,
+                           int64_t* emitted);
+/* The only push.  Stream b receives n_new[b] samples (from samples + sample_off[b]) and f_new[b] video frames (packed
+ * stream-major in `video`, [sum f_new][128][128] in the session's video dtype, 4-byte aligned) and is closed when flush
+ * && flush[b]; lock-step use is the same counts for every stream.  out [B][out_stride] receives host_n_out[b] samples
+ * per stream; mel_db / pred_db (nullable) receive, packed [sum host_w_new][n_mels][spf], the whole window the network
+ * saw and predicted for every window the call completed, not only the kept columns.
+ * Refused with AVSE_ERR_INVALID and "stream b: ..." naming the first offending stream, before any GPU work and with
+ * the session exactly as it was: negative or too large counts; input or a flush after the stream's flush; a flush with
+ * n > H q f; more than max_windows windows completed by the call; after the call, the samples completing more than
+ * max_windows windows that the video does not (wa - windows > M), or the video more than the samples
+ * (wv - windows > M); out NULL or out_stride below what a stream emits.  A failure after the launches have begun
+ * marks the session broken (AVSE_ERR_INVALID until avse_slide_reset).  Asynchronous on `stream`; never synchronises
+ * apart from the staging-slot wait of avse_stream_push_each; not capturable into a graph.  With AVSE_F32_SPLIT weights
+ * the forward is the unchecked one and the guard bits accumulate in the context. */
+int avse_slide_push_each(avse_slide* s, const float* samples, const int64_t* sample_off /* HOST [B] */,
+                         const int64_t* n_new /* HOST [B] */, const void* video_frames,
+                         const int64_t* f_new /* HOST [B] */, const uint8_t* flush /* HOST [B], nullable */,
+                         const float* vnorm_mean, const float* vnorm_std, float* out, int64_t out_stride,
+                         int64_t* host_n_out /* HOST [B] */, float* mel_db /* nullable */, float* pred_db /* nullable */,
+                         int64_t* host_w_new /* HOST [B], nullable */, void* stream);
+/* The streams with which[b] != 0 (all of them: avse_slide_reset, which also mends a broken session) go back to the
+ * state after create, ordered on `stream`. */
+int avse_slide_reset_each(avse_slide* s, const uint8_t* which /* HOST [B] */, void* stream);
+int avse_slide_reset(avse_slide* s, void* stream);
+/* HOST: per stream, samples and video frames received and whether it is flushed.  Outputs nullable. */
+int avse_slide_state(const avse_slide* s, int64_t* n_samples, int64_t* n_video_frames, uint8_t* flushed);
+void avse_slide_destroy(avse_slide* s);
 
 /* ---- resampling: any sample rate around a session ----
  * y = scipy.signal.resample_poly(x, up, down) with its defaults, up / down = (sr_out / g) / (sr_in / g),
