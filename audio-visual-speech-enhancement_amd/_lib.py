@@ -157,6 +157,14 @@ SIGNATURES = {
     "avse_slide_reset": (_int, [_c_void_p, _c_void_p]),
     "avse_slide_state": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "avse_slide_destroy": (None, [_c_void_p]),
+    # offline sliding (ragged, host count arrays): windows(ctx, mel, host n_frames, host n_slices, n_utt, spf, F, stride,
+    # n_mels, top_db, net_in, stream); video_windows(ctx, video, video_dtype, host n_slices, n_utt, F, stride, w0, n, out,
+    # stream); keep(ctx, pred, host n_slices, n_utt, spf, F, stride, n_mels, out, stream)
+    "avse_slide_windows": (_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _flt, _c_void_p,
+                                  _c_void_p]),
+    "avse_slide_video_windows": (_int, [_c_void_p, _c_void_p, _int, _c_void_p, _i64, _int, _int, _i64, _i64, _c_void_p,
+                                        _c_void_p]),
+    "avse_slide_keep": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, _int, _int, _c_void_p, _c_void_p]),
     # resampling: supported(sr_in, sr_out); counts(sr_in, sr_out, n_in, flushed, host n_out); ragged(ctx, sig, host
     # sig_off, host n_samples, n_utt, sr_in, sr_out, out, host out_off, stream); resampler create(ctx, n_streams, sr_in,
     # sr_out, out); push_each(r, samples, host sample_off, host n_new, host flush, out, out_stride, host n_out, stream);

@@ -1349,6 +1349,118 @@ def slide_state(session):
     return n.tolist(), f.tolist(), [bool(x) for x in fl]
 
 
+# ---- offline sliding: whole utterances through a flushed sliding session's windows ----
+def _slide_geometry(n_slices, frames_per_slice, video_frames, stride):
+    """The host checks the three offline sliding calls share -> (n_slices as int64 [U], spf, F, stride)."""
+    spf, F, s = int(frames_per_slice), int(video_frames), int(stride)
+    if spf < 1 or F < 1 or spf % F:
+        raise ValueError(f"frames_per_slice {spf} must be a positive multiple of video_frames {F}")
+    if not 1 <= s <= F:
+        raise ValueError(f"the stride must be 1 .. {F} (video_frames), got {s}")
+    ns = np.ascontiguousarray(np.asarray(n_slices), dtype=np.int64)
+    if ns.ndim != 1:
+        raise ValueError("n_slices must be 1-D")
+    if ns.size and ns.min() < 0:
+        raise ValueError("negative counts")
+    return ns, spf, F, s
+
+
+def slide_window_counts(n_slices, frames_per_slice=20, video_frames=5, stride=1):
+    """Per utterance of n_slices[u] slices, (windows W_u, predicted columns P_u) of the flushed sliding stream, as int64
+    arrays: avse_slide_counts_geom's totals (the hop and n_fft do not enter them)."""
+    ns, spf, F, s = _slide_geometry(n_slices, frames_per_slice, video_frames, stride)
+    lengths, inverse = np.unique(ns, return_inverse=True)      # one library call per distinct length
+    wp = np.array([slide_counts(0, F * S, True, stride=s, geometry=(2, 1, spf, F))[1:3] for S in lengths.tolist()],
+                  dtype=np.int64).reshape(-1, 2)
+    return wp[inverse, 0], wp[inverse, 1]
+
+
+def slide_windows(mel_packed, n_frames, n_slices, frames_per_slice=20, video_frames=5, stride=1, n_mels=80, top_db=80.0):
+    """avse_slide_windows: the network's audio input for the windows of a ragged batch.  mel_packed: the 1-D packed
+    UNCLAMPED [n_mels, T_u] blocks (spectrogram_ragged(top_db=None, frames_per_slice=0)), n_frames the T_u, n_slices the
+    S_u.  Returns [sum W_u, n_mels, frames_per_slice]: window j of an utterance is its frames [q s j, q s j + spf)
+    clamped at (the maximum of its frames up to the window's last) - top_db (None: no clamp)."""
+    _dev_f32(mel_packed, "mel_packed")
+    ns, spf, F, s = _slide_geometry(n_slices, frames_per_slice, video_frames, stride)
+    nf = np.ascontiguousarray(np.asarray(n_frames), dtype=np.int64)
+    if nf.shape != ns.shape:
+        raise ValueError("n_frames and n_slices must be of one size")
+    if nf.size and (nf < spf * ns).any():
+        raise ValueError("an utterance has fewer frames than its slices' windows read")
+    if mel_packed.dim() != 1 or int(nf.sum()) * n_mels != mel_packed.numel():
+        raise ValueError("n_frames do not add up to the packed buffer")
+    W, _ = slide_window_counts(ns, spf, F, s)
+    dev = mel_packed.device
+    out = torch.empty((int(W.sum()), n_mels, spf), dtype=torch.float32, device=dev)
+    if out.numel():
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_slide_windows(
+                ctx.handle, _lib.ptr(mel_packed), nf.ctypes.data, ns.ctypes.data, int(ns.size), spf, F, s, int(n_mels),
+                float(-1.0 if top_db is None else top_db), _lib.ptr(out), _lib.stream_handle(dev)), "avse_slide_windows")
+    return out
+
+
+def slide_video_windows(video, n_slices, stride=1, w0=0, n=None, out=None):
+    """avse_slide_video_windows: the network's video input for windows [w0, w0 + n) of the batch's window list (n None:
+    to its end).  video: [sum S_u, 128, 128, F] slices, float32 or uint8.  Returns [n, 128, 128, F] of the same dtype
+    (into the first n rows of `out` when given): window j of an utterance is its frames s j .. s j + F - 1."""
+    _dev_video(video, "video")
+    if video.dim() != 4 or tuple(video.shape[1:3]) != (128, 128):
+        raise ValueError("video must be [slices, 128, 128, frames]")
+    F = int(video.shape[3])
+    ns, _, _, s = _slide_geometry(n_slices, F, F, stride)
+    if int(ns.sum()) != video.shape[0]:
+        raise ValueError("n_slices do not add up to the video's slices")
+    if F not in (5, 6):
+        raise ValueError("video windows are built for 5 and 6 video frames per slice")
+    W, _ = slide_window_counts(ns, F, F, s)
+    total = int(W.sum())
+    w0 = int(w0)
+    n = total - w0 if n is None else int(n)
+    if w0 < 0 or n < 0 or w0 + n > total:
+        raise ValueError(f"windows [{w0}, {w0 + n}) lie outside the batch's {total} windows")
+    if out is None:
+        out = torch.empty((n,) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
+    else:
+        _dev_video(out, "out")
+        if out.dtype != video.dtype or out.device != video.device or out.dim() != 4 or out.shape[0] < n or \
+                tuple(out.shape[1:]) != tuple(video.shape[1:]):
+            raise ValueError(f"out must hold {n} windows of the video's shape, dtype and device")
+    if n:
+        dev = video.device
+        ctx = _lib.context(dev)
+        vdt = _lib.AVSE_VIDEO_U8 if video.dtype == torch.uint8 else _lib.AVSE_VIDEO_F32
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_slide_video_windows(
+                ctx.handle, _lib.ptr(video), vdt, ns.ctypes.data, int(ns.size), F, s, w0, n, _lib.ptr(out),
+                _lib.stream_handle(dev)), "avse_slide_video_windows")
+    return out[:n]
+
+
+def slide_keep(pred, n_slices, video_frames=5, stride=1):
+    """avse_slide_keep: the kept columns of the predicted windows pred [sum W_u, n_mels, spf] -> (the 1-D packed
+    [n_mels, P_u] blocks, the P_u): istft_ragged's 1-D input and its counts."""
+    _dev_f32(pred, "pred")
+    if pred.dim() != 3:
+        raise ValueError("pred must be [windows, n_mels, frames_per_slice]")
+    n_mels, spf = int(pred.shape[1]), int(pred.shape[2])
+    ns, spf, F, s = _slide_geometry(n_slices, spf, video_frames, stride)
+    W, P = slide_window_counts(ns, spf, F, s)
+    if int(W.sum()) != pred.shape[0]:
+        raise ValueError("n_slices do not add up to pred's windows")
+    dev = pred.device
+    total = int(P.sum()) * n_mels
+    packed = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    if total:
+        ctx = _lib.context(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().avse_slide_keep(
+                ctx.handle, _lib.ptr(pred), ns.ctypes.data, int(ns.size), spf, F, s, n_mels, _lib.ptr(packed),
+                _lib.stream_handle(dev)), "avse_slide_keep")
+    return packed[:total], P
+
+
 def resample_supported(sr_in, sr_out, return_message=False):
     """avse_resample_supported (host only, no GPU): 0 when sr_in -> sr_out is served (max(up, down) <= 640 after
     reduction), else the status resample / resampler_create would raise with (3: unsupported, 1: invalid).

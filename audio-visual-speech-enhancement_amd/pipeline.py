@@ -38,13 +38,27 @@ def _has_blank(video):
 class Enhancer:
     """Batched predict path for one device: `enhancer(signals, video, vmean, vstd)` -> enhanced signals."""
 
-    def __init__(self, weights, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, chunk=1024):
+    def __init__(self, weights, video_frame_rate=25.0, sample_rate=16000, slice_duration_ms=200, chunk=1024, stride=None):
+        """stride (None, or 1 .. the video frames per slice): with a stride the object computes what a flushed
+        SlidingStreamEnhancer of that stride does, at batch throughput: network windows at every
+        stride-th video frame, each clamped at its causal floor, window 0's columns and the newest q * stride of every
+        later window kept.  Its outputs are hop * (predicted - 1) samples per utterance, predicted =
+        spf + q stride ((F (S - 1)) // stride): shorter than the slice path's where the stride does not divide
+        F (S - 1).  `chunk` then counts windows, and video_present is refused (a partly blank window has no rule yet)."""
         self.weights = weights
         self.fps = float(video_frame_rate)
         self.sr = int(sample_rate)
         self.slice_ms = slice_duration_ms
         self.chunk = int(chunk)
         self.range_bits = 0
+        self.stride = None if stride is None else int(stride)
+        if self.stride is not None:
+            F = int(round(self.fps * float(slice_duration_ms) / 1000))      # video frames per slice of this geometry
+            if not 1 <= self.stride <= F:
+                raise ValueError(f"stride must be 1 .. {F} (the video frames per slice), got {stride}")
+            if self.chunk < 1:
+                raise ValueError("chunk must be positive")
+        self.staged_video_bytes = 0      # stride: bytes of the largest chunk of video windows the last call staged
 
     def geometry(self, n_video_slices):
         return data_processor.frame_geometry(self.sr, self.slice_ms, n_video_slices, self.fps)
@@ -80,9 +94,15 @@ class Enhancer:
         video_present: [U, S] bool (host), False where a slice has no video (ops.forward's video_present: the slice is
         predicted from the all-zero normalised video; the network was not trained for that, and the quality of its
         audio-only estimate is unmeasured).  video keeps its full shape; the contents of such slices are never read."""
+        if self.stride is not None and video_present is not None:
+            raise ValueError("video_present is not built with a stride: a partly blank window has no rule")
         if signals.dim() != 2 or video.dim() != 5 or video.shape[0] != signals.shape[0]:
             raise ValueError("signals must be [U, L] and video [U, S, H, W, frames] with the same U")
         U, S = video.shape[0], video.shape[1]
+        if self.stride is not None:      # [U, hop * (predicted - 1)]: the rows of enhance_ragged's packed buffer
+            outs = self._slide(list(signals), list(video), vmean, vstd, timings,
+                               frames=video.contiguous().view((U * S,) + tuple(video.shape[2:])))
+            return torch.stack(outs)
         g = self.geometry(S)
         if g["n_slices"] != S:
             raise ValueError(f"{S} video slices but the audio geometry gives {g['n_slices']} spectrogram slices")
@@ -141,13 +161,102 @@ class Enhancer:
                            istft_ms=ev[2].elapsed_time(ev[3]))
         return out
 
-    def enhance_ragged(self, signals, videos, vmean=None, vstd=None, video_present=None):
-        """__call__ for utterances of mixed lengths: signals[u] is [L_u] float32, videos[u] [S_u, 128, 128, frames]
+    def _slide(self, signals, videos, vmean, vstd, timings, return_spectrograms=False, frames=None):
+        """The strided path of __call__ / enhance_ragged for signals[u] [L_u] and videos[u]
+        [S_u, 128, 128, F]: one unclamped ragged STFT, the causal clamp and window gather (ops.slide_windows), forwards
+        over chunks of <= `chunk` windows (which may span utterances) with each chunk's video windows gathered into one
+        staging buffer (ops.slide_video_windows), the kept columns (ops.slide_keep), one ragged ISTFT.  -> a list of
+        [hop * (predicted_u - 1)] views of one buffer; with return_spectrograms (out, net_in, pred, W)."""
+        if len(signals) != len(videos) or not signals:
+            raise ValueError("signals and videos must be non-empty lists of one length")
+        geo = [self.geometry(int(v.shape[0])) for v in videos]
+        g0 = geo[0]
+        spf, F = g0["spectrogram_samples_per_slice"], self.weights.F
+        fixed = []
+        for u, (s, v, g) in enumerate(zip(signals, videos, geo)):
+            if s.dim() != 1 or v.dim() != 4:
+                raise ValueError(f"signals[{u}] must be [L] and videos[{u}] [S, H, W, frames]")
+            if v.shape[0] < 1 or g["n_slices"] != v.shape[0]:
+                raise ValueError(f"{v.shape[0]} video slices but the audio geometry gives {g['n_slices']} spectrogram slices")
+            if spf != self.weights.T or v.shape[-1] != F:
+                raise ValueError(f"{self.fps} fps gives [80, {spf}] slices with {v.shape[-1]} video frames; the weights "
+                                 f"are for [80, {self.weights.T}] x {self.weights.F} frames (build the network for this rate)")
+            L = g["signal_length"]
+            if s.shape[0] != L:
+                s = torch.nn.functional.pad(s, (0, max(0, L - s.shape[0])))[:L]
+            fixed.append(s.contiguous())
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timings is not None else None
+
+        def mark(i):
+            if ev:
+                ev[i].record()
+        mark(0)
+        kw = dict(sample_rate=self.sr, n_fft=g0["n_fft"], hop_length=g0["hop_length"], n_mels=data_processor.N_MELS,
+                  fmin=data_processor.MEL_FMIN, fmax=data_processor.MEL_FMAX)
+        un, T, _, stft, sviews = ops.spectrogram_ragged(fixed, top_db=None, frames_per_slice=0, return_stft=True, **kw)
+        mark(1)
+        slices = np.array([int(v.shape[0]) for v in videos], dtype=np.int64)
+        clips = ops.slide_windows(un, T, slices, frames_per_slice=spf, video_frames=F, stride=self.stride,
+                                  n_mels=data_processor.N_MELS)
+        mark(2)
+        n = clips.shape[0]
+        if frames is None:      # (__call__ hands over its batch as it stands)
+            frames = torch.cat(videos) if len(videos) > 1 else videos[0].contiguous()
+        pred = torch.empty_like(clips)
+        stage = torch.empty((min(n, self.chunk),) + tuple(frames.shape[1:]), dtype=frames.dtype, device=frames.device)
+        self.staged_video_bytes = stage.numel() * stage.element_size()
+        split = self.weights.dtype == _lib.AVSE_F32_SPLIT
+        pipe = ops.RangePipeline(self.weights.ctx) if split else None
+        if split:
+            self.weights.ctx.set_aside_range()
+
+        def chunk(a, b, checked):      # the staging buffer is reused in stream order; a recompute gathers its chunk again
+            v = ops.slide_video_windows(frames, slices, stride=self.stride, w0=a, n=b - a, out=stage)
+            ops.forward(self.weights, clips[a:b], v, vmean, vstd, out=pred[a:b], checked=checked)
+
+        for a in range(0, n, self.chunk):
+            b = min(n, a + self.chunk)
+            chunk(a, b, False)
+            if split:
+                pipe.submit(lambda a=a, b=b: chunk(a, b, True))
+        mark(3)
+
+        def istft():
+            kept, P = ops.slide_keep(pred, slices, video_frames=F, stride=self.stride)
+            mark(4)
+            return ops.istft_ragged(kept, P, stft, [sh[1] for sh in sviews.shapes], **kw)
+        out = istft()
+        self.range_bits = 0
+        if split:
+            self.range_bits = pipe.drain()
+            if pipe.recomputed:      # a chunk was redone after the ISTFT had been queued: redo the ISTFT after it
+                out = istft()
+        if ev:
+            ev[5].record()
+            ev[5].synchronize()
+            timings.update(stft_ms=ev[0].elapsed_time(ev[1]), forward_ms=ev[2].elapsed_time(ev[3]),
+                           istft_ms=ev[4].elapsed_time(ev[5]), windows_ms=ev[1].elapsed_time(ev[2]),
+                           keep_ms=ev[3].elapsed_time(ev[4]))
+        if return_spectrograms:
+            return out, clips, pred, ops.slide_window_counts(slices, spf, F, self.stride)[0]
+        return out
+
+    def enhance_ragged(self, signals, videos, vmean=None, vstd=None, video_present=None, return_spectrograms=False):
+        """With a stride: the same arguments -> a list of [hop * (predicted_u - 1)] tensors (views of one buffer), each
+        the bits of that utterance alone; return_spectrograms (stride only) -> (that list, the windows' inputs
+        [sum W_u, 80, spf], their predictions, W_u).  Without a stride:
+        __call__ for utterances of mixed lengths: signals[u] is [L_u] float32, videos[u] [S_u, 128, 128, frames]
         (float32 or uint8, one dtype for all).  One ragged STFT, the forward over the concatenated clips of all
         utterances (in chunks of <= `chunk`, which may span utterances), one ragged ISTFT.  Each signal is padded /
         truncated to its own S_u slices first, as __call__ does for the batch.  Returns a list of [hop * (S_u * spf - 1)]
         tensors (views of one buffer), each the bits __call__ gives for that utterance alone.
         video_present: one bool sequence [S_u] per utterance, as __call__'s."""
+        if self.stride is not None:
+            if video_present is not None:
+                raise ValueError("video_present is not built with a stride: a partly blank window has no rule")
+            return self._slide(list(signals), list(videos), vmean, vstd, None, return_spectrograms=return_spectrograms)
+        if return_spectrograms:
+            raise ValueError("return_spectrograms is for an Enhancer with a stride")
         signals, videos = list(signals), list(videos)
         if len(signals) != len(videos) or not signals:
             raise ValueError("signals and videos must be non-empty lists of one length")

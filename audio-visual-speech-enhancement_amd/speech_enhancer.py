@@ -297,15 +297,41 @@ def sample_groups(samples):
     return list(groups.values())
 
 
+def check_stride(stride, samples):
+    """`predict --stride`: ValueError unless 1 <= stride <= the video frames per slice of every sample."""
+    frames = sorted({int(smp.video_samples.shape[-1]) for smp in samples})
+    if stride < 1 or (frames and stride > frames[0]):
+        raise ValueError("the stride must be 1 .. %s (the samples' video frames per slice), got %d"
+                         % (frames[0] if frames else "F", stride))
+
+
+def strided_signals(dw, group, frames, stride, chunk, vmean, vstd):
+    """`predict --stride`: the waveforms of the group's samples from pipeline.Enhancer(stride=stride), the flushed sliding
+    session's output (network windows at every stride-th video frame), computed from the mixtures and `frames`
+    ([sum S_u, 128, 128, F] on the device, the samples' slices in order) -> a list of numpy arrays, each
+    hop * (predicted - 1) samples."""
+    import torch
+    from .pipeline import Enhancer
+    sr, fps = group[0].mixed_signal.get_sample_rate(), group[0].video_frame_rate
+    enhancer = Enhancer(dw, video_frame_rate=fps, sample_rate=sr, chunk=chunk, stride=stride)
+    sigs = [torch.from_numpy(np.asarray(g.mixed_signal.get_data(channel_index=0)).astype(np.float32)).to(frames.device)
+            for g in group]
+    videos = list(frames.split([int(g.video_samples.shape[0]) for g in group]))
+    return [y.cpu().numpy() for y in enhancer.enhance_ragged(sigs, videos, vmean, vstd)]
+
+
 class BatchPredictor:
     """predict + evaluate + reconstruct of a group of equal-shape samples as one batch on one device: one forward over
     all their slices (in chunks of <= `chunk` clips), one MSE per sample (the avse_mse of the per-sample path), one
-    STFT of the stacked mixtures for the phase and one ISTFT.  Each result equals predict_one's bit for bit."""
+    STFT of the stacked mixtures for the phase and one ISTFT.  Each result equals predict_one's bit for bit.
+    stride (None, or 1 .. the video frames per slice): the signals are pipeline.Enhancer(stride=stride)'s instead
+    (strided_signals); the losses stay the slice-based ones."""
 
-    def __init__(self, network, video_normalizer=None, chunk=1024):
+    def __init__(self, network, video_normalizer=None, chunk=1024, stride=None):
         self.network = network
         self.video_normalizer = video_normalizer
         self.chunk = int(chunk)
+        self.stride = stride
 
     def __call__(self, group):
         import torch
@@ -331,6 +357,9 @@ class BatchPredictor:
         pred = pred.view(U, S, nm, T)
         losses = [ops.mse(pred[u], speech[u]) for u in range(U)]
         sr, fps = group[0].mixed_signal.get_sample_rate(), group[0].video_frame_rate
+        if self.stride is not None:
+            ys = strided_signals(dw, group, frames, self.stride, self.chunk, m, s)
+            return [(float(losses[u].item()), AudioSignal(ys[u], sr)) for u in range(U)]
         n_fft = int(float(sr) / fps)
         hop = int(n_fft / 4)
         sig = torch.from_numpy(np.stack([np.asarray(g.mixed_signal.get_data(channel_index=0)) for g in group])
@@ -345,12 +374,14 @@ class BatchPredictor:
 class RaggedBatchPredictor:
     """BatchPredictor without the split by length: samples that share frame rate, sample rate and slice shape run as
     one batch whatever their slice counts and mixture lengths — one forward over all their slices, one MSE per sample,
-    one ragged STFT of the mixtures for the phase and one ragged ISTFT.  Each result equals predict_one's bit for bit."""
+    one ragged STFT of the mixtures for the phase and one ragged ISTFT.  Each result equals predict_one's bit for bit.
+    stride: as BatchPredictor's."""
 
-    def __init__(self, network, video_normalizer=None, chunk=1024):
+    def __init__(self, network, video_normalizer=None, chunk=1024, stride=None):
         self.network = network
         self.video_normalizer = video_normalizer
         self.chunk = int(chunk)
+        self.stride = stride
 
     @staticmethod
     def groups(samples):
@@ -391,6 +422,9 @@ class RaggedBatchPredictor:
         ends = np.cumsum(S)
         losses = [ops.mse(pred[int(e - k):int(e)], speech[int(e - k):int(e)]) for e, k in zip(ends, S)]
         sr, fps = group[0].mixed_signal.get_sample_rate(), group[0].video_frame_rate
+        if self.stride is not None:
+            ys = strided_signals(dw, group, frames, self.stride, self.chunk, m, s)
+            return [(float(losses[u].item()), AudioSignal(ys[u], sr)) for u in range(U)]
         n_fft = int(float(sr) / fps)
         hop = int(n_fft / 4)
         kw = dict(sample_rate=sr, n_fft=n_fft, hop_length=hop, n_mels=data_processor.N_MELS,
@@ -465,6 +499,8 @@ def _launch_ranks(n, argv):
 
 
 def predict(args):
+    if args.stride is not None and args.stride < 1:      # before any rank starts; the upper bound needs the samples
+        raise SystemExit("predict --stride: the stride must be at least 1, got %d" % args.stride)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_launch_ranks(args.gpus, args.argv))
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -494,12 +530,22 @@ def predict(args):
     network = SpeechEnhancementNetwork.load(model_path, compute_dtype=args.dtype)
     video_normalizer = data_processor.VideoNormalizer.load(layout.normalizer_file(args.model))
     samples = load_preprocessed_blob(layout.preprocessed(args.data_name))
-    if args.per_sample:
+    fallback = lambda smp: predict_one(network, video_normalizer, smp)  # noqa: E731
+    if args.stride is not None:
+        try:      # before the loop: predict_samples would log the refusal once per sample, skip them all and exit 0
+            check_stride(args.stride, samples)
+        except ValueError as e:
+            raise SystemExit("predict --stride: %s" % e)
+        # the strided signal comes from the batched predictor alone: --per-sample and the retry of a failed group run
+        # it one sample at a time (each utterance of a ragged batch is the bits of its own call)
+        strided = RaggedBatchPredictor(network, video_normalizer, stride=args.stride)
+        fallback = lambda smp: strided([smp])[0]  # noqa: E731
+        predictor = (lambda group: [strided([smp])[0] for smp in group]) if args.per_sample else strided
+    elif args.per_sample:
         predictor = lambda group: [predict_one(network, video_normalizer, smp) for smp in group]  # noqa: E731
     else:
         predictor = RaggedBatchPredictor(network, video_normalizer)
-    losses = predict_samples(samples, predictor, run_dir, world, rank,
-                             fallback=lambda smp: predict_one(network, video_normalizer, smp))
+    losses = predict_samples(samples, predictor, run_dir, world, rank, fallback=fallback)
     if rank == 0:
         for i, smp in enumerate(samples):
             print("predicting (%s, %s)..." % (smp.video_file_path, smp.noise_file_path))
@@ -545,6 +591,10 @@ def main(argv=None):
     q.add_argument("-g", "--gpus", type=int, default=1)
     q.add_argument("--dtype", default="float32_split", choices=["float32_split", "float32", "bfloat16"])
     q.add_argument("--per-sample", action="store_true", help="one forward / STFT / ISTFT per sample (unbatched)")
+    q.add_argument("--stride", type=int, default=None,
+                   help="network windows at every STRIDE-th video frame (1 .. frames per slice): enhanced.wav is the "
+                        "flushed sliding session's output; the printed loss stays the slice-based one, so the slice "
+                        "path's forward runs as well (F / STRIDE + 1 times the forwards of a run without the flag)")
     q.set_defaults(func=predict)
 
     argv = sys.argv[1:] if argv is None else list(argv)

@@ -41,7 +41,10 @@ extern "C" {
  *    avse_retimer_push_each, avse_retimer_reset_each, avse_retimer_state, avse_retimer_destroy, avse_forward_mixed,
  *    avse_forward_mixed_checked, avse_stream_push_each_mixed, avse_stream_blank, avse_slide_supported,
  *    avse_slide_create, avse_slide_counts, avse_slide_counts_geom, avse_slide_push_each, avse_slide_reset_each,
- *    avse_slide_reset, avse_slide_state, avse_slide_destroy */
+ *    avse_slide_reset, avse_slide_state, avse_slide_destroy, avse_slide_windows, avse_slide_video_windows,
+ *    avse_slide_keep (K22's three entry points too stay under version 3, as every addition before them: they are new
+ *    symbols, nothing existing changed, and the host tests of each earlier addition pin avse_abi_version() == 3; a
+ *    binding that needs them asks for the symbols) */
 #define AVSE_ABI_VERSION 3
 
 enum avse_status {
@@ -611,6 +614,48 @@ int avse_slide_reset(avse_slide* s, void* stream);
 /* HOST: per stream, samples and video frames received and whether it is flushed.  Outputs nullable. */
 int avse_slide_state(const avse_slide* s, int64_t* n_samples, int64_t* n_video_frames, uint8_t* flushed);
 void avse_slide_destroy(avse_slide* s);
+
+/* ---- offline sliding enhancement: whole utterances through the windows of a flushed sliding session ----
+ * What a sliding session computes for a stream that is fed and flushed, for a RAGGED batch of whole utterances at batch
+ * throughput: avse_spectrogram_ragged(top_db < 0, frames_per_slice 0) -> avse_slide_windows -> avse_forward* over chunks of
+ * windows, each chunk's video from avse_slide_video_windows -> avse_slide_keep -> avse_istft_ragged(frames_per_slice 0).
+ * The three calls here move values and take maxima; they round nothing.  spf = frames_per_slice, F = video_frames,
+ * q = spf / F, s = stride.  Utterance u has S_u = n_slices[u] slices, f = F S_u video frames, and
+ *   W_u = S_u > 0 ? (f - F) / s + 1 : 0       windows: avse_slide_counts_geom(.., n_samples 0, f, flushed 1)'s
+ *   P_u = W_u > 0 ? spf + q s (W_u - 1) : 0   predicted columns, likewise
+ * The windows of all utterances, in utterance order, are "the window list" (sum W_u entries).  S_u == 0 is legal and
+ * yields nothing.  Every count array is HOST [n_utt] int64.  All three calls are asynchronous on `stream`; their tables go
+ * through context scratch, which grows outside a stream capture only, as avse_spectrogram_ragged's (and a captured call is
+ * replayed before the next ragged or sliding call on the context).
+ * Refused with AVSE_ERR_INVALID before any GPU work: a NULL pointer argument, n_utt < 0, a negative count, spf or F below
+ * 1 or spf % F != 0, a stride outside 1 .. F, an n_frames[u] below q F S_u, a window range outside the window list, a
+ * device pointer that is not 16-byte aligned, and a batch too large (n_mels times an utterance's frames, the windows of
+ * the batch times 4, or an item table past 2^31 - 1).
+ *
+ * avse_slide_windows: the network's audio input.
+ *   mel_db    per utterance [n_mels][n_frames[u]] UNCLAMPED mel-dB, concatenated: what avse_spectrogram_ragged writes
+ *             with top_db < 0 and frames_per_slice 0 (n_frames[u] = q F S_u + 1 for a signal of hop q F S_u samples)
+ *   net_in    [sum W_u][n_mels][spf]: window j of utterance u is its frames [q s j, q s j + spf), clamped from below at
+ *             (the maximum of its frames 0 .. q s j + spf - 1) - top_db: the causal floor of avse_slide_push_each
+ *             (top_db < 0: no clamp).  One block per utterance forms the prefix maximum of the frames' maxima along
+ *             time in chunks of 256 frames with a carry; maxima are exact, so the bits do not depend on that shape. */
+int avse_slide_windows(avse_ctx* ctx, const float* mel_db, const int64_t* n_frames, const int64_t* n_slices,
+                       int64_t n_utt, int frames_per_slice, int video_frames, int stride, int n_mels, float top_db,
+                       float* net_in, void* stream);
+/* avse_slide_video_windows: the network's video input for windows [w0, w0 + n) of the window list, so that a forward over
+ * a chunk of windows stages that chunk's video only.
+ *   video     [sum S_u][128][128][F] slices, float32 or uint8 (avse_video_dtype), the utterances' slices consecutive
+ *   out       [n][128][128][F] in the same dtype: out[w][y][x][i] = video[slice (s j + i) / F of the utterance][y][x]
+ *             [(s j + i) % F], j the window's index within its utterance
+ * F 5 and 6 are built (else AVSE_ERR_UNSUPPORTED); whole 16-byte vectors in and out for both dtypes. */
+int avse_slide_video_windows(avse_ctx* ctx, const void* video, int video_dtype, const int64_t* n_slices, int64_t n_utt,
+                             int video_frames, int stride, int64_t w0, int64_t n, void* out, void* stream);
+/* avse_slide_keep: the kept columns of the predicted windows.
+ *   pred_db   [sum W_u][n_mels][spf]: the forward's output for the window list
+ *   mel_db    per utterance [n_mels][P_u], concatenated (avse_istft_ragged's frames_per_slice 0 layout, n_frames = P_u):
+ *             all spf columns of window 0, then the last q s columns of each later window */
+int avse_slide_keep(avse_ctx* ctx, const float* pred_db, const int64_t* n_slices, int64_t n_utt, int frames_per_slice,
+                    int video_frames, int stride, int n_mels, float* mel_db, void* stream);
 
 /* ---- resampling: any sample rate around a session ----
  * y = scipy.signal.resample_poly(x, up, down) with its defaults, up / down = (sr_out / g) / (sr_in / g),
